@@ -1,20 +1,26 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the DSMIL hot paths on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: re-launches itself as N ranks, one per GPU)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]   (N > 1: re-launches itself as N ranks, one per GPU)
+    python bench.py --gpus N --steps K --warmup W --full [--workload ...]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
 Headline (`value`): bags/s of the aggregator on BASELINE.json configs[1] — Camelyon16 weights (C=1), fp32, bags of
-10 000 x 512.  One "step" = `passes_per_step` passes of the hot path (dsmil_agg_forward: instance logits +
+10 000 x 512.  One "step" = 96 passes (HEADLINE_PASSES_PER_STEP) of the hot path (dsmil_agg_forward: instance logits +
 critical-instance arg-max, query MLP on MFMA, attention softmax over instances, weighted value sum, Conv1d bag head)
 over one batch of --bags synthetic bags already resident in HBM; the batch (64 bags = 1.31 GB) is larger than the
-256 MiB Infinity Cache, so every pass streams its features from HBM.  `passes_per_step` is chosen after the warm-up so
-that the timed region (EXACTLY --steps steps between barrier + synchronize on both sides, max over ranks) lasts at
-least --min-seconds (1 s): a 22 ms region cannot be corroborated from outside.  Bags are independent units: with N
-ranks each rank owns its own --bags bags (weak scaling), no data-path collective.
+256 MiB Infinity Cache, so every pass streams its features from HBM.  --warmup W steps, then EXACTLY --steps K steps
+are timed between barrier + synchronize on both sides (max over ranks); `ms_per_step` = that region / K.  Bags are
+independent units: with N ranks each rank owns its own --bags bags (weak scaling), no data-path collective.
 
-Sub-objects of the same JSON line (each measured the same way):
+A plain run does only that and prints the headline line.  --dump-outputs DIR then also writes what the last timed step
+computed: for each of the three batches the outputs of its last pass (classes, prediction_bag, A, B, critical_idx) as
+DIR/batch<i>_<output>.npy; the inputs are seeded, so runs with the same arguments are comparable output for output.
+
+--full adds everything else below (and every option from --bags on needs it): the headline's `roofline`, one-stream
+and lone-bag figures, `cpu_baseline`, and the other legs, whose steps are sized so that each timed region lasts at
+least --min-seconds (1 s).  Sub-objects of the same JSON line (each measured the same way):
   aggregator_bf16  BASELINE configs[2]: TCGA weights (C=2), bf16 feature storage, f32 accumulate
   embedder         configs[3]: IClassifier(ResNet-18-IN) over --patches synthetic 224x224 patches per rank per step;
                    with N ranks ONE RCCL all-gather of the [--patches,512] rows follows inside the step (weak)
@@ -43,8 +49,8 @@ launch stream inside the library.  With several streams a launch's start-to-end 
 contains the kernels co-running with it, so the kernel's OWN duration is measured in a second region right after the
 timed one (same inputs, one pass in flight, 300 passes); the in-region interval is reported beside it.
 `cpu_baseline` is the same forward on this box's host cores.  Prints ONE JSON line (rank 0).  The line is compact by default
-(--verbose adds the explanatory strings and the committed per-kernel tables); `config.legs` and the trailing `summary` key
-repeat every leg's value and roofline fraction so that a truncated stdout tail still carries them.
+(--verbose adds the explanatory strings and the committed per-kernel tables); with --full, `config.legs` and the trailing
+`summary` key repeat every leg's value and roofline fraction so that a truncated stdout tail still carries them.
 """
 import argparse
 import ctypes
@@ -101,6 +107,10 @@ ACT_BYTES_PER_PATCH = (3 * 224 * 224 * 4 + 112 * 112 * 64 * 4          # stem
 
 
 KERNEL_TABLE = "r06_kernel_table.json"   # the latest committed per-kernel table (tools/kernel_table.py)
+# one step of the headline = 96 passes of --bags bags (~56 ms on one MI355X; the default 20 steps time ~1.1 s), whatever
+# --steps is; a multiple of the three batches the default three streams are dealt, so every step passes over each of them
+HEADLINE_PASSES_PER_STEP = 96
+DUMP_LIMIT_BYTES = 63 * 10 ** 6   # --dump-outputs: below 64 MB in all, .npy headers included
 
 
 def _kernel_table(leg):
@@ -214,9 +224,10 @@ class Ctx:
     def timed(self, step, steps, warmup, min_seconds, channel=None, fixed_passes=None):
         """Warm up, pick passes_per_step so the region lasts >= min_seconds, then time EXACTLY `steps` steps
         (each = passes_per_step calls of `step`) between fences; returns (seconds [max over ranks], passes_per_step,
-        kernel_ms_total, launches) — the last two from the library's HIP-event channel when given."""
+        kernel_ms_total, launches) — the last two from the library's HIP-event channel when given.  With `fixed_passes`
+        a step is that many calls whatever --steps is, and the warm-up runs `warmup` such steps."""
         torch = self.torch
-        for _ in range(max(1, warmup)):
+        for _ in range(max(1, warmup) * (fixed_passes or 1)):
             step()
         self.fence()
         if fixed_passes is not None:
@@ -259,8 +270,34 @@ class Ctx:
 # ---------------------------------------------------------------------------------------------------------------
 # aggregator legs (configs[1] fp32 headline, configs[2] bf16 storage)
 # ---------------------------------------------------------------------------------------------------------------
-def aggregator_leg(cx, weights_tag, dtype, single_bag=True):
+def _host_outputs(outs, limit=DUMP_LIMIT_BYTES):
+    """{name: (classes, pred, A, B, idx) tensors} -> {name_field: float32 / float64 host array} within `limit` bytes in all
+    (over it, every array above 1 MB keeps a fixed, seeded sample of its flattened elements, all in the same proportion)."""
+    import numpy as np
+    arrs = {}
+    for name, (classes, pred, A, B, idx) in outs.items():
+        for field, t in (("classes", classes), ("prediction_bag", pred), ("A", A), ("B", B), ("critical_idx", idx)):
+            a = t.detach().cpu().numpy()
+            arrs[f"{name}_{field}"] = a.astype(np.float64 if a.dtype.kind in "iu" else np.float32)
+    big = [k for k, a in arrs.items() if a.nbytes > 10 ** 6]
+    small = sum(a.nbytes for a in arrs.values()) - sum(arrs[k].nbytes for k in big)
+    total = sum(arrs[k].nbytes for k in big)
+    if small + total > limit:
+        rng = np.random.default_rng(0)
+        for k in big:
+            a = arrs[k]
+            n = max(1, int(a.size * (limit - small) / total))
+            arrs[k] = a.ravel()[np.sort(rng.choice(a.size, n, replace=False))]
+    return arrs
+
+
+def aggregator_leg(cx, weights_tag, dtype, single_bag=True, passes_per_step=None, keep_outputs=False):
+    """One aggregator configuration.  Without --full only what the headline needs: the timed region (`passes_per_step`
+    passes per step when given) and the line's value; --full adds the kernel's own time and roofline, the one-stream
+    figure and (single_bag) the lone-bag latency.  keep_outputs: the timed region's last pass over each of its batches,
+    as host arrays, goes to cx.outputs (--dump-outputs)."""
     torch, args, dev = cx.torch, cx.args, cx.dev
+    full = args.full
     import dsmil_wsi_amd.ops as ops
     from dsmil_wsi_amd.synthetic import load_weights
     wnp = load_weights(weights_tag)
@@ -299,19 +336,28 @@ def aggregator_leg(cx, weights_tag, dtype, single_bag=True):
     offsets = ops.offsets_tensor(lengths, dev)
     out = []
     turn = [0]
+    last = {}   # batch index -> the outputs of its latest pass
 
     def one():
         turn[0] += 1
-        return ops.agg_forward(batches[turn[0] % n_batches], lengths, w, offsets=offsets)
+        i = turn[0] % n_batches
+        last[i] = ops.agg_forward(batches[i], lengths, w, offsets=offsets)
+        return last[i]
 
     def step():
         out[:] = pool.run(one) if pool is not None else one()
 
-    dt, inner, kern_ms_tot, launches = cx.timed(step, args.steps, args.warmup, args.min_seconds, channel=0)
-    kern_alone_ms, _ = cx.kernel_alone(one, 0, passes=300)
+    # the HIP-event channel of the dominant kernel only feeds the roofline (--full)
+    dt, inner, kern_ms_tot, launches = cx.timed(step, args.steps, args.warmup, args.min_seconds, channel=0 if full else None,
+                                                fixed_passes=passes_per_step)
+    if keep_outputs:   # (the timed region ended on a device-wide synchronize)
+        cx.outputs = _host_outputs({f"batch{i}": last[i] for i in sorted(last)})
+    kern_alone_ms = None
+    if full:
+        kern_alone_ms, _ = cx.kernel_alone(one, 0, passes=300)
     # the same passes with ONE in flight (no stream pool), beside the pooled headline
     value_1s = None
-    if pool is not None:
+    if pool is not None and full:
         pool.join()
         def step1():
             out[:] = one()
@@ -361,6 +407,10 @@ def aggregator_leg(cx, weights_tag, dtype, single_bag=True):
                        # what the fp32 summation order of the persistent batch kernels is tied to (a constant since round 6:
                        # results do not depend on the box), and the box itself
                        "device_cus": int(cx.L.dsmil_device_cus()), "persistent_grid": int(cx.L.dsmil_agg_persistent_grid(-1))}}
+    if not full:   # the one-stream and lone-bag probes, the kernel's own time and the roofline are --full figures
+        for k in ("value_one_stream", "single_bag_forward_ms", "single_bag_forward_ms_is", "single_bag_forward_best_round_ms"):
+            del line["config"][k]
+        return line
     # The PASS reads the features twice (k_logits_stream: the instance arg-max of dsmil.py:51-53 must be known before any
     # attention score; then the attend kernel): against the single-read bytes of SURVEY §8(d) a pass cannot exceed 0.5 of the HBM
     # roof.  Both fractions of the whole path, on the HBM roof alone:
@@ -1113,6 +1163,11 @@ def _summary(line):
     return out
 
 
+# options of the --full run only: a plain run measures the headline as configured here and nothing else
+FULL_ONLY = ("bags", "rows", "feats", "patches", "workload", "min_seconds", "streams", "streams_bf16", "slide_patches", "e2e_grid",
+             "cpu_seconds", "no_cpu_baseline", "force_collective", "verbose", "no_single_bag")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1142,14 +1197,33 @@ def main():
                          "the default line is compact so that a truncated stdout tail still holds every leg")
     ap.add_argument("--no-single-bag", action="store_true",
                     help="skip the single-bag latency probe (profiling runs: keeps per-kernel averages clean)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the other legs (--workload), CPU baselines, the kernels' own times and "
+                         "rooflines, the one-stream and lone-bag probes; every option above from --bags on needs it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step computed (per batch: classes, prediction_bag, A, B, "
+                         "critical_idx) as DIR/<name>.npy, float32 / float64, below 64 MB in all")
     args = ap.parse_args()
+    if not args.full:
+        given = [a for a in FULL_ONLY if getattr(args, a) != ap.get_default(a)]
+        if given:
+            ap.error("--" + ", --".join(a.replace("_", "-") for a in given) + ": only with --full")
     maybe_self_launch(args)
     wl = {"all": "aggregator,aggregator_bf16,embedder,embedder_half,embedder_bf16,train,slide,slide_half,slide_bf16,slide_h2d,slide100k,decode,slide_jpeg,e2e,e2e_half,slide_jpeg_half,feats_csv", "both": "aggregator,embedder"}.get(args.workload, args.workload)
-    wl = [w for w in wl.split(",") if w]
+    wl = [w for w in wl.split(",") if w] if args.full else ["aggregator"]
+    if args.dump_outputs is not None and "aggregator" not in wl:
+        ap.error("--dump-outputs writes the headline's outputs: --workload must include aggregator")
     cx = Ctx(args)
     line = {}
     if "aggregator" in wl:
-        line = aggregator_leg(cx, "c16", "f32", single_bag=not args.no_single_bag)
+        line = aggregator_leg(cx, "c16", "f32", single_bag=args.full and not args.no_single_bag,
+                              passes_per_step=HEADLINE_PASSES_PER_STEP, keep_outputs=args.dump_outputs is not None)
+    if args.dump_outputs is not None and cx.rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in cx.outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+        del cx.outputs
     subs = {}
     if "train" in wl:   # (the latency-bound legs run before the long throughput legs)
         subs["train_c1"] = train_leg(cx, "c16")
@@ -1197,7 +1271,7 @@ def main():
                 kt = _kernel_table(leg)
                 if obj is not None and kt is not None:
                     obj["kernels"] = kt
-        if not args.no_cpu_baseline and cx.world == 1:   # CPU baselines: rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and cx.world == 1:   # CPU baselines: rank 0 at N = 1 only
             if "aggregator" in wl:
                 line["cpu_baseline"] = cpu_baseline_aggregator("c16", args.rows, args.feats, args.cpu_seconds)
             if "embedder" in line:
@@ -1207,9 +1281,10 @@ def main():
         line = {**{k: line[k] for k in order if k in line}, **{k: v for k, v in line.items() if k not in order}}
         if not args.verbose:
             _strip_prose(line)
-        summ = _summary(line)
-        line.setdefault("config", {})["legs"] = summ     # the driver's parsed record keeps `config` whole
-        line["summary"] = summ                           # ... and the tail of stdout keeps the last key
+        if args.full:   # (a plain line holds the headline alone)
+            summ = _summary(line)
+            line.setdefault("config", {})["legs"] = summ     # the driver's parsed record keeps `config` whole
+            line["summary"] = summ                           # ... and the tail of stdout keeps the last key
         print(json.dumps(line), flush=True)
     if cx.dist is not None:
         cx.dist.barrier()

@@ -60,7 +60,7 @@ def test_bench_under_torchrun_one_rank_with_forced_collectives():
     """The driver's N > 1 launch line with N = 1: torch.distributed.run -> bench.py --gpus 1, slide leg with the packed
     all-gather forced through RCCL."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "slide",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--workload", "slide",
            "--slide-patches", "1024", "--steps", "2", "--warmup", "1", "--force-collective", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -13,7 +13,7 @@ case $stage in
 tests)
   timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/pytest_gpu.log; tail -5 $OUT/pytest_gpu.log;;
 bench)
-  timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -c 3000 $OUT/bench.json; tail -5 $OUT/bench.err;;
+  timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -c 3000 $OUT/bench.json; tail -5 $OUT/bench.err;;
 variants)
   DSMIL_NATIVE_LIB=libdsmil_hip_expt.so timeout 900 python tools/variants.py aggregator base: xe:DSMIL_EXPT=8 mlponly:DSMIL_EXPT=4 xe_mlponly:DSMIL_EXPT=12 novsum:DSMIL_EXPT=1 s9:DSMIL_MLP=s9 > $OUT/variants_agg.log 2>&1; cat $OUT/variants_agg.log;;
 variants2)
@@ -36,14 +36,14 @@ tests_new)
 stamps)
   for e in 68 76; do DSMIL_NATIVE_LIB=libdsmil_hip_trace.so DSMIL_EXPT=$e timeout 300 python tools/stamp.py > $OUT/stamps_$e.log 2>&1; tail -12 $OUT/stamps_$e.log; done;;
 prof_agg)
-  (cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $OUT/trace_agg -o t -- python $R/bench.py --workload aggregator,aggregator_bf16 --streams 1 --steps 4 --warmup 1 --min-seconds 0.1 --no-cpu-baseline --no-single-bag > $OUT/trace_agg.log 2>&1); find $OUT/trace_agg -name "*kernel_stats.csv" | head -2 | xargs -I{} sh -c 'head -12 {}';;
+  (cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $OUT/trace_agg -o t -- python $R/bench.py --full --workload aggregator,aggregator_bf16 --streams 1 --steps 4 --warmup 1 --min-seconds 0.1 --no-cpu-baseline --no-single-bag > $OUT/trace_agg.log 2>&1); find $OUT/trace_agg -name "*kernel_stats.csv" | head -2 | xargs -I{} sh -c 'head -12 {}';;
 prof_emb)
-  (cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $OUT/trace_emb -o t -- python $R/bench.py --workload embedder --streams 1 --steps 3 --warmup 1 --min-seconds 0.1 --no-cpu-baseline > $OUT/trace_emb.log 2>&1); find $OUT/trace_emb -name "*kernel_stats.csv" | head -2 | xargs -I{} sh -c 'head -24 {}';;
+  (cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $OUT/trace_emb -o t -- python $R/bench.py --full --workload embedder --streams 1 --steps 3 --warmup 1 --min-seconds 0.1 --no-cpu-baseline > $OUT/trace_emb.log 2>&1); find $OUT/trace_emb -name "*kernel_stats.csv" | head -2 | xargs -I{} sh -c 'head -24 {}';;
 pmc_agg|pmc_emb)
   W=aggregator,aggregator_bf16; [ $stage = pmc_emb ] && W=embedder
   for c in "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES SQ_BUSY_CYCLES" "FETCH_SIZE" "WRITE_SIZE" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY"; do
     n=$(echo $c | tr ' ' '_' | cut -c1-40)
-    (cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --pmc $c -f csv -d $OUT/${stage}_$n -o p -- python $R/bench.py --workload $W --streams 1 --steps 3 --warmup 1 --min-seconds 0.05 --no-cpu-baseline --no-single-bag > $OUT/${stage}_$n.log 2>&1)
+    (cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --pmc $c -f csv -d $OUT/${stage}_$n -o p -- python $R/bench.py --full --workload $W --streams 1 --steps 3 --warmup 1 --min-seconds 0.05 --no-cpu-baseline --no-single-bag > $OUT/${stage}_$n.log 2>&1)
   done; find $OUT -name "*counter_collection.csv" | head;;
 esac
 done

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/s6
 mkdir -p $OUT
 for t in 0 44 42 24 22; do
-  (cd /tmp && export TMPDIR=/tmp && DSMIL_NATIVE_LIB=libdsmil_hip_expt.so DSMIL_S6_TILE=$t timeout 300 rocprofv3 --kernel-trace -f csv -d $OUT/t$t -o t -- python $R/bench.py --workload embedder --streams 1 --steps 2 --warmup 1 --min-seconds 0.05 --no-cpu-baseline --no-single-bag > $OUT/t$t.log 2>&1)
+  (cd /tmp && export TMPDIR=/tmp && DSMIL_NATIVE_LIB=libdsmil_hip_expt.so DSMIL_S6_TILE=$t timeout 300 rocprofv3 --kernel-trace -f csv -d $OUT/t$t -o t -- python $R/bench.py --full --workload embedder --streams 1 --steps 2 --warmup 1 --min-seconds 0.05 --no-cpu-baseline --no-single-bag > $OUT/t$t.log 2>&1)
   python - $OUT/t$t/t_kernel_trace.csv $t <<'P'
 import csv, sys, collections
 rows = list(csv.DictReader(open(sys.argv[1])))

@@ -20,7 +20,7 @@ for r in range(rounds):   # interleaved rounds: box drift hits every variant ali
     for name, env in specs:
         e = dict(os.environ)
         e.update(env)
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--no-cpu-baseline",
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", workload, "--no-cpu-baseline",
                               "--no-single-bag", "--streams", "1", "--steps", "5", "--warmup", "2", "--min-seconds", "0.4"],
                              env=e, capture_output=True, text=True, timeout=600)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
