@@ -1227,7 +1227,7 @@ __global__ __launch_bounds__(256, (UB == 8 ? 1 : 6)) void k_finish(
     const int kq = tid & 15, tg = tid >> 4;
     constexpr int UA = UB == 8 ? 8 : 4;            // rows per thread in flight of the A pass
     if (!has_k && rbeg >= rend && !ml_out) {   // a block of the grid (sized for the LONGEST bag) with neither rows nor a k-run of this bag
-        if (tid < C * C) pred_part[(((long long)bag * nblk + blockIdx.x) * C) * C + tid] = 0.f;
+        for (int i = tid; i < C * C; i += 256) pred_part[(((long long)bag * nblk + blockIdx.x) * C) * C + i] = 0.f;   // any C: a slot holds C * C
         return;
     }
     for (int c = 0; c < C; ++c) {
@@ -1268,7 +1268,7 @@ __global__ __launch_bounds__(256, (UB == 8 ? 1 : 6)) void k_finish(
         }
         float* pp = pred_part + (((long long)bag * nblk + blockIdx.x) * C) * C + c;  // [o] stride C
         if (!has_k) {
-            if (tid < C) pp[tid * C] = 0.f;
+            for (int o = tid; o < C; o += 256) pp[(long long)o * C] = 0.f;
             continue;
         }
         // B[c][kb..kb+63]: 16 thread groups walk the tiles, 16 lanes x float4 cover the k-run

@@ -57,6 +57,13 @@ typedef struct dsmil_agg_params {
     int32_t nonlinear; /* dsmil.py:30-33: 1 = Linear-ReLU-Linear-Tanh query, 0 = Linear  */
 } dsmil_agg_params;
 
+/* Supported number of classes C per entry point (dsmil.py:43: the aggregator handles any number of classes):
+ *   forward (dsmil_agg_forward / _ex / _bf16, the instance-sharded calls), dsmil_agg_backward / _ex, dsmil_fc_forward:
+ *       any C >= 1 (C <= 2 takes dedicated kernels; a larger C walks the classes in pairs)
+ *   dsmil_agg_loss_head, dsmil_agg_train_step: 1 <= C <= 64 (one wave of classes); C > 64 -> DSMIL_E_UNSUPPORTED, and
+ *       MILNet.bag_loss / training.FusedTrainStep compose the objective from the calls above instead
+ * tests/test_agg_classes_gpu.py checks every route at C > 2 against the fp64 oracle. */
+
 /* Replaces MILNet.forward / FCLayer.forward + BClassifier.forward (dsmil.py:10-12,46-62,70-74)
  * for a BATCH of n_bags independent bags stored back to back ("varlen"):
  *   feats    device [total_rows, K] fp32 row-major; bag b owns rows offsets[b]..offsets[b+1]-1

@@ -3,7 +3,8 @@
 
 Run in the build container only (needs /root/reference, which does not exist on the GPU box):
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py            # agg_golden.npz and the weight sets under dsmil-wsi_amd/data/
+    python tests/golden/make_golden.py --classes  # agg_golden_classes.npz only (C > 2; touches no other file)
 
 It imports /root/reference/dsmil.py unmodified, loads the two shipped aggregator weight files
 (example_aggregator_weights/{c16,tcga}_aggregator.pth, used by testing_c16.py:121 and
@@ -159,5 +160,59 @@ def main():
     print("wrote", len(cases), "cases:", ", ".join(sorted(cases)))
 
 
+# ---- more than two classes (dsmil.py:43 "can handle multiple class"; train_tcga.py --num_classes) --------------------
+# (K, C, nonlinear, weight seed, forward bag sizes, gradient bag sizes): the weights live inside agg_golden_classes.npz
+CLASS_SETS = [
+    (64, 5, True, 21, (200,), (200,)),
+    (166, 4, True, 22, (57,), (57,)),
+    (512, 5, True, 23, (300,), ()),
+    (64, 17, True, 24, (120,), ()),
+    (64, 6, False, 25, (80,), ()),
+]
+
+
+def class_set_name(K, C, nonlinear):
+    return f"K{K}_C{C}_{'nl' if nonlinear else 'lin'}"
+
+
+def main_classes():
+    flat = {}
+    for K, C, nonlinear, wseed, fwd_ns, grad_ns in CLASS_SETS:
+        ws = class_set_name(K, C, nonlinear)
+        net = build(K, C, nonlinear)
+        ortho_init(net, seed=wseed)
+        with torch.no_grad():   # fp16-exact values: the file stores them as float16 without loss (half the bytes)
+            for prm in net.parameters():
+                prm.copy_(prm.half().float())
+        for k, v in sd_to_np(net.state_dict()).items():
+            flat[f"{ws}/w/{k}"] = v.astype(np.float16)
+        cases = {}
+        for N in fwd_ns:
+            seed = 5000 + N + K + C
+            x = make_bag(seed, N, K)
+            out = run_fwd(net, x)
+            out["x_sha"] = np.array(sha(x))
+            out["seed"] = np.int64(seed)
+            cases[f"{ws}/fwd_N{N}"] = out
+        for N in grad_ns:
+            seed = 6000 + N + K + C
+            x = make_bag(seed, N, K)
+            label = make_label(seed, C)
+            out = run_grad(net, x, label)
+            out["x_sha"] = np.array(sha(x))
+            out["seed"] = np.int64(seed)
+            out["label"] = label
+            cases[f"{ws}/grad_N{N}"] = out
+        for name, d in cases.items():
+            for k, v in d.items():
+                flat[f"{name}/{k}"] = v
+    path = os.path.join(HERE, "agg_golden_classes.npz")
+    np.savez_compressed(path, **flat)
+    print("wrote", path, os.path.getsize(path), "bytes:", ", ".join(class_set_name(*c[:3]) for c in CLASS_SETS))
+
+
 if __name__ == "__main__":
-    main()
+    if "--classes" in sys.argv[1:]:
+        main_classes()
+    else:
+        main()

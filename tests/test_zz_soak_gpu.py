@@ -20,6 +20,7 @@ import agg_oracle as orc
 from conftest import load_weights
 from inputs import make_bag, make_label
 from test_agg_gpu import _cmp
+from util import poison_workspace as _poison_workspace
 
 pytestmark = pytest.mark.gpu
 
@@ -45,14 +46,6 @@ class _Load:
             e = torch.cuda.Event()
             e.record(self.s)
         self.ev.append(e)
-
-
-def _poison_workspace(ops):
-    """Every word of the native workspace of the current stream (q_max, hand-off flags, tile partials) becomes
-    0xFFFFFFFF = NaN / "flag set": a read of anything the CURRENT call has not written shows up as a NaN or, for a
-    flag that was not cleared, as a tile that did not wait."""
-    if ops._ws_last[0] is not None:
-        ops._ws_last[0].fill_(0xFF)
 
 
 def test_inline_query_handoff_stress_forward():
