@@ -38,6 +38,8 @@
 #include "agg_split.h"
 #include "agg_hs.h"
 #include "lds_attr.h"
+#define DSMIL_VALUE_BWD
+#include "agg_value.h"
 
 namespace {
 
@@ -1509,6 +1511,34 @@ int dsmil_agg_train_step(const float* feats, int64_t N, const int64_t* row_map, 
     }
     return agg_backward_impl(feats, nullptr, N, p, A, Bm, idx, nullptr, gmax, gpred, nullptr, nullptr, &g, nullptr, row_map,
                              bw8, L.bwd_bytes, stream, nullptr, qmax, true, &lh, &af, (unfuse & 2) != 0);
+}
+
+// ---- the value stream's parameter gradients (agg_value.h): what autograd derives for dsmil.py:39 behind g_vals ----
+size_t dsmil_value_workspace_bytes(int64_t rows, int32_t K, int32_t Kv) {
+    if (rows <= 0 || K <= 0 || Kv <= 0) return 0;
+    return vp_ws_layout(rows, K, Kv).total;
+}
+
+int dsmil_value_backward(const float* feats, const float* V, const float* g_vals, int64_t rows, int32_t K, int32_t Kv,
+                         const int64_t* row_map, float* g_v_w, float* g_v_b, void* ws, size_t ws_bytes, void* stream) {
+    if (!feats || !V || !g_vals || !g_v_w || !g_v_b || !ws || rows <= 0 || K <= 0 || Kv <= 0) return DSMIL_E_INVALID;
+    if ((uintptr_t)ws % 256) return DSMIL_E_ALIGN;
+    const VpWs L = vp_ws_layout(rows, K, Kv);
+    if (ws_bytes < L.total) return DSMIL_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    VtnArgs a{};
+    a.G = g_vals; a.V = V; a.X = feats; a.rowmap = row_map;
+    a.part = (float*)((char*)ws + L.part); a.pb = (float*)((char*)ws + L.pb);
+    a.N = rows; a.K = K; a.Kv = Kv;
+    vtn_plan(rows, K, Kv, a.S, a.R);
+    a.nsk = (K + 63) / 64; a.nsu = (Kv + 127) / 128;
+    const long long wgs = (long long)a.nsk * a.nsu * a.S;
+    if (wgs > 0x7fffffffLL) return DSMIL_E_UNSUPPORTED;
+    hipLaunchKernelGGL(k_value_tn, dim3((unsigned)wgs), dim3(256), 0, st, a);
+    if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    const long long n = (long long)Kv * K + Kv;
+    hipLaunchKernelGGL(k_value_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.part, a.pb, g_v_w, g_v_b, K, Kv, a.S);
+    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 
 #ifdef DSMIL_TRACE

@@ -45,6 +45,8 @@
 #include "agg_f2.h"
 #include "agg_f3.h"
 #include "agg_res.h"
+#define DSMIL_VALUE_FWD
+#include "agg_value.h"
 #include "lds_attr.h"
 
 namespace {
@@ -2027,6 +2029,51 @@ int dsmil_agg_pack_f2(const float* q0_w, const float* q2_w, int32_t K, void* pac
     if ((uintptr_t)packed % 16) return DSMIL_E_ALIGN;
     hipLaunchKernelGGL(k_pack_agg_f2, dim3(64), dim3(256), 0, (hipStream_t)stream, q0_w, q2_w, (_Float16*)packed, K,
                        2 * ((K + 31) / 32));
+    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
+}
+
+// ---- the value stream of BClassifier(passing_v=True): V = ReLU(Linear(K, K)(feats)), dsmil.py:35-39,48 (agg_value.h) ----
+size_t dsmil_value_packed_bytes(int32_t K, int32_t Kv) { return (K <= 0 || Kv <= 0) ? 0 : vp_image_bytes(K, Kv); }
+
+int dsmil_value_pack(const float* v_w, int32_t K, int32_t Kv, void* packed, void* stream) {
+    if (!v_w || !packed || K <= 0 || Kv <= 0) return DSMIL_E_INVALID;
+    if ((uintptr_t)packed % 16) return DSMIL_E_ALIGN;
+    hipLaunchKernelGGL(k_pack_value, dim3(256), dim3(256), 0, (hipStream_t)stream, v_w, (_Float16*)packed, K, Kv, vp_nks(K),
+                       vp_ntp(Kv));
+    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
+}
+
+int dsmil_value_forward(const float* feats, int64_t rows, int32_t K, int32_t Kv, const float* v_w, const float* v_b,
+                        const void* packed, const int64_t* row_map, float* V_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!feats || !v_w || !v_b || !V_out || rows <= 0 || K <= 0 || Kv <= 0) return DSMIL_E_INVALID;
+    if (rows * (int64_t)Kv / 256 + 1 > 0x7fffffffLL) return DSMIL_E_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    if (K > VP_MAX_K) {
+        hipLaunchKernelGGL(k_value_proj_valu, dim3((unsigned)((rows * Kv + 255) / 256)), dim3(256), 0, st, feats, row_map, v_w,
+                           v_b, V_out, (long long)rows, K, Kv);
+        return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
+    }
+    if (!packed) {   // cut Wv into the workspace first (a caller with fixed weights packs once: dsmil_value_pack)
+        if (!ws) return DSMIL_E_INVALID;
+        if ((uintptr_t)ws % 256) return DSMIL_E_ALIGN;
+        if (ws_bytes < vp_image_bytes(K, Kv)) return DSMIL_E_WORKSPACE;
+        const int rc = dsmil_value_pack(v_w, K, Kv, ws, stream);
+        if (rc) return rc;
+        packed = ws;
+    }
+    if ((uintptr_t)packed % 16) return DSMIL_E_ALIGN;
+    const int nks = vp_nks(K);
+    const int RG = K <= 512 ? 2 : 1;
+    const int lds = nks * 4 * (32 * RG) * 16 + 32 * RG * 4;
+    const int vec = (K % 4 == 0) && ((uintptr_t)feats % 16 == 0);
+    const bool full = vec && K % 32 == 0;
+    void (*fn)(const float*, const int64_t*, const f32x4*, const float*, float*, long long, int, int, int) =
+        RG == 2 ? (full ? (nks == 32 ? k_value_proj<2, 32, true> : k_value_proj<2, 0, true>) : k_value_proj<2, 0, false>)
+                : (full ? k_value_proj<1, 0, true> : k_value_proj<1, 0, false>);
+    if (!dsmil_lds::allow((const void*)fn, lds)) return DSMIL_E_LAUNCH;
+    const long long tiles = (rows + 32 * RG - 1) / (32 * RG);
+    hipLaunchKernelGGL(fn, dim3((unsigned)tiles), dim3(VP_THREADS), lds, st, feats, row_map, (const f32x4*)packed, v_b, V_out,
+                       (long long)rows, K, Kv, vec);
     return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 

@@ -178,8 +178,6 @@ def sharded_bag_forward(milnet, feats_local, row_offset, group=None, gather=_gat
     import torch.nn.functional as F
     from . import ops
     ic, bc = milnet.i_classifier, milnet.b_classifier
-    if bc.passing_v:
-        raise NotImplementedError("instance sharding is implemented for v = Identity (every reference script)")
     x = feats_local
     n_local, K = x.shape
     lin = ic.fc[0]
@@ -222,12 +220,15 @@ def sharded_bag_forward(milnet, feats_local, row_offset, group=None, gather=_gat
         crit_rows = allmsg[best_r, ar, 1 + lanes:].contiguous()               # [C,K]
         idx = gidx[best_r, ar]
         # ---- 2. this shard's attention against the bag-wide critical rows
+        #         (passing_v, dsmil.py:48: the value rows of the LOCAL instances — ops.value_proj natively, bc.v on the CPU)
+        Kv = w["fcc_w"].shape[2]
         if n_local == 0:
             A_un = x.new_zeros((0, C))
             ml = torch.stack([x.new_full((C,), float("-inf")), x.new_zeros((C,))], dim=1)
-            B_un = x.new_zeros((C, K))
+            B_un = x.new_zeros((C, Kv))
         elif native:
-            A_un, ml, B_un = ops.agg_shard_attend(x, w, crit_rows, nonlinear=bc.nonlinear)
+            vals = ops.value_proj(x, bc.v[1].weight.detach(), bc.v[1].bias.detach()) if bc.passing_v else None
+            A_un, ml, B_un = ops.agg_shard_attend(x, w, crit_rows, vals=vals, nonlinear=bc.nonlinear)
         else:
             q = bc.q
             Q = q(x)
@@ -236,7 +237,7 @@ def sharded_bag_forward(milnet, feats_local, row_offset, group=None, gather=_gat
             m = s.max(dim=0).values
             A_un = torch.exp(s - m)
             ml = torch.stack([m, A_un.sum(0)], dim=1)
-            B_un = A_un.t().mm(x)
+            B_un = A_un.t().mm(bc.v(x) if bc.passing_v else x)
         stat = torch.stack(gather(torch.cat([ml, B_un], dim=1), group))       # [R, C, 2+K]
         m_all, l_all, B_all = stat[:, :, 0], stat[:, :, 1], stat[:, :, 2:]
         m = m_all.max(dim=0).values

@@ -135,10 +135,24 @@ class BClassifier(nn.Module):
         C = self.fcc(B).view(1, -1)
         return C, A, B
 
+    def _values(self, feats):
+        """V = self.v(feats) (dsmil.py:48) for CUDA rows, None for v = Identity.  CUDA fp32 rows that need no gradient take
+        the native projection (ops.value_proj: Linear + ReLU in one HIP launch; its parameter gradients in
+        ops.value_proj_backward).  An ACTIVE dropout (training mode, p > 0) is torch's own, applied to the rows first — the
+        native projection then runs on the dropped rows; torch's random stream is not reproduced inside a kernel.  Rows that
+        require a gradient and bf16-stored rows keep the torch route (nn.Linear + ReLU under autograd)."""
+        if not self.passing_v:
+            return None
+        drop, lin = self.v[0], self.v[1]
+        if feats.dtype != torch.float32 or (torch.is_grad_enabled() and feats.requires_grad):
+            return self.v(feats)
+        x = drop(feats) if (drop.training and drop.p > 0) else feats
+        return _ValueProjFunction.apply(x, lin.weight, lin.bias)
+
     def forward(self, feats, c):
         if not feats.is_cuda:
             return self._forward_cpu(feats, c)
-        vals = self.v(feats) if self.passing_v else None  # passing_v: unused by every script
+        vals = self._values(feats)
         w = self._weights()
         pred, A, B = _AggFunction.apply(feats, c, vals, None, None, w["q0_w"], w["q0_b"], w["q2_w"],
                                         w["q2_b"], w["fcc_w"], w["fcc_b"], self.nonlinear)[1:4]
@@ -155,12 +169,15 @@ class MILNet(nn.Module):
 
     def forward(self, x):
         ic, bc = self.i_classifier, self.b_classifier
-        if (x.is_cuda and isinstance(ic, FCLayer) and isinstance(bc, BClassifier)
-                and not bc.passing_v and x.dim() == 2):
-            # one fused native call: instance logits + aggregator (dsmil.py:70-74)
+        native_v = not bc.passing_v or (x.dtype == torch.float32 and not (torch.is_grad_enabled() and x.requires_grad)) \
+            if isinstance(bc, BClassifier) else False
+        if x.is_cuda and isinstance(ic, FCLayer) and isinstance(bc, BClassifier) and native_v and x.dim() == 2:
+            # one fused native call: instance logits + aggregator (dsmil.py:70-74); with passing_v the native value
+            # projection runs in front of it and its result goes in as `vals` (bf16 rows and rows that require a gradient
+            # keep the two-module route below)
             w = bc._weights()
             lin = ic.fc[0]
-            classes, pred, A, B = _AggFunction.apply(x, None, None, lin.weight, lin.bias, w["q0_w"],
+            classes, pred, A, B = _AggFunction.apply(x, None, bc._values(x), lin.weight, lin.bias, w["q0_w"],
                                                      w["q0_b"], w["q2_w"], w["q2_b"], w["fcc_w"],
                                                      w["fcc_b"], bc.nonlinear)[0:4]
             return classes, pred, A, B
@@ -172,12 +189,15 @@ class MILNet(nn.Module):
         """A hipGraph-replayed forward for bags of exactly ``n_rows`` rows (inference; weights frozen): returns a
         callable feats -> (classes, pred [1,C], A, B [1,C,K]).  Single-bag latency is launch-bound otherwise."""
         ic, bc = self.i_classifier, self.b_classifier
-        if not (isinstance(ic, FCLayer) and isinstance(bc, BClassifier) and not bc.passing_v):
-            raise NotImplementedError("graphed forward: FCLayer + BClassifier with v = Identity")
+        if not (isinstance(ic, FCLayer) and isinstance(bc, BClassifier)):
+            raise NotImplementedError("graphed forward: FCLayer + BClassifier")
         w = {k: (v.detach() if v is not None else None) for k, v in bc._weights().items()}
         lin = ic.fc[0]
         w["fc_w"], w["fc_b"] = lin.weight.detach(), lin.bias.detach()
-        g = ops.GraphedAggForward(w, n_rows, lin.in_features, nonlinear=bc.nonlinear, device=lin.weight.device)
+        # passing_v: the value projection is captured with the rest (inference: the dropout of bc.v is the identity)
+        v_w, v_b = (bc.v[1].weight.detach(), bc.v[1].bias.detach()) if bc.passing_v else (None, None)
+        g = ops.GraphedAggForward(w, n_rows, lin.in_features, nonlinear=bc.nonlinear, device=lin.weight.device,
+                                  v_w=v_w, v_b=v_b)
 
         def run(feats):
             classes, pred, A, B, _ = g(feats)
@@ -192,7 +212,8 @@ class MILNet(nn.Module):
             ins, bag, _, _ = milnet(bag_feats);  mx = max(ins, 0)
             loss = 0.5 BCEWithLogitsLoss(bag, y) + 0.5 BCEWithLogitsLoss(mx, y)
         Returns (loss [], bag_prediction [1,C], max_prediction [C]).  CUDA fp32 bags with FCLayer + BClassifier
-        (v = Identity) take the fused path; everything else composes the same objective from torch ops."""
+        (v = Identity) take the fused path; everything else — a passing_v model included, whose forward and backward are
+        native all the same (value projection + aggregator) — composes the same objective around ``self(x)``."""
         ic, bc = self.i_classifier, self.b_classifier
         if (feats.is_cuda and feats.dtype == torch.float32 and feats.dim() == 2 and isinstance(ic, FCLayer)
                 and isinstance(bc, BClassifier) and not bc.passing_v and not feats.requires_grad
@@ -223,8 +244,10 @@ class MILNet(nn.Module):
         Returns a list of (classes, pred, A, B) tuples shaped like ``forward``'s.  New capability
         (the reference loops one bag per iteration, train_tcga.py:92-99)."""
         ic, bc = self.i_classifier, self.b_classifier
-        if not (isinstance(ic, FCLayer) and isinstance(bc, BClassifier) and not bc.passing_v):
+        if not (isinstance(ic, FCLayer) and isinstance(bc, BClassifier)):
             return [self.forward(b) for b in bags]
+        if bc.passing_v and bags[0].dtype != torch.float32:
+            return [self.forward(b) for b in bags]   # (the value layer on bf16-stored rows: the torch route, bag by bag)
         if isinstance(bags, tuple):
             feats, lengths = bags
         else:
@@ -233,9 +256,11 @@ class MILNet(nn.Module):
         w = bc._weights()
         lin = ic.fc[0]
         w["fc_w"], w["fc_b"] = lin.weight, lin.bias
+        # passing_v: ONE projection over the concatenated rows, then one aggregator call over the batch
+        vals = bc._values(feats)
         classes, pred, A, B, _ = ops.agg_forward(feats, lengths, {k: (v.detach() if v is not None else None)
                                                                   for k, v in w.items()},
-                                                 nonlinear=bc.nonlinear)
+                                                 vals=vals, nonlinear=bc.nonlinear)
         out, o = [], 0
         for i, n in enumerate(lengths):
             out.append((classes[o:o + n], pred[i:i + 1], A[o:o + n], B[i:i + 1]))
@@ -263,6 +288,29 @@ class _FCFunction(torch.autograd.Function):
         gx = g32.mm(w.float()).to(x.dtype) if ctx.needs_input_grad[0] else None
         gw = g32.t().mm(x32).to(w.dtype) if ctx.needs_input_grad[1] else None
         gb = g32.sum(0).to(w.dtype) if ctx.needs_input_grad[2] else None
+        return gx, gw, gb
+
+
+class _ValueProjFunction(torch.autograd.Function):
+    """V = ReLU(x Wv^T + bv) in the native library (dsmil_value_forward); backward = dsmil_value_backward for the two
+    parameter gradients (mask and both contractions in HIP, deterministic).  The gradient of the INPUT rows,
+    g_x = (g * (V > 0)) Wv, is composed from torch ops and only when a caller asks for it (BClassifier sends rows that
+    require a gradient down the torch route, so no module path does)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        V = ops.value_proj(x.detach(), w.detach(), b.detach())
+        ctx.save_for_backward(x, w, V)
+        return V
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, V = ctx.saved_tensors
+        gw = gb = gx = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            gw, gb = ops.value_proj_backward(x, V, g)
+        if ctx.needs_input_grad[0]:
+            gx = (g * (V > 0)).mm(w)
         return gx, gw, gb
 
 

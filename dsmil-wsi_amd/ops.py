@@ -342,6 +342,72 @@ def agg_forward(feats, lengths, w, classes_in=None, vals=None, nonlinear=True, o
     return classes, pred, A, B, idx
 
 
+def _value_params(v_w, dev):
+    """BClassifier.v's weight [Kv, K] as two fp16 planes of its power-of-two scaled values in MFMA-fragment order
+    (dsmil_value_pack, csrc/agg_value.h), prepared once per weight set (cached like _f2_params)."""
+    L = _native.lib()
+    key = ("value", str(dev), _tkey(v_w))
+    ent = _split_cache.get(key)
+    if ent is not None:
+        ent[2].wait(dev, ent[0])
+        return ent[0]
+    Kv, K = v_w.shape
+    packed = torch.empty(L.dsmil_value_packed_bytes(K, Kv), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.dsmil_value_pack(_ptr(v_w), K, Kv, _ptr(packed), _stream(dev))
+    _native.check(rc, "dsmil_value_pack")
+    _split_cache.put(key, (packed, [v_w], _Ready(dev)))
+    return packed
+
+
+def value_proj(feats, v_w, v_b, row_map=None):
+    """dsmil_value_forward: V = ReLU(feats @ v_w^T + v_b), the Linear + ReLU of BClassifier.v (dsmil.py:35-39,48), in ONE
+    native launch (fp32 in, fp32 out; the weight planes are cut once per weight set).  feats [rows, K] fp32 CUDA, v_w [Kv, K],
+    v_b [Kv]; ``row_map`` (int64 [n]): logical row i is physical row row_map[i] of feats.  Returns V [n, Kv] in logical order."""
+    feats = _f32c(feats, "feats"); v_w = _f32c(v_w, "v_w"); v_b = _f32c(v_b, "v_b")
+    dev = feats.device
+    rows, K = feats.shape
+    Kv = v_w.shape[0]
+    if v_w.shape[1] != K or v_b.numel() != Kv:
+        raise ValueError(f"v_w must be [Kv,{K}] and v_b [Kv], got {tuple(v_w.shape)} / {tuple(v_b.shape)}")
+    row_map = _i64c(row_map, "row_map")
+    n = int(row_map.numel()) if row_map is not None else rows
+    V = torch.empty((n, Kv), dtype=torch.float32, device=dev)
+    if n == 0:
+        return V
+    packed = _value_params(v_w, dev)
+    with torch.cuda.device(dev):
+        rc = _native.lib().dsmil_value_forward(_ptr(feats), n, K, Kv, _ptr(v_w), _ptr(v_b), _ptr(packed), _ptr(row_map), _ptr(V),
+                                               None, 0, _stream(dev))
+    _native.check(rc, "dsmil_value_forward")
+    return V
+
+
+def value_proj_backward(feats, V, g_vals, row_map=None):
+    """dsmil_value_backward: the PARAMETER gradients of BClassifier.v's Linear behind g_vals (what agg_backward returns as
+    ``vals``):  gZ = g_vals * (V > 0),  g_v_w [Kv, K] = gZ^T feats,  g_v_b [Kv] = colsum gZ — deterministic (fixed-order
+    sums).  The gradient of the input rows (gZ v_w) is not formed here: a caller that needs it composes it from torch ops
+    (modules._ValueProjFunction).  Returns (g_v_w, g_v_b)."""
+    feats = _f32c(feats, "feats"); V = _f32c(V, "V"); g_vals = _f32c(g_vals, "g_vals")
+    dev = feats.device
+    K = feats.shape[1]
+    n, Kv = V.shape
+    row_map = _i64c(row_map, "row_map")
+    if tuple(g_vals.shape) != (n, Kv) or n != (int(row_map.numel()) if row_map is not None else feats.shape[0]):
+        raise ValueError(f"V / g_vals must be [rows,{Kv}], got {tuple(V.shape)} / {tuple(g_vals.shape)}")
+    g_w = torch.empty((Kv, K), dtype=torch.float32, device=dev)
+    g_b = torch.empty((Kv,), dtype=torch.float32, device=dev)
+    if n == 0:
+        return g_w.zero_(), g_b.zero_()
+    L = _native.lib()
+    ws = _workspace(dev, L.dsmil_value_workspace_bytes(n, K, Kv))
+    with torch.cuda.device(dev):
+        rc = L.dsmil_value_backward(_ptr(feats), _ptr(V), _ptr(g_vals), n, K, Kv, _ptr(row_map), _ptr(g_w), _ptr(g_b), _ptr(ws),
+                                    ws.numel(), _stream(dev))
+    _native.check(rc, "dsmil_value_backward")
+    return g_w, g_b
+
+
 class GraphedAggForward:
     """MILNet.forward of ONE bag shape captured into a hipGraph and replayed (the library enqueues on the
     caller's stream, allocates nothing and never synchronises, so the whole 5-launch forward is capturable).  A single
@@ -353,24 +419,32 @@ class GraphedAggForward:
     Inference only: the capture holds the addresses of the weights and of their packed plane cuts, so the weights
     must stay as they are — build a new object after an optimizer step or a load_state_dict."""
 
-    def __init__(self, w, n_rows, K, nonlinear=True, device=None, dtype=torch.float32):
+    def __init__(self, w, n_rows, K, nonlinear=True, device=None, dtype=torch.float32, v_w=None, v_b=None):
         dev = torch.device(device) if device is not None else w["q0_w"].device
         self.w, self.n, self.nonlinear, self.dev = w, int(n_rows), nonlinear, dev
+        if v_w is not None and dtype != torch.float32:
+            raise ValueError("the value layer (v_w / v_b) is implemented for fp32 bags")
+
+        def fwd():   # with v_w / v_b (BClassifier(passing_v=True)): the projection launch is captured with the rest
+            vals = self._vals = value_proj(self.x, v_w, v_b) if v_w is not None else None   # (V lives as long as the graph)
+            return agg_forward(self.x, [self.n], w, vals=vals, nonlinear=nonlinear, offsets=self.offsets)
         self.x = torch.zeros((self.n, K), dtype=dtype, device=dev)
         self.offsets = offsets_tensor([self.n], dev)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):   # warm-up outside capture: workspace, packed weights, function attributes
             for _ in range(2):
-                agg_forward(self.x, [self.n], w, nonlinear=nonlinear, offsets=self.offsets)
+                fwd()
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         # the captured launches read these buffers by address: keep them alive as long as the graph
         self._keep = [_split_params(_f32c(w["q0_w"], "q0_w"), _f32c(w.get("q2_w"), "q2_w"), nonlinear, dev)
                       if dtype == torch.float32 else _bf16_params(w, nonlinear, dev)]
+        if v_w is not None:
+            self._keep.append(_value_params(_f32c(v_w, "v_w"), dev))
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            self.out = agg_forward(self.x, [self.n], w, nonlinear=nonlinear, offsets=self.offsets)
+            self.out = fwd()
         self._keep.append(_ws_last[0])   # the workspace of the capture stream
 
     def __call__(self, feats):

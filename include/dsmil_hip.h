@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define DSMIL_ABI_VERSION 5
+#define DSMIL_ABI_VERSION 6
 #define DSMIL_Q_DIM 128 /* query width hard-coded at dsmil.py:31,33 */
 
 enum {
@@ -258,6 +258,32 @@ int dsmil_agg_backward(const float* feats, const float* vals, int64_t N, const d
                        const float* g_pred, const float* g_A, const float* g_B,
                        const dsmil_agg_grads* g, float* g_vals, void* ws, size_t ws_bytes,
                        void* stream);
+
+/* ---- the value stream of BClassifier(passing_v=True) (ABI 6) ---------------------------------------------------------
+ * Replaces `V = self.v(feats)` of dsmil.py:48 with self.v = Sequential(Dropout, Linear(K, K), ReLU) (dsmil.py:35-39; the
+ * dropout is the caller's: it hands in the rows it wants projected):  V[n, j] = max(0, sum_k feats[n, k] v_w[j, k] + v_b[j]),
+ * fp32 in, fp32 out, fp32-class arithmetic (fp16 MFMA over two-plane cuts of the row-scaled rows and the tensor-scaled
+ * weights, three plane products, fp32 accumulation: csrc/agg_value.h).  The result is the `vals` of dsmil_agg_forward.
+ *   v_w [Kv, K], v_b [Kv]   b_classifier.v.1.{weight,bias}  (Kv == K in the reference)
+ *   dsmil_value_pack     replaces nothing in the reference (its nn.Linear reads the weights as they are): cuts v_w ONCE per
+ *                        weight set into dsmil_value_packed_bytes(K, Kv) bytes (16-B aligned) of MFMA-fragment-ordered planes
+ *   dsmil_value_forward  dsmil.py:48.  packed: that image, or NULL = cut v_w into `ws` first (then ws must hold
+ *                        dsmil_value_workspace_bytes(rows, K, Kv) bytes, 256-B aligned; with an image, ws may be NULL).
+ *                        row_map: int64 [rows] or NULL, logical row i is physical row row_map[i] of feats (see
+ *                        dsmil_agg_opts); V_out [rows, Kv] is in logical order.  One launch (two with packed == NULL).  Any K:
+ *                        K <= 1024 on the matrix cores, wider rows on a plain fp32 kernel.
+ *   dsmil_value_backward what autograd derives for dsmil.py:39 behind g_vals (= dsmil_agg_backward's g_vals) for the layer's
+ *                        PARAMETERS:  gZ = g_vals * (V > 0),  g_v_w [Kv, K] = gZ^T feats,  g_v_b [Kv] = column sums of gZ
+ *                        (both OVERWRITTEN; gZ is never written to memory; bf16 MFMA over exact three-plane cuts, fixed-order
+ *                        two-stage sums: two runs give the same bits).  V, g_vals [rows, Kv] in logical order.  The gradient of
+ *                        the input rows (gZ v_w) is not computed here.  Two launches. */
+size_t dsmil_value_packed_bytes(int32_t K, int32_t Kv);
+int dsmil_value_pack(const float* v_w, int32_t K, int32_t Kv, void* packed, void* stream);
+size_t dsmil_value_workspace_bytes(int64_t rows, int32_t K, int32_t Kv);
+int dsmil_value_forward(const float* feats, int64_t rows, int32_t K, int32_t Kv, const float* v_w, const float* v_b,
+                        const void* packed, const int64_t* row_map, float* V_out, void* ws, size_t ws_bytes, void* stream);
+int dsmil_value_backward(const float* feats, const float* V, const float* g_vals, int64_t rows, int32_t K, int32_t Kv,
+                         const int64_t* row_map, float* g_v_w, float* g_v_b, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- one training step per C call (ABI 3) --------------------------------------------------------
  * Replaces the body of the reference's training loop for one bag, train_tcga.py:60-75 (train_mil.py:44-56 likewise):
