@@ -28,6 +28,10 @@
 //                        gH / gz2 (bias gradients) from the staged values
 //   k_bwd_reduce         fixed-order sums of the row-range partials -> g_W1, g_b1, g_W2, g_b2; the sparse max-stream
 //                        gradient of the FCLayer (g_max) in the same launch
+//   k_bwd_gx (agg_gx.h)  ONLY when the caller asks for the gradient of the input rows (dsmil_agg_backward_rows with g_feats):
+//                        g_x = gH W1 (gz2 W1 for the linear query) + g_c Wf + g_max[c] Wf[c] at row idx_c + A gB (v = Identity),
+//                        one pass over 128-row x 64-column tiles that writes g_x once; a call without g_feats launches
+//                        exactly what it launched before
 // dsmil_agg_train_step chains forward -> loss head -> this backward -> one Adam kernel over all eight tensors:
 // one C call per train_tcga.py:60-75 step.
 
@@ -40,6 +44,7 @@
 #include "lds_attr.h"
 #define DSMIL_VALUE_BWD
 #include "agg_value.h"
+#include "agg_gx.h"
 
 namespace {
 
@@ -1190,7 +1195,8 @@ int agg_backward_impl(const float* feats, const float* vals, int64_t N, const ds
                       const float* g_max, const float* g_pred, const float* g_A, const float* g_B,
                       const dsmil_agg_grads* g, float* g_vals, const int64_t* rowmap, void* ws, size_t ws_bytes,
                       void* stream, const void* packed_split, const float* qmax_in, bool prepared = false,
-                      const LossHeadArgs* lhp = nullptr, const AdamFuse* adam = nullptr, bool own_fc_launch = false) {
+                      const LossHeadArgs* lhp = nullptr, const AdamFuse* adam = nullptr, bool own_fc_launch = false,
+                      float* g_feats = nullptr) {
     if (adam && (!g_max || g_classes)) return DSMIL_E_INVALID;   // the fused optimizer step is the training loop's
     if (!feats || !p || !A || !Bm || !idx || (!g_pred && !lhp) || !g || !ws) return DSMIL_E_INVALID;
     if (g_max && (!g->fc_w || !g->fc_b)) return DSMIL_E_INVALID;
@@ -1198,6 +1204,7 @@ int agg_backward_impl(const float* feats, const float* vals, int64_t N, const ds
     if (!p->q0_w || !p->q0_b || !p->fcc_w || (p->nonlinear && (!p->q2_w || !p->q2_b))) return DSMIL_E_INVALID;
     if (!g->q0_w || !g->q0_b || !g->fcc_w || !g->fcc_b || (p->nonlinear && (!g->q2_w || !g->q2_b))) return DSMIL_E_INVALID;
     if (g_classes && (!g->fc_w || !g->fc_b)) return DSMIL_E_INVALID;
+    if (g_feats && (g_classes || g_max) && !p->fc_w) return DSMIL_E_INVALID;   // the instance stream's share of g_x reads Wf
     if (!vals) vals = feats;
     if (vals == feats && p->Kv != p->K) return DSMIL_E_INVALID;
     if (((uintptr_t)ws % 256) || ((uintptr_t)p->q0_b % 16) || (p->nonlinear && ((uintptr_t)p->q2_b % 16))) return DSMIL_E_ALIGN;
@@ -1330,6 +1337,15 @@ int agg_backward_impl(const float* feats, const float* vals, int64_t N, const ds
             hipLaunchKernelGGL(k_bwd_gvals<1>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, A, gB, g_vals, (long long)N, Kv, C);
         if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
     }
+    // 10. gradient of the input rows (only on request): gH / gz2, gB are still in the workspace
+    if (g_feats) {
+        GxArgs gx{};
+        gx.L = p->nonlinear ? gH : gz2; gx.W = p->q0_w; gx.out = g_feats; gx.N = N; gx.J = QD; gx.K = K; gx.lvec = 1;
+        gx.gc = g_classes; gx.Wf = p->fc_w; gx.A = vals == feats ? A : nullptr; gx.gB = gB; gx.idx = idx; gx.gmax = g_max;
+        gx.C = (g_classes || g_max || vals == feats) ? C : 0;
+        if (!gx_launch<false>(gx, st)) return DSMIL_E_UNSUPPORTED;
+        if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    }
     return DSMIL_OK;
 }
 
@@ -1390,6 +1406,19 @@ int dsmil_agg_backward_ex(const float* feats, const float* vals, int64_t N, cons
                           void* stream) {
     return agg_backward_impl(feats, vals, N, p, A, Bm, idx, g_classes, g_max, g_pred, g_A, g_B, g, g_vals, rowmap,
                              ws, ws_bytes, stream, nullptr, nullptr);
+}
+
+size_t dsmil_agg_backward_rows_workspace_bytes(int64_t N, int32_t K, int32_t Kv, int32_t C) {
+    return dsmil_agg_backward_workspace_bytes(N, K, Kv, C);   // k_gx reads what the backward left in its workspace: nothing is added
+}
+
+int dsmil_agg_backward_rows(const float* feats, const float* vals, int64_t N, const dsmil_agg_params* p,
+                            const float* A, const float* Bm, const int64_t* idx, const float* g_classes,
+                            const float* g_max, const float* g_pred, const float* g_A, const float* g_B,
+                            const dsmil_agg_grads* g, float* g_vals, const int64_t* rowmap, void* ws, size_t ws_bytes,
+                            void* stream, float* g_feats) {
+    return agg_backward_impl(feats, vals, N, p, A, Bm, idx, g_classes, g_max, g_pred, g_A, g_B, g, g_vals, rowmap,
+                             ws, ws_bytes, stream, nullptr, nullptr, false, nullptr, nullptr, false, g_feats);
 }
 
 int dsmil_adam_step(int32_t n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
@@ -1538,6 +1567,20 @@ int dsmil_value_backward(const float* feats, const float* V, const float* g_vals
     if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
     const long long n = (long long)Kv * K + Kv;
     hipLaunchKernelGGL(k_value_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.part, a.pb, g_v_w, g_v_b, K, Kv, a.S);
+    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
+}
+
+int dsmil_value_backward_rows(const float* feats, const float* V, const float* g_vals, int64_t rows, int32_t K, int32_t Kv,
+                              const float* v_w, const void* packed, int32_t accumulate, float* g_feats, void* ws,
+                              size_t ws_bytes, void* stream) {
+    (void)feats; (void)packed; (void)ws_bytes;   // the product reads neither the rows nor the forward's image (agg_gx.h)
+    if (!V || !g_vals || !v_w || !g_feats || rows <= 0 || K <= 0 || Kv <= 0) return DSMIL_E_INVALID;
+    if (ws && ((uintptr_t)ws % 256)) return DSMIL_E_ALIGN;
+    GxArgs gx{};
+    gx.L = g_vals; gx.V = V; gx.W = v_w; gx.out = g_feats; gx.N = rows; gx.J = Kv; gx.K = K;
+    gx.accumulate = accumulate ? 1 : 0;
+    gx.lvec = (Kv % 4 == 0) && (((uintptr_t)g_vals | (uintptr_t)V) % 16 == 0);
+    if (!gx_launch<true>(gx, (hipStream_t)stream)) return DSMIL_E_UNSUPPORTED;
     return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 

@@ -136,15 +136,15 @@ class BClassifier(nn.Module):
         return C, A, B
 
     def _values(self, feats):
-        """V = self.v(feats) (dsmil.py:48) for CUDA rows, None for v = Identity.  CUDA fp32 rows that need no gradient take
-        the native projection (ops.value_proj: Linear + ReLU in one HIP launch; its parameter gradients in
-        ops.value_proj_backward).  An ACTIVE dropout (training mode, p > 0) is torch's own, applied to the rows first — the
-        native projection then runs on the dropped rows; torch's random stream is not reproduced inside a kernel.  Rows that
-        require a gradient and bf16-stored rows keep the torch route (nn.Linear + ReLU under autograd)."""
+        """V = self.v(feats) (dsmil.py:48) for CUDA rows, None for v = Identity.  CUDA fp32 rows take the native projection
+        whether or not they require a gradient (ops.value_proj: Linear + ReLU in one HIP launch; its parameter gradients in
+        ops.value_proj_backward, the gradient of the rows in ops.value_proj_backward_rows).  An ACTIVE dropout (training
+        mode, p > 0) is torch's own, applied to the rows first — the native projection then runs on the dropped rows; torch's
+        random stream is not reproduced inside a kernel.  bf16-stored rows keep the torch route (nn.Linear + ReLU)."""
         if not self.passing_v:
             return None
         drop, lin = self.v[0], self.v[1]
-        if feats.dtype != torch.float32 or (torch.is_grad_enabled() and feats.requires_grad):
+        if feats.dtype != torch.float32:
             return self.v(feats)
         x = drop(feats) if (drop.training and drop.p > 0) else feats
         return _ValueProjFunction.apply(x, lin.weight, lin.bias)
@@ -169,12 +169,11 @@ class MILNet(nn.Module):
 
     def forward(self, x):
         ic, bc = self.i_classifier, self.b_classifier
-        native_v = not bc.passing_v or (x.dtype == torch.float32 and not (torch.is_grad_enabled() and x.requires_grad)) \
-            if isinstance(bc, BClassifier) else False
+        native_v = (not bc.passing_v or x.dtype == torch.float32) if isinstance(bc, BClassifier) else False
         if x.is_cuda and isinstance(ic, FCLayer) and isinstance(bc, BClassifier) and native_v and x.dim() == 2:
             # one fused native call: instance logits + aggregator (dsmil.py:70-74); with passing_v the native value
-            # projection runs in front of it and its result goes in as `vals` (bf16 rows and rows that require a gradient
-            # keep the two-module route below)
+            # projection runs in front of it and its result goes in as `vals` (bf16 rows keep the two-module route below);
+            # rows that require a gradient get it from the native backward (k_bwd_gx, k_value_gx)
             w = bc._weights()
             lin = ic.fc[0]
             classes, pred, A, B = _AggFunction.apply(x, None, bc._values(x), lin.weight, lin.bias, w["q0_w"],
@@ -212,8 +211,10 @@ class MILNet(nn.Module):
             ins, bag, _, _ = milnet(bag_feats);  mx = max(ins, 0)
             loss = 0.5 BCEWithLogitsLoss(bag, y) + 0.5 BCEWithLogitsLoss(mx, y)
         Returns (loss [], bag_prediction [1,C], max_prediction [C]).  CUDA fp32 bags with FCLayer + BClassifier
-        (v = Identity) take the fused path; everything else — a passing_v model included, whose forward and backward are
-        native all the same (value projection + aggregator) — composes the same objective around ``self(x)``."""
+        (v = Identity) whose rows need no gradient take the fused path (the fused loss call has no row-gradient output);
+        everything else — a passing_v model and rows that require a gradient included, whose forward and backward are
+        native all the same (value projection + aggregator + the row-gradient kernels) — composes the same objective
+        around ``self(x)``."""
         ic, bc = self.i_classifier, self.b_classifier
         if (feats.is_cuda and feats.dtype == torch.float32 and feats.dim() == 2 and isinstance(ic, FCLayer)
                 and isinstance(bc, BClassifier) and not bc.passing_v and not feats.requires_grad
@@ -272,7 +273,9 @@ class MILNet(nn.Module):
 # autograd glue
 # ---------------------------------------------------------------------------------------------
 class _FCFunction(torch.autograd.Function):
-    """c = x W^T + b in the native library; backward is three small dense products."""
+    """c = x W^T + b in the native library; backward is three small dense products (torch: the stand-alone FCLayer /
+    IClassifier head.  Inside MILNet(FCLayer, BClassifier) the layer is fused into _AggFunction, whose backward — the
+    instance stream's share of the row gradient included — is native)."""
 
     @staticmethod
     def forward(ctx, x, w, b):
@@ -293,9 +296,8 @@ class _FCFunction(torch.autograd.Function):
 
 class _ValueProjFunction(torch.autograd.Function):
     """V = ReLU(x Wv^T + bv) in the native library (dsmil_value_forward); backward = dsmil_value_backward for the two
-    parameter gradients (mask and both contractions in HIP, deterministic).  The gradient of the INPUT rows,
-    g_x = (g * (V > 0)) Wv, is composed from torch ops and only when a caller asks for it (BClassifier sends rows that
-    require a gradient down the torch route, so no module path does)."""
+    parameter gradients and dsmil_value_backward_rows for the gradient of the INPUT rows, g_x = (g * (V > 0)) Wv (mask and
+    all three contractions in HIP, deterministic)."""
 
     @staticmethod
     def forward(ctx, x, w, b):
@@ -310,7 +312,7 @@ class _ValueProjFunction(torch.autograd.Function):
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             gw, gb = ops.value_proj_backward(x, V, g)
         if ctx.needs_input_grad[0]:
-            gx = (g * (V > 0)).mm(w)
+            gx = ops.value_proj_backward_rows(V, g, w.detach())
         return gx, gw, gb
 
 
@@ -347,7 +349,8 @@ class _BagLossFunction(torch.autograd.Function):
 class _AggFunction(torch.autograd.Function):
     """Forward = dsmil_agg_forward (HIP).  Backward = analytic gradient of dsmil.py:46-62 (the
     arg-max indices are constants, as in the reference's autograd graph); it re-derives Q from
-    the saved inputs (dsmil_agg_backward, csrc/agg_bwd.hip — SURVEY.md §8(f) row N1)."""
+    the saved inputs (dsmil_agg_backward, csrc/agg_bwd.hip — SURVEY.md §8(f) row N1).  The gradient of the input rows,
+    when asked for, comes from the same native call (dsmil_agg_backward_rows, k_bwd_gx)."""
 
     @staticmethod
     def forward(ctx, feats, c_in, vals, fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, nonlinear):
@@ -375,30 +378,43 @@ class _AggFunction(torch.autograd.Function):
     def backward(ctx, g_cls, g_pred, g_A, g_B, _g_idx):
         if ctx.bf16:
             raise NotImplementedError("the bf16-storage aggregator path is inference only")
-        if not ctx.needs_input_grad[0]:
+        if not ctx.needs_input_grad[0] or _AggFunction._native_accepts(ctx):
             return _AggFunction._backward_native(ctx, g_cls, g_pred, g_A, g_B)
         return _AggFunction._backward_dense(ctx, g_cls, g_pred, g_A, g_B)
 
     @staticmethod
+    def _native_accepts(ctx):
+        """What dsmil_agg_backward_rows rejects (DSMIL_E_ALIGN): query biases that are not 16-byte aligned, e.g. views into
+        a flat parameter buffer.  Every nn.Module parameter allocated by torch passes."""
+        q0_b, q2_b = ctx.saved_tensors[4], ctx.saved_tensors[6]
+        return all(t is None or t.data_ptr() % 16 == 0 for t in (q0_b, q2_b))
+
+    @staticmethod
     def _backward_native(ctx, g_cls, g_pred, g_A, g_B):
-        """dsmil_agg_backward (HIP): every parameter gradient, and g_vals for a trainable v."""
+        """dsmil_agg_backward (HIP): every parameter gradient, g_vals for a trainable v, and — when the input rows require
+        one — their gradient (v = Identity: A gB included; caller's vals: the value function adds its own share)."""
         feats, vals, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx = ctx.saved_tensors
         C = fcc_w.shape[0]
         if g_pred is None:
             g_pred = torch.zeros((1, C), device=feats.device)
         w = {"fc_w": fc_w, "fc_b": None, "q0_w": q0_w, "q0_b": q0_b, "q2_w": q2_w, "q2_b": q2_b,
              "fcc_w": fcc_w, "fcc_b": None}
-        want_v = ctx.has_vals and ctx.needs_input_grad[2]
+        want_x = ctx.needs_input_grad[0]
+        # (vals sharing feats' memory IS v = Identity to the kernels: the rows' gradient then already holds A gB)
+        same = ctx.has_vals and vals.data_ptr() == feats.data_ptr()
+        want_v = ctx.has_vals and ctx.needs_input_grad[2] and not (want_x and same)
         g = ops.agg_backward(feats, w, A, B, idx, g_pred, g_classes=None if ctx.has_cin else g_cls,
                              g_A=g_A, g_B=g_B[0] if g_B is not None else None,
-                             vals=vals if ctx.has_vals else None, nonlinear=ctx.nonlinear, want_g_vals=want_v)
-        return (None, None, g.get("vals"), g.get("fc_w"), g.get("fc_b"), g["q0_w"], g["q0_b"],
+                             vals=vals if ctx.has_vals else None, nonlinear=ctx.nonlinear, want_g_vals=want_v,
+                             want_g_feats=want_x)
+        return (g.get("feats"), None, g.get("vals"), g.get("fc_w"), g.get("fc_b"), g["q0_w"], g["q0_b"],
                 g.get("q2_w"), g.get("q2_b"), g["fcc_w"], g["fcc_b"], None)
 
     @staticmethod
     def _backward_dense(ctx, g_cls, g_pred, g_A, g_B):
-        """Only when the gradient of the INPUT rows is requested (no reference script does: bags are
-        data, train_tcga.py:60-66): the same analytic gradient composed from dense GPU products."""
+        """The fallback for what the native call rejects when the gradient of the INPUT rows is requested (_native_accepts:
+        misaligned query biases): the same analytic gradient composed from dense GPU products.  No fp32 CUDA route of
+        FCLayer + BClassifier with ordinary parameters reaches it."""
         feats, vals, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx = ctx.saved_tensors
         x = feats
         V = vals if ctx.has_vals else feats

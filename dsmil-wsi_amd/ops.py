@@ -386,8 +386,7 @@ def value_proj(feats, v_w, v_b, row_map=None):
 def value_proj_backward(feats, V, g_vals, row_map=None):
     """dsmil_value_backward: the PARAMETER gradients of BClassifier.v's Linear behind g_vals (what agg_backward returns as
     ``vals``):  gZ = g_vals * (V > 0),  g_v_w [Kv, K] = gZ^T feats,  g_v_b [Kv] = colsum gZ — deterministic (fixed-order
-    sums).  The gradient of the input rows (gZ v_w) is not formed here: a caller that needs it composes it from torch ops
-    (modules._ValueProjFunction).  Returns (g_v_w, g_v_b)."""
+    sums).  The gradient of the input rows (gZ v_w) is value_proj_backward_rows.  Returns (g_v_w, g_v_b)."""
     feats = _f32c(feats, "feats"); V = _f32c(V, "V"); g_vals = _f32c(g_vals, "g_vals")
     dev = feats.device
     K = feats.shape[1]
@@ -406,6 +405,33 @@ def value_proj_backward(feats, V, g_vals, row_map=None):
                                     ws.numel(), _stream(dev))
     _native.check(rc, "dsmil_value_backward")
     return g_w, g_b
+
+
+def value_proj_backward_rows(V, g_vals, v_w, out=None, accumulate=False):
+    """dsmil_value_backward_rows: the INPUT-row gradient of BClassifier.v's Linear + ReLU behind g_vals,
+    g_x [rows, K] = (g_vals * (V > 0)) @ v_w, in one native launch (k_value_gx: mask applied while the operand is staged,
+    bf16 MFMA over exact three-plane cuts, deterministic).  V, g_vals [rows, Kv] fp32 CUDA, v_w [Kv, K].  ``out``: an
+    fp32 [rows, K] buffer to write — or, with ``accumulate``, to add to (the aggregator's own g_feats: one buffer, no add
+    pass); None allocates.  Returns out."""
+    V = _f32c(V, "V"); g_vals = _f32c(g_vals, "g_vals"); v_w = _f32c(v_w, "v_w")
+    dev = V.device
+    n, Kv = V.shape
+    K = v_w.shape[1]
+    if tuple(g_vals.shape) != (n, Kv) or v_w.shape[0] != Kv:
+        raise ValueError(f"g_vals must be [{n},{Kv}] and v_w [{Kv},K], got {tuple(g_vals.shape)} / {tuple(v_w.shape)}")
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate needs the buffer to add to (out)")
+        out = torch.empty((n, K), dtype=torch.float32, device=dev)
+    elif (tuple(out.shape) != (n, K) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev):
+        raise ValueError(f"out must be a contiguous fp32 [{n},{K}] tensor on {dev}")
+    if n == 0:
+        return out
+    with torch.cuda.device(dev):
+        rc = _native.lib().dsmil_value_backward_rows(None, _ptr(V), _ptr(g_vals), n, K, Kv, _ptr(v_w), None,
+                                                     1 if accumulate else 0, _ptr(out), None, 0, _stream(dev))
+    _native.check(rc, "dsmil_value_backward_rows")
+    return out
 
 
 class GraphedAggForward:
@@ -526,13 +552,16 @@ def agg_loss_head(classes, pred, idx, label):
 
 
 def agg_backward(feats, w, A, B, idx, g_pred, g_classes=None, g_A=None, g_B=None, vals=None, nonlinear=True,
-                 want_g_vals=False, g_max=None, row_map=None):
+                 want_g_vals=False, g_max=None, row_map=None, want_g_feats=False):
     """dsmil_agg_backward: parameter gradients of FCLayer + BClassifier for ONE bag (what autograd
     derives for train_tcga.py:67-72).  feats [N,K] fp32 CUDA, w as in agg_forward, A [N,C], B [1,C,Kv],
     idx [1,C] = the forward's outputs; g_* = upstream gradients (None = zero).  Returns a dict with the
     gradient of every key of ``w`` (fc_* only when g_classes or g_max is given, q2_* only when nonlinear) and
     ``vals`` (when want_g_vals).  ``g_max`` [C]: the sparse gradient of max_n classes[n,:] (the training objective's
-    instance stream); ``row_map``: see agg_forward (N = its length)."""
+    instance stream); ``row_map``: see agg_forward (N = its length).  ``want_g_feats``: also return ``feats``, the
+    gradient of the input rows [N,K] in LOGICAL row order (dsmil_agg_backward_rows, one more launch: k_bwd_gx); with
+    caller-supplied ``vals`` it leaves out the value stream's share (value_proj_backward_rows adds that).  A call without
+    it is dsmil_agg_backward_ex as before."""
     feats = _f32c(feats, "feats")
     dev = feats.device
     N, K = feats.shape
@@ -563,12 +592,20 @@ def agg_backward(feats, w, A, B, idx, g_pred, g_classes=None, g_A=None, g_B=None
     L = _native.lib()
     nbytes = L.dsmil_agg_backward_workspace_bytes(N, K, Kv, C)
     ws = _workspace(dev, nbytes)
+    g_feats = new(N, K) if want_g_feats else None
     with torch.cuda.device(dev):
-        rc = L.dsmil_agg_backward_ex(_ptr(feats), _ptr(vals), N, ctypes.byref(p), _ptr(A), _ptr(B), _ptr(idx),
-                                     _ptr(g_classes), _ptr(g_max), _ptr(g_pred), _ptr(g_A), _ptr(g_B), ctypes.byref(g),
-                                     _ptr(g_vals), _ptr(row_map), _ptr(ws), ws.numel(), _stream(dev))
-    _native.check(rc, "dsmil_agg_backward_ex")
+        if want_g_feats:
+            rc = L.dsmil_agg_backward_rows(_ptr(feats), _ptr(vals), N, ctypes.byref(p), _ptr(A), _ptr(B), _ptr(idx),
+                                           _ptr(g_classes), _ptr(g_max), _ptr(g_pred), _ptr(g_A), _ptr(g_B), ctypes.byref(g),
+                                           _ptr(g_vals), _ptr(row_map), _ptr(ws), ws.numel(), _stream(dev), _ptr(g_feats))
+        else:
+            rc = L.dsmil_agg_backward_ex(_ptr(feats), _ptr(vals), N, ctypes.byref(p), _ptr(A), _ptr(B), _ptr(idx),
+                                         _ptr(g_classes), _ptr(g_max), _ptr(g_pred), _ptr(g_A), _ptr(g_B), ctypes.byref(g),
+                                         _ptr(g_vals), _ptr(row_map), _ptr(ws), ws.numel(), _stream(dev))
+    _native.check(rc, "dsmil_agg_backward_rows" if want_g_feats else "dsmil_agg_backward_ex")
     del keep
+    if want_g_feats:
+        out["feats"] = g_feats
     if want_g_vals:
         out["vals"] = g_vals
     return out

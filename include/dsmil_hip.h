@@ -258,6 +258,24 @@ int dsmil_agg_backward(const float* feats, const float* vals, int64_t N, const d
                        const float* g_pred, const float* g_A, const float* g_B,
                        const dsmil_agg_grads* g, float* g_vals, void* ws, size_t ws_bytes,
                        void* stream);
+/* dsmil_agg_backward_rows: everything dsmil_agg_backward_ex does, plus the gradient of the INPUT rows — what autograd
+ * leaves in `x.grad` for `x.requires_grad_(); loss.backward()` through MILNet.forward (dsmil.py:70-74), i.e. through the
+ * query stream (dsmil.py:49,53-55), FCLayer (dsmil.py:10-12) and, for v = Identity, `B = A^T V` (dsmil.py:57):
+ *     g_feats [N, K] = gH q0_w  (+ g_classes fc_w)  (+ g_max[c] fc_w[c] at row idx_c)  (+ A gB  when vals is feats / NULL)
+ * OVERWRITTEN, fp32, in LOGICAL row order when row_map is given (the convention of A and g_vals; the caller scatters it
+ * if it wants physical rows).  With caller-supplied value rows (passing_v) the value stream's share is NOT included: it
+ * reaches the rows through the caller's v layer — dsmil_value_backward_rows adds it.  p->fc_w must be given when g_classes
+ * or g_max is.  g_feats == NULL behaves exactly as dsmil_agg_backward_ex (same launches, same bits); with g_feats one
+ * more launch (k_bwd_gx, csrc/agg_gx.h), deterministic.  The workspace is the backward's
+ * (dsmil_agg_backward_rows_workspace_bytes == dsmil_agg_backward_workspace_bytes today).
+ * Added without a change of DSMIL_ABI_VERSION (it stays 6, no existing signature moved): a caller detects this entry
+ * and dsmil_value_backward_rows by SYMBOL (dlsym / hasattr on the loaded library). */
+size_t dsmil_agg_backward_rows_workspace_bytes(int64_t N, int32_t K, int32_t Kv, int32_t C);
+int dsmil_agg_backward_rows(const float* feats, const float* vals, int64_t N, const dsmil_agg_params* p,
+                            const float* A, const float* B, const int64_t* idx, const float* g_classes,
+                            const float* g_max, const float* g_pred, const float* g_A, const float* g_B,
+                            const dsmil_agg_grads* g, float* g_vals, const int64_t* row_map, void* ws,
+                            size_t ws_bytes, void* stream, float* g_feats);
 
 /* ---- the value stream of BClassifier(passing_v=True) (ABI 6) ---------------------------------------------------------
  * Replaces `V = self.v(feats)` of dsmil.py:48 with self.v = Sequential(Dropout, Linear(K, K), ReLU) (dsmil.py:35-39; the
@@ -276,7 +294,16 @@ int dsmil_agg_backward(const float* feats, const float* vals, int64_t N, const d
  *                        PARAMETERS:  gZ = g_vals * (V > 0),  g_v_w [Kv, K] = gZ^T feats,  g_v_b [Kv] = column sums of gZ
  *                        (both OVERWRITTEN; gZ is never written to memory; bf16 MFMA over exact three-plane cuts, fixed-order
  *                        two-stage sums: two runs give the same bits).  V, g_vals [rows, Kv] in logical order.  The gradient of
- *                        the input rows (gZ v_w) is not computed here.  Two launches. */
+ *                        the input rows (gZ v_w) is not computed here (dsmil_value_backward_rows does).  Two launches.
+ *   dsmil_value_backward_rows  what autograd derives for dsmil.py:35-39,48 behind g_vals for the layer's INPUT rows:
+ *                        g_feats [rows, K] = (g_vals * (V > 0)) v_w, or g_feats += that with accumulate != 0 (the
+ *                        aggregator's own g_feats and this term then share one buffer, no separate add pass).  Logical row
+ *                        order throughout.  gZ is never written to memory; bf16 MFMA over exact three-plane cuts, six plane
+ *                        products, fixed order: two runs give the same bits.  One launch (k_value_gx, csrc/agg_gx.h), any K
+ *                        and Kv on the matrix cores.  feats and packed are not read by this product (v_w is cut as it is
+ *                        staged: the forward's image is ordered along K, this contraction runs along Kv) and may be NULL;
+ *                        it needs no workspace: ws may be NULL (ws_bytes 0); a non-NULL ws must be 256-B aligned.
+ *                        Detected by symbol, see dsmil_agg_backward_rows. */
 size_t dsmil_value_packed_bytes(int32_t K, int32_t Kv);
 int dsmil_value_pack(const float* v_w, int32_t K, int32_t Kv, void* packed, void* stream);
 size_t dsmil_value_workspace_bytes(int64_t rows, int32_t K, int32_t Kv);
@@ -284,6 +311,9 @@ int dsmil_value_forward(const float* feats, int64_t rows, int32_t K, int32_t Kv,
                         const void* packed, const int64_t* row_map, float* V_out, void* ws, size_t ws_bytes, void* stream);
 int dsmil_value_backward(const float* feats, const float* V, const float* g_vals, int64_t rows, int32_t K, int32_t Kv,
                          const int64_t* row_map, float* g_v_w, float* g_v_b, void* ws, size_t ws_bytes, void* stream);
+int dsmil_value_backward_rows(const float* feats, const float* V, const float* g_vals, int64_t rows, int32_t K, int32_t Kv,
+                              const float* v_w, const void* packed, int32_t accumulate, float* g_feats, void* ws,
+                              size_t ws_bytes, void* stream);
 
 /* ---- one training step per C call (ABI 3) --------------------------------------------------------
  * Replaces the body of the reference's training loop for one bag, train_tcga.py:60-75 (train_mil.py:44-56 likewise):
