@@ -34,6 +34,38 @@ class AggOpts(ctypes.Structure):
     _fields_ = [("packed_split", ctypes.c_void_p), ("row_map", ctypes.c_void_p), ("packed_f2", ctypes.c_void_p)]
 
 
+class AggCall(ctypes.Structure):
+    """struct dsmil_agg_call (include/dsmil_hip.h): a forward call as the library's route function sees it."""
+    _fields_ = [("total_rows", ctypes.c_int64), ("max_rows", ctypes.c_int64)] + [(n, ctypes.c_int32) for n in (
+        "n_bags", "K", "Kv", "C", "nonlinear", "bf16", "aligned", "classes_given", "vals_separate", "row_map", "packed_split",
+        "packed_f2", "phase", "skip_pred", "prologue_job", "several_streams", "cus")]
+
+
+class AggRoute(ctypes.Structure):
+    """struct dsmil_agg_route (include/dsmil_hip.h): the kernels dsmil_agg_forward_route answers for a call."""
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "nw", "r0", "logits", "logits_vec", "logits_cp", "prologue", "rowmax", "qmax", "qmax_vec", "qmax_threads", "ragged",
+        "ragged_attend", "tile_attend", "tile_logits", "image", "attend", "attend_nw", "attend_vec", "attend_np", "attend_xe",
+        "attend_tu", "finish", "finish_rows", "pred")]
+
+
+# enum values of include/dsmil_hip.h, by position
+LOGITS = ("none", "given", "stream", "pipe", "argmax")
+QMAX = ("launch", "inline", "shard1", "shard2")
+IMAGE = ("none", "f2_caller", "f2_cut", "split_caller", "split_cut", "bf16")
+ATTEND = ("none", "f3", "f2", "bf16_res", "bf16_dma", "bf16_ring", "split", "hs", "f32")
+FINISH = ("none", "lean", "vec4", "scalar")
+
+
+def forward_route(**call):
+    """dsmil_agg_forward_route for a call given as dsmil_agg_call fields (missing ones are 0; ``aligned`` defaults to 7: every
+    operand 16-byte aligned).  Touches no device when ``cus`` is given."""
+    c = AggCall(**dict({"aligned": 7}, **call))
+    r = AggRoute()
+    check(lib().dsmil_agg_forward_route(ctypes.byref(c), ctypes.byref(r)), "dsmil_agg_forward_route")
+    return r
+
+
 class AggGrads(ctypes.Structure):
     """struct dsmil_agg_grads (include/dsmil_hip.h)."""
     _fields_ = [(n, ctypes.c_void_p) for n in
@@ -77,6 +109,7 @@ SIGNATURES = {
                                               c_f32p, c_f32p, c_f32p, ctypes.c_void_p, ctypes.c_size_t,
                                               ctypes.c_void_p]),
     "dsmil_agg_tile_rows": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64]),
+    "dsmil_agg_forward_route": (ctypes.c_int, [ctypes.POINTER(AggCall), ctypes.POINTER(AggRoute)]),
     "dsmil_agg_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
                                                     ctypes.c_int32, ctypes.c_int32]),
     "dsmil_agg_packed_bf16_bytes": (ctypes.c_size_t, [ctypes.c_int32]),

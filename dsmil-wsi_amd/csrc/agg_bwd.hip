@@ -1116,7 +1116,6 @@ inline unsigned long long* tn_trace_buffer() {
     return buf;
 }
 #endif
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 struct BwdWs {
     size_t gB, Dv, zero, qmax, gq, gA, gs, gz2, Hb, Qb, gH, gqp, wsplit, w2t, part0, part1, pb0, pb1, part, part_b, off, total;
     int splits, rows;   // k_tn_small (dense instance-logit gradient)
@@ -1163,8 +1162,6 @@ BwdWs bwd_layout(long long N, int K, int Kv, int C, int nonlinear) {
     w.total = o;
     return w;
 }
-
-__global__ void k_set_offsets(int64_t* off, long long N) { off[0] = 0; off[1] = N; }
 
 template <typename KernelT, typename ArgT>
 int launch_tile_kernel(KernelT kern, const ArgT& arg, int nw, bool dma, long long N, hipStream_t st) {
@@ -1512,7 +1509,7 @@ int dsmil_agg_train_step(const float* feats, int64_t N, const int64_t* row_map, 
     const float* qmax = nullptr;
     const float* pred_part = nullptr;
     int pred_blocks = 0;
-    dsmil_agg_forward_leftovers(w8 + L.fwd, 1, N, K, K, C, nullptr, &qmax, &pred_part, &pred_blocks);
+    dsmil_agg_forward_leftovers(w8 + L.fwd, 1, N, K, K, C, &qmax, &pred_part, &pred_blocks);
     const LossHeadArgs lh{label, classes, (unfuse & 4) ? pred : nullptr, idx, loss, mx, gpred, gmax, pred_part, p->fcc_b, pred, pred_blocks};
     // optimizer.step() (train_tcga.py:73): Adam over the eight tensors, applied by the backward's last launch (k_bwd_reduce)
     // to the gradient elements it has just formed; scalars formed in double as in dsmil_adam_step

@@ -11,11 +11,9 @@ int dsmil_fc_forward_rows(const float* feats, int64_t total_rows, int32_t K, int
                           const float* fc_b, float* classes, const int64_t* rowmap, void* stream);
 
 // library-internal (defined in agg_fwd.hip): what a finished fp32 dsmil_agg_forward(_ex) call leaves in its workspace for
-// the backward of the same bag — the plane-cut query weights (null if the forward did not cut them: caller-supplied
-// packed_split, or an MFMA form without planes) and q_max [n_bags, C, 128]
+// the backward of the same bag — q_max [n_bags, C, 128] and k_finish's partial bag heads (read from the forward's layout)
 void dsmil_agg_forward_leftovers(void* ws, int32_t n_bags, int64_t total_rows, int32_t K, int32_t Kv, int32_t C,
-                                 const void** packed_split, const float** qmax, const float** pred_part = nullptr,
-                                 int* pred_blocks = nullptr);
+                                 const float** qmax, const float** pred_part = nullptr, int* pred_blocks = nullptr);
 // library-internal: dsmil_agg_forward_ex WITHOUT its last launch (k_pred): pred[o] = fcc_b[o] + the sum of
 // pred_part[block][o][c] in (block, c) order is left to the caller (dsmil_agg_train_step: the loss head of k_bwd_prep)
 // `job` (dsmil_agg_train_step): what k_train_prologue does — plane-cut W1 | W2 (-> wsplit), W2^T (-> w2t) and the lone bag's
@@ -42,6 +40,9 @@ constexpr int BK = 32;           // k-chunk staged per pipeline step
 constexpr int LDK = BK + 4;      // LDS row stride in floats (144 B): conflict-free ds_read_b128
 constexpr int W_TILE = QD * LDK; // floats per staged weight chunk
 constexpr int R0 = 128;          // rows per workgroup of k_logits_argmax
+
+inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }   // workspace regions start on 256-B boundaries
+__global__ void k_set_offsets(int64_t* off, long long N) { off[0] = 0; off[1] = N; }   // the {0, N} offsets of a lone bag
 
 // Wave-wide sum / max, every lane gets the result.  On DPP: row_ror 8, 4, 2, 1 inside the four 16-lane rows (every lane of a
 // row then holds the row's value), then the four rows through v_readlane and three scalar-operand VALU ops — ~11 instructions,

@@ -9,22 +9,22 @@
 //   A    = softmax_n(Q qmax^T / sqrt(128))        attention over instances   [N,C]
 //   B    = A^T V,  pred = Conv1d(C,C,K)(B)         bag embedding / bag logits
 //
-// Launch sequence on one stream (no host sync, hipGraph-capturable):
-//   k_logits_stream   HBM stream over x: c, per-tile (max,idx) partials (8 lanes per row, full-line
-//                     non-temporal loads; k_logits_argmax is the general form: bf16 rows, K % 4 != 0,
-//                     caller-supplied logits)
-//   k_qmax            per (bag,class): finish argmax, run the query MLP on the critical row
-//   k_pack_agg_split  cut the query weights into three exact bf16 planes, MFMA-fragment order
-//   k_query_attend_split  the dominant kernel: per 32-row wave tile the query MLP runs TRANSPOSED
-//                     (H^T = W1 X^T keeps instances on the MFMA column axis, so the ReLU'd H^T
-//                     accumulator registers are fed straight back as the B operand of Q^T = W2 H^T:
-//                     no LDS round trip) on bf16 MFMA over exact three-plane cuts of the fp32
-//                     operands (agg_split.h; DSMIL_MLP=f32 selects k_query_attend on
-//                     v_mfma_f32_32x32x2_f32); scores, tile-local softmax statistics and the weighted
-//                     value sum are fused behind it.  Q is never written to memory.
-//   k_finish, k_pred  combine tile partials: A = exp(s-m)/l, B, pred
-// dsmil_agg_shard_* (one bag sharded by instances over several GPUs) run the same kernels in two
-// phases around the caller's exchanges.
+// Launch sequence on one stream (no host sync, hipGraph-capturable); which kernel fills each step is the ROUTE of the call,
+// chosen in pick_route() below from its shape, dtype, alignment and options (DESIGN.md §3 has the table):
+//   logits     k_logits_stream: HBM stream over x: c, per-tile (max,idx) partials (8 lanes per row, full-line non-temporal
+//              loads); k_logits_pipe beside another stream's resident attend kernel; k_logits_argmax is the general form
+//              (K % 4 != 0, caller-supplied logits)
+//   q_max      k_qmax per (bag,class): finish argmax, run the query MLP on the critical row (or inside k_attend_hs)
+//   weights    k_pack_agg_split / k_pack_agg_f2 cut the query weights into MFMA-fragment planes unless the caller did
+//   attend     the dominant kernel.  k_query_attend_split: per 32-row wave tile the query MLP runs TRANSPOSED
+//              (H^T = W1 X^T keeps instances on the MFMA column axis, so the ReLU'd H^T accumulator registers are fed
+//              straight back as the B operand of Q^T = W2 H^T: no LDS round trip) on bf16 MFMA over exact three-plane cuts
+//              of the fp32 operands (agg_split.h); scores, tile-local softmax statistics and the weighted value sum are
+//              fused behind it, Q is never written to memory.  k_attend_hs (few rows), k_attend_f3 / k_attend_f2 (fp32
+//              batches), k_attend_bf16_res / k_query_attend_bf16_dma / k_query_attend_bf16 (bf16 rows) are its other forms.
+//   finish     k_finish, k_pred combine tile partials: A = exp(s-m)/l, B, pred
+// dsmil_agg_shard_* (one bag sharded by instances over several GPUs) run the same steps in two phases around the caller's
+// exchanges.
 //
 // MFMA fragment maps used (cdna_hip_programming.md §3): 32x32x2 f32: A lane l = A[i=l&31][k=l>>5],
 // B lane l = B[k=l>>5][j=l&31], D lane l reg r = D[(r&3)+8*(r>>2)+4*(l>>5)][l&31].
@@ -1357,26 +1357,54 @@ __global__ __launch_bounds__(256) void k_fc(const float* __restrict__ feats,
 }
 
 // ---- host side ------------------------------------------------------------------------------
+// agg_forward_impl: validate, lay out the workspace (ws_layout), pick the route (pick_route), then
+//   logits -> q_max -> weight image -> attend -> finish -> pred,
+// each step a switch on the route.  WHICH kernels a call takes is decided in pick_route() and nowhere else
+// (dsmil_agg_forward_route asks it from outside); HOW a kernel is launched — grid, LDS bytes, arguments — is written once
+// per kernel family next to its launch.
 struct WsLayout {
     size_t part_val, part_idx, qmax, qflag, part_ml, part_B, pred_part, wsplit, wf2, rowmax, off2, tile_pre, total;
     long long slots0, slots, nchunk_max;
 };
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// Experiment builds (-DDSMIL_EXPERIMENTS) read ablation / geometry knobs from the environment, once per
-// process; the product build has none of them.
+// Experiment builds (-DDSMIL_EXPERIMENTS) read ablation / geometry knobs from the environment, once per process; the
+// product build has the all-zero instance, so every branch on a knob folds away.
+struct Expt {
+    int bits;          // DSMIL_EXPT: 8 no k_attend_hs + the XE split form, 16 / 32 the split kernel's TU forms, 64 stamp trace (no combine),
+                       // 256 no bf16 DMA kernel, 512 no k_attend_bf16_res, 1024 / 2048 its ablation forms; the kernels read the rest
+    int nw;            // DSMIL_NW: 8 | 4 | 1 forces the tile regime
+    int lds_pad;       // DSMIL_LDS_PAD: extra dynamic LDS of the split / hs kernels (forces 1 block per CU)
+    int logits_old;    // DSMIL_LOGITS_OLD: k_logits_argmax instead of the streaming kernels
+    int no_hs, no_qmi, no_f2;   // DSMIL_NO_HS, DSMIL_NO_QMI, DSMIL_NO_F2
+    int f2_abl, f2_grid, f3_dbg;   // DSMIL_F2_ABL, DSMIL_F2_GRID, DSMIL_F3_DBG: forms / grid of the resident kernels
+    int no_prologue_role;          // DSMIL_NO_PROLOGUE_ROLE: the training prologue stays its own launch
+    int mlp;           // DSMIL_MLP: 0 = six plane products (the product form), 1 = f32, 9 = s9
+};
 #ifdef DSMIL_EXPERIMENTS
-int expt_env(const char* name) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : 0;
+const Expt& expt() {
+    static const Expt e = [] {
+        auto env = [](const char* name) { const char* v = getenv(name); return v ? atoi(v) : 0; };
+        const char* m = getenv("DSMIL_MLP");
+        return Expt{env("DSMIL_EXPT"), env("DSMIL_NW"), env("DSMIL_LDS_PAD"), env("DSMIL_LOGITS_OLD"), env("DSMIL_NO_HS"),
+                    env("DSMIL_NO_QMI"), env("DSMIL_NO_F2"), env("DSMIL_F2_ABL"), env("DSMIL_F2_GRID"), env("DSMIL_F3_DBG"),
+                    env("DSMIL_NO_PROLOGUE_ROLE"), !m ? 0 : !strcmp(m, "f32") ? 1 : !strcmp(m, "s9") ? 9 : 0};
+    }();
+    return e;
 }
+#else
+constexpr Expt kNoExpt{};
+constexpr const Expt& expt() { return kNoExpt; }
 #endif
+
+// Which MFMA form the fp32 query MLP uses (see agg_split.h).  Default: 6 plane products — the three left
+// out are together below 2^-20 of |x*w|, i.e. below the fp32 accumulation rounding the reference's own
+// 512-long dot products carry (tests/accuracy_report.py: identical measured error for 0 / 9 / 6).
+// Experiment builds (libdsmil_hip_expt.so): DSMIL_MLP = s9 | f32 selects the bit-exact-product forms.
+int mlp_mode() { return expt().mlp == 1 ? 0 : expt().mlp == 9 ? 9 : 6; }
 
 int pick_nw(int n_bags, long long total_rows) {
-#ifdef DSMIL_EXPERIMENTS
-    static const int force = expt_env("DSMIL_NW");
+    const int force = expt().nw;
     if (force == 8 || force == 4 || force == 1) return force;
-#endif
     // 128-row workgroups (4 waves) once they alone give >= 2 workgroups per CU; otherwise
     // 32-row single-wave workgroups so that a lone bag still spreads over the chip.
     const long long tiles128 = total_rows / 128 + n_bags;
@@ -1385,57 +1413,30 @@ int pick_nw(int n_bags, long long total_rows) {
 
 inline size_t f2_image_bytes(int K) { return (size_t)(2 * ((K + 31) / 32) + 8) * F2_CHUNK_F4 * 16 + F2_TRAILER_BYTES; }
 
-WsLayout ws_layout(int n_bags, long long total_rows, long long max_rows, int K, int Kv, int C, int BM) {
+WsLayout ws_layout(int n_bags, long long total_rows, long long max_rows, int K, int Kv, int C) {
     WsLayout w;
+    const int BM = pick_nw(n_bags, total_rows) * 32;
     w.slots0 = total_rows / 32 + n_bags + 1;   // (32 = the smallest rows-per-workgroup of the logits kernels)
     const int bms = BM > F2_BM ? F2_BM : BM;   // (k_attend_f2 runs 64-row tiles in the 128-row regime)
     w.slots = total_rows / bms + n_bags + 1;
     if (w.slots < RS_MAX_WG + n_bags) w.slots = RS_MAX_WG + n_bags;   // k_attend_bf16_res: one slot per (workgroup, bag) pair, slot = workgroup + bag
     w.nchunk_max = finish_blocks(max_rows, Kv);
     size_t o = 0;
-    w.part_val = o; o = al(o + (size_t)w.slots0 * C * sizeof(float));
-    w.part_idx = o; o = al(o + (size_t)w.slots0 * C * sizeof(long long));
-    w.qmax = o; o = al(o + (size_t)n_bags * C * QD * sizeof(float));
-    w.qflag = o; o = al(o + (size_t)n_bags * C * sizeof(int));   // k_attend_hs: hand-off flags of the in-launch critical query
-    w.part_ml = o; o = al(o + (size_t)w.slots * C * 2 * sizeof(float));
-    w.part_B = o; o = al(o + (size_t)w.slots * C * Kv * sizeof(float));
-    w.pred_part = o; o = al(o + (size_t)n_bags * w.nchunk_max * C * C * sizeof(float));
-    w.wsplit = o; o = al(o + (size_t)(2 * ((K + 31) / 32) + 8) * S3_CHUNK_F4 * 16);  // cut query weights
-    w.wf2 = o; o = al(o + f2_image_bytes(K));     // k_attend_f2: fp16 two-plane query weights (when the caller brought none)
-    w.rowmax = o; o = al(o + (size_t)total_rows * sizeof(float));   // k_attend_f2: max |x| per row (k_logits_stream)
-    w.off2 = o; o = al(o + 2 * sizeof(int64_t));  // {0, N} of a lone shard (dsmil_agg_shard_*)
-    w.tile_pre = o; o = al(o + (size_t)2 * (n_bags + 1) * sizeof(int));   // ragged batches: tile prefixes of the persistent kernel and of the logits pass
+    auto take = [&](size_t bytes) { size_t p = o; o = al(o + bytes); return p; };
+    w.part_val = take((size_t)w.slots0 * C * sizeof(float));
+    w.part_idx = take((size_t)w.slots0 * C * sizeof(long long));
+    w.qmax = take((size_t)n_bags * C * QD * sizeof(float));
+    w.qflag = take((size_t)n_bags * C * sizeof(int));   // k_attend_hs: hand-off flags of the in-launch critical query
+    w.part_ml = take((size_t)w.slots * C * 2 * sizeof(float));
+    w.part_B = take((size_t)w.slots * C * Kv * sizeof(float));
+    w.pred_part = take((size_t)n_bags * w.nchunk_max * C * C * sizeof(float));
+    w.wsplit = take((size_t)(2 * ((K + 31) / 32) + 8) * S3_CHUNK_F4 * 16);  // cut query weights
+    w.wf2 = take(f2_image_bytes(K));     // k_attend_f2: fp16 two-plane query weights (when the caller brought none)
+    w.rowmax = take((size_t)total_rows * sizeof(float));   // k_attend_f2: max |x| per row (k_logits_stream)
+    w.off2 = take(2 * sizeof(int64_t));  // {0, N} of a lone shard (dsmil_agg_shard_*)
+    w.tile_pre = take((size_t)2 * (n_bags + 1) * sizeof(int));   // ragged batches: tile prefixes of the persistent kernel and of the logits pass
     w.total = o;
     return w;
-}
-
-template <int NW, int VEC>
-int launch_attend(const AttendArgs& a, long long max_rows, int n_bags, hipStream_t st) {
-    constexpr int BM = NW * 32;
-    const size_t lds = (size_t)(2 * W_TILE + 2 * BM * LDK) * sizeof(float);
-    if (!dsmil_lds::allow((const void*)k_query_attend<NW, VEC>, (int)lds)) return DSMIL_E_LAUNCH;
-    dim3 grid((unsigned)((max_rows + BM - 1) / BM), (unsigned)n_bags);
-    const int slot = dsmil_prof::begin(dsmil_prof::CH_ATTEND, st);
-    hipLaunchKernelGGL((k_query_attend<NW, VEC>), grid, dim3(NW * 64), lds, st, a);
-    dsmil_prof::end(dsmil_prof::CH_ATTEND, slot, st);
-    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
-}
-
-template <int NW, int VEC, int NP, bool XE = false, int TU = 8>
-int launch_attend_split(const AttendArgs& a, long long max_rows, int n_bags, hipStream_t st) {
-    constexpr int BM = NW * 32;
-    size_t lds = VEC == 4 ? (size_t)(3 * S3_CHUNK_F4 * 4 + 2 * BM * 32) * sizeof(float)
-                          : (size_t)(2 * S3_CHUNK_F4 * 4 + 2 * BM * LDK) * sizeof(float);
-#ifdef DSMIL_EXPERIMENTS
-    static const int lds_pad = expt_env("DSMIL_LDS_PAD");  // force 1 block/CU
-    lds += (size_t)lds_pad;
-#endif
-    if (!dsmil_lds::allow((const void*)k_query_attend_split<NW, VEC, NP, XE, TU>, (int)lds)) return DSMIL_E_LAUNCH;
-    dim3 grid((unsigned)((max_rows + BM - 1) / BM), (unsigned)n_bags);
-    const int slot = dsmil_prof::begin(dsmil_prof::CH_ATTEND, st);
-    hipLaunchKernelGGL((k_query_attend_split<NW, VEC, NP, XE, TU>), grid, dim3(NW * 64), lds, st, a);
-    dsmil_prof::end(dsmil_prof::CH_ATTEND, slot, st);
-    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 
 // Compute units of the current device (cached per device id; 256 on MI355X).
@@ -1461,7 +1462,6 @@ std::atomic<int> g_use_f2{2};
 // A CONSTANT (256 = the CUs of an unpartitioned MI355X), not the visible CU count: the run length `per` fixes which tiles
 // share a partial, i.e. the fp32 summation order, so the outputs must not depend on the box (partition mode, masked CUs).
 std::atomic<int> g_persistent_grid{256};
-// DSMIL_LOGITS_PIPE=0: the bf16 batch path keeps k_logits_stream (A/B of the co-resident logits pass, round 6)
 // dsmil_agg_logits_form(): bf16 batches of K = 512 rows, C <= 2 have a second set of kernels around the persistent attend
 // kernel — k_logits_pipe, a 4-wave k_qmax, the lean k_finish — that fit beside a resident k_attend_bf16_res workgroup of
 // ANOTHER stream's batch.  2 = always, 0 = never (k_logits_stream, 16-wave k_qmax, k_finish: what every other shape takes),
@@ -1469,7 +1469,9 @@ std::atomic<int> g_persistent_grid{256};
 // kernels are ~6 % slower per pass (a narrower q_max launch, fewer bytes in flight per wave), beside another stream's attend
 // kernel they make the pass 12-17 % faster.  Bit-identical outputs in every mode.
 std::atomic<int> g_logits_form{1};
-bool several_streams_recently(hipStream_t st) {   // the last four batch calls did not all come in on this stream
+// The last four batch calls did not all come in on this stream.  RECORDS the stream: only a real forward call whose shape
+// could take k_logits_pipe (pipe_shape) asks, a route query never does.
+bool several_streams_recently(hipStream_t st) {
     static std::atomic<uintptr_t> ring[4];
     static std::atomic<unsigned> pos{0};
     const uintptr_t me = (uintptr_t)st + 1;       // (0 = empty slot; the null stream is a stream)
@@ -1483,47 +1485,177 @@ bool several_streams_recently(hipStream_t st) {   // the last four batch calls d
 }
 constexpr int PIPE_R0 = 512;   // rows per k_logits_pipe workgroup (workgroups enter a CU's one free slot one at a time)
 constexpr int PIPE_QT = 256;   // threads of the k_qmax launch in front of a co-resident pass
-bool coresident_wanted(hipStream_t st) {
-    const int form = g_logits_form.load(std::memory_order_relaxed);
-    const bool several = several_streams_recently(st);      // (always recorded, whatever the mode)
-    return form == 2 || (form == 1 && several);
-}
 int persistent_grid(int cap) {
     int g = g_persistent_grid.load(std::memory_order_relaxed);
     if (g <= 0) g = 256;
     return g < cap ? g : cap;
 }
 
-// The in-launch hand-off needs its producers to RUN while tiles spin on their flags.  Producers are the first workgroups of
-// every grid row and the hardware dispatches a grid in order, but HIP promises neither: the query is inlined only when
-// every workgroup of the launch can be resident at once (k_attend_hs: 2 workgroups per CU by LDS and registers), so that
-// progress does not depend on dispatch order at all.  Larger batches take the k_qmax launch.
-bool hs_inline_fits(long long max_rows, int n_bags, int C) {
-    const long long wgs = ((max_rows + HS_BM - 1) / HS_BM + C) * (long long)n_bags;
-    return wgs <= 2LL * device_cus();
+// ---- the route ------------------------------------------------------------------------------
+typedef dsmil_agg_call Call;
+typedef dsmil_agg_route Route;
+
+// 16-byte alignment facts of a call's fp32 operands (dsmil_agg_call::aligned)
+int aligned_bits(const void* feats, const void* vals, const dsmil_agg_params* p, const void* crit_rows) {
+    const uintptr_t all = (uintptr_t)feats | (uintptr_t)vals | (uintptr_t)p->q0_w | (uintptr_t)p->fc_w |
+                          (uintptr_t)(p->nonlinear ? p->q2_w : p->q0_w);
+    const uintptr_t w = (uintptr_t)p->q0_w | (uintptr_t)p->fc_w, r = (uintptr_t)crit_rows | (uintptr_t)p->q0_w;
+    return (all % 16 == 0 ? 1 : 0) | (w % 16 == 0 ? 2 : 0) | (r % 16 == 0 ? 4 : 0);
+}
+// 16-B vector loads on every operand of the forward / on the FCLayer and query weights
+bool call_v4(const Call& c) { return c.bf16 || ((c.K % 4 == 0) && (c.Kv % 4 == 0) && (c.aligned & 1)); }
+bool call_w4(const Call& c) { return (c.K % 4 == 0) && (c.aligned & 2); }
+// the streaming logits kernels (k_logits_stream / k_logits_pipe) can read this call's rows
+bool stream_ok(const Call& c) { return !c.classes_given && !expt().logits_old && (c.bf16 ? (c.K % 8 == 0) : call_v4(c)); }
+// bf16 batches of K = 512 rows: the shape k_logits_pipe is written for.  Whether it is WANTED depends on the streams the
+// library has seen: agg_forward_impl consults (and feeds) that record for calls of this shape only.
+bool pipe_shape(const Call& c) {
+    return c.bf16 && stream_ok(c) && c.K == 512 && c.C <= 2 && pick_nw(c.n_bags, c.total_rows) == 4 && c.phase == 0 &&
+           !c.row_map && c.max_rows < 0x7fffffffLL;
 }
 
-int launch_attend_hs(const AttendArgs& a, long long max_rows, int n_bags, hipStream_t st) {
-    size_t lds = HS_LDS_BYTES;
-#ifdef DSMIL_EXPERIMENTS
-    static const int lds_pad = expt_env("DSMIL_LDS_PAD");  // force 1 block/CU
-    lds += (size_t)lds_pad;
-#endif
-    if (!dsmil_lds::allow((const void*)k_attend_hs<6>, (int)lds)) return DSMIL_E_LAUNCH;
-    dim3 grid((unsigned)((max_rows + HS_BM - 1) / HS_BM + (a.qm_flag ? a.C : 0)), (unsigned)n_bags);
+// Launches nothing, needs no device when c.cus is given.  Order of the tests inside each step = priority of the kernels.
+Route pick_route(const Call& c) {
+    const Expt& ex = expt();
+    const int K = c.K, C = c.C, NW = pick_nw(c.n_bags, c.total_rows), BM = NW * 32;
+    const bool bf16 = c.bf16, v4 = call_v4(c), w4 = call_w4(c), sok = stream_ok(c), same_vals = !c.vals_separate;
+    const int batch_form = g_use_f2.load(std::memory_order_relaxed), logits_form = g_logits_form.load(std::memory_order_relaxed);
+    Route r{};
+    r.nw = NW;
+    // 1. instance logits + arg-max partials.  k_logits_pipe (fits beside a resident k_attend_bf16_res workgroup of another
+    // stream): its workgroups take more rows (they are dispatched one at a time into the one free slot of a CU) and its k_qmax
+    // launch is 4 waves wide so that it fits the same slot
+    const bool lpipe = pipe_shape(c) && (logits_form == 2 || (logits_form == 1 && c.several_streams));
+    // rows per workgroup: 32 instead of R0 when there are few rows (the 32-row regime) and a streaming kernel runs
+    r.r0 = lpipe ? PIPE_R0 : (NW == 1 && sok && c.phase != 2) ? 32 : R0;
+    if (c.phase == 2) r.logits = DSMIL_LOGITS_NONE;   // the caller already knows the bag-wide critical rows
+    else if (c.classes_given) { r.logits = DSMIL_LOGITS_GIVEN; r.logits_vec = 1; }
+    else if (sok) { r.logits = lpipe ? DSMIL_LOGITS_PIPE : DSMIL_LOGITS_STREAM; r.logits_cp = C >= 2 ? 2 : 1; }
+    else { r.logits = DSMIL_LOGITS_ARGMAX; r.logits_vec = (bf16 ? w4 : v4) ? 4 : 1; }
+    r.prologue = c.prologue_job && r.logits == DSMIL_LOGITS_STREAM && !bf16;
+    // few rows, fp32: k_attend_hs; with a streaming logits kernel before it, the critical row's query runs inside the attend
+    // launch (AttendArgs::qm_flag) instead of as k_qmax between the two
+    const bool use_hs = !bf16 && NW == 1 && v4 && !ex.no_hs && mlp_mode() == 6 && !(ex.bits & 8);
+    // batches (128-row regime), fp32, v = Identity, K a multiple of 128 up to 512: the resident kernels on the fp16 two-plane
+    // form (agg_f2.h, agg_f3.h); they need the row maxima the streaming logits kernel leaves behind
+    const bool use_f2 = !bf16 && NW == 4 && v4 && !ex.no_f2 && mlp_mode() == 6 && sok && c.phase == 0 && same_vals &&
+                        (K % 128 == 0) && K <= 16 * F2_MAXSTEPS && batch_form;
+    r.rowmax = use_f2;
+    // RAGGED batch in the 128-row regime (the persistent attend kernels and the streaming logits pass): the work lists are the
+    // real tiles (prefix per bag: k_tile_prefix), not n_bags x the tiles of the longest bag
+    r.ragged = NW == 4 && sok && c.phase == 0 && (long long)c.max_rows * c.n_bags != (long long)c.total_rows &&
+               c.total_rows / 32 + c.n_bags < 0x7fffffffLL;
+    r.tile_attend = bf16 ? RS_BM : F3_BM;
+    r.tile_logits = r.r0;
+    // 2. critical instance + its query.  The in-launch hand-off needs its producers to RUN while tiles spin on their flags.
+    // Producers are the first workgroups of every grid row and the hardware dispatches a grid in order, but HIP promises
+    // neither: the query is inlined only when every workgroup of the launch can be resident at once (k_attend_hs: 2 workgroups
+    // per CU by LDS and registers), so that progress does not depend on dispatch order at all.
+    const long long hs_wgs = ((c.max_rows + HS_BM - 1) / HS_BM + C) * (long long)c.n_bags;
+    auto hs_inline_fits = [&] { return hs_wgs <= 2LL * (c.cus > 0 ? c.cus : device_cus()); };   // (asks the device only when it matters)
+    r.qmax_threads = QMAX_T;
+    if (c.phase == 1) { r.qmax = DSMIL_QMAX_SHARD1; r.qmax_vec = v4 ? 4 : 1; return r; }
+    if (use_hs && sok && c.phase == 0 && !ex.no_qmi && g_inline_query.load(std::memory_order_relaxed) && hs_inline_fits())
+        r.qmax = DSMIL_QMAX_INLINE, r.qmax_threads = 0;
+    else if (c.phase == 2) { r.qmax = DSMIL_QMAX_SHARD2; r.qmax_vec = (K % 4 == 0) && (c.aligned & 4) ? 4 : 1; }
+    else if (bf16) { r.qmax = DSMIL_QMAX_LAUNCH; r.qmax_vec = w4 ? 4 : 1; r.qmax_threads = lpipe ? PIPE_QT : QMAX_T; }
+    else { r.qmax = DSMIL_QMAX_LAUNCH; r.qmax_vec = v4 ? 4 : 1; }
+    // 3. the weight image of the query MLP
+    const int mode = (NW == 8) ? 0 : mlp_mode();
+    if (use_f2) r.image = c.packed_f2 ? DSMIL_IMAGE_F2_CALLER : DSMIL_IMAGE_F2_CUT;
+    else if (!bf16 && mode) r.image = c.packed_split ? DSMIL_IMAGE_SPLIT_CALLER : DSMIL_IMAGE_SPLIT_CUT;
+    else r.image = bf16 ? DSMIL_IMAGE_BF16 : DSMIL_IMAGE_NONE;
+    // 4. query MLP on MFMA + scores + tile softmax + weighted value sum
+    const bool bf16_dma = bf16 && NW == 4 && !(ex.bits & 256);   // feature rows are 16-B aligned on this path (K % 8 == 0)
+    // the tile-resident kernel (agg_res.h) needs the whole K of a tile in LDS and this wave's weight slice in registers:
+    // instantiated for K = 512 and K = 256, values == features, C <= 2
+    const bool bf16_res = bf16_dma && (K == 512 || K == 256) && c.Kv == K && same_vals && C <= 2 && !(ex.bits & 512);
+    const bool use_f3 = use_f2 && c.nonlinear && C <= 2 && batch_form == 2;
+    auto tiled = [&](int kind, int nw, int vec, int np, int xe = 0, int tu = 8) {
+        r.attend = kind; r.attend_nw = nw; r.attend_vec = vec; r.attend_np = np; r.attend_xe = xe; r.attend_tu = tu;
+    };
+    const int vec = v4 ? 4 : 1;
+    if (use_f3) r.attend = DSMIL_ATTEND_F3;
+    else if (use_f2) r.attend = DSMIL_ATTEND_F2;
+    else if (bf16_res) r.attend = DSMIL_ATTEND_BF16_RES;
+    else if (bf16_dma) r.attend = DSMIL_ATTEND_BF16_DMA;
+    else if (bf16) tiled(DSMIL_ATTEND_BF16_RING, NW == 4 ? 4 : 1, 0, 0);
+    // DSMIL_MLP=s9 and the ablation variants: ex is all zero in the product library
+    else if (mode == 9) tiled(DSMIL_ATTEND_SPLIT, NW == 4 ? 4 : 1, vec, 9);
+    else if (mode == 6 && NW == 4 && v4 && (ex.bits & 16)) tiled(DSMIL_ATTEND_SPLIT, 4, 4, 6, 0, 16);
+    else if (mode == 6 && NW == 4 && v4 && (ex.bits & 32)) tiled(DSMIL_ATTEND_SPLIT, 4, 4, 6, 0, 32);
+    else if (mode == 6 && (NW == 4 || NW == 1) && v4 && (ex.bits & 8)) tiled(DSMIL_ATTEND_SPLIT, NW, 4, 6, 1);
+    else if (mode == 6 && NW == 4) tiled(DSMIL_ATTEND_SPLIT, 4, vec, 6);
+    else if (use_hs) r.attend = DSMIL_ATTEND_HS;   // few rows: hidden units split over the SIMDs
+    else if (mode == 6) tiled(DSMIL_ATTEND_SPLIT, 1, vec, 6);
+    else if (NW == 8) tiled(DSMIL_ATTEND_F32, 8, 4, 0);
+    else tiled(DSMIL_ATTEND_F32, NW == 4 ? 4 : 1, vec, 0);
+    // ragged batch on a persistent kernel: the item list is the real tiles (prefix per bag), not max_rows-padded bags
+    r.ragged_attend = r.ragged && (use_f3 || bf16_res);
+    // 5. combine (skipped under the stamp-trace knob, which leaves its stamps in A); the lean form fits beside a resident
+    // attend workgroup and goes with k_logits_pipe
+    if (ex.bits & 64) return r;
+    const int a_bm = r.attend == DSMIL_ATTEND_F3 ? F3_BM : r.attend == DSMIL_ATTEND_F2 ? F2_BM : r.attend == DSMIL_ATTEND_HS ? HS_BM :
+                     r.attend == DSMIL_ATTEND_BF16_RES ? RS_BM : BM;
+    if (c.Kv % 4 == 0 && lpipe && r.attend == DSMIL_ATTEND_BF16_RES) { r.finish = DSMIL_FINISH_LEAN; r.finish_rows = RS_BM; }
+    else if (c.Kv % 4 == 0) { r.finish = DSMIL_FINISH_VEC4; r.finish_rows = a_bm; }
+    else { r.finish = DSMIL_FINISH_SCALAR; r.finish_rows = BM; }
+    r.pred = c.phase == 0 && !c.skip_pred;   // (else the bag head runs after the cross-shard merge / in the caller's next launch)
+    return r;
+}
+
+// ---- the attend launches ---------------------------------------------------------------------
+// LDS opt-in, profiler bracket, launch, error check: the same for every attend kernel
+template <typename Kern, typename... Args>
+int launch_attend_kernel(Kern kern, dim3 grid, int threads, size_t lds, hipStream_t st, const Args&... args) {
+    if (!dsmil_lds::allow((const void*)kern, (int)lds)) return DSMIL_E_LAUNCH;
     const int slot = dsmil_prof::begin(dsmil_prof::CH_ATTEND, st);
-    hipLaunchKernelGGL(k_attend_hs<6>, grid, dim3(HS_THREADS), lds, st, a);
+    hipLaunchKernelGGL(kern, grid, dim3(threads), lds, st, args...);
     dsmil_prof::end(dsmil_prof::CH_ATTEND, slot, st);
     return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 
-// Which MFMA form the fp32 query MLP uses (see agg_split.h).  Default: 6 plane products — the three left
-// out are together below 2^-20 of |x*w|, i.e. below the fp32 accumulation rounding the reference's own
-// 512-long dot products carry (tests/accuracy_report.py: identical measured error for 0 / 9 / 6).
-// Experiment builds (libdsmil_hip_expt.so): DSMIL_MLP = s9 | f32 selects the bit-exact-product forms, read once per
-// process; the product library has the one form.
+// What an attend launch reports: its status and, for the persistent kernels that deal runs of tiles (k_attend_f3,
+// k_attend_bf16_res), the run length and the tiles per bag k_finish needs to find a bag's partials (0, 0 otherwise)
+struct Attended { int rc, per, T; };
+
+// k_attend_f3 / k_attend_bf16_res: contiguous runs of `per` tile items per workgroup — consecutive tiles belong to the same
+// bag and share one partial, so `per` fixes the fp32 summation order.  Ragged batch (a.tile_pre): the items are the real
+// tiles, at most total_rows / bm + n_bags of them (the kernel reads the exact count from tile_pre[n_bags]) and T is the
+// kernel's placeholder ragged_T; uniform: T tiles per bag.
+template <typename Kern, typename... Lead>
+Attended launch_runs(Kern kern, int threads, int lds, int bm, int cap, int ragged_T, const AttendArgs& a, long long max_rows,
+                     long long total_rows, int n_bags, hipStream_t st, const Lead&... lead) {
+    const int cus = persistent_grid(cap);
+    const long long T = a.tile_pre ? ragged_T : (max_rows + bm - 1) / bm;
+    const long long n_items = a.tile_pre ? total_rows / bm + n_bags : T * n_bags;
+    if (n_items > 0x7fffffffLL) return {DSMIL_E_UNSUPPORTED, 0, 0};
+    const long long per = (n_items + cus - 1) / cus;
+    const unsigned grid = (unsigned)((n_items + per - 1) / per);
+    return {launch_attend_kernel(kern, dim3(grid), threads, (size_t)lds, st, a, lead..., (int)T, (int)n_items, (int)per), (int)per, (int)T};
+}
+
+// batches of fp32 bags, two-layer query, C <= 2: 32-row tiles, the query weights resident in registers (agg_f3.h)
+Attended launch_f3(const AttendArgs& a, const float* rowmax, long long max_rows, long long total_rows, int n_bags, hipStream_t st) {
+    void (*fn)(AttendArgs, const float*, int, int, int) = nullptr;
+    const bool two = a.C == 2;
+    switch (a.K / 32) {
+        case 4: fn = two ? k_attend_f3<4, true> : k_attend_f3<4, false>; break;
+        case 8: fn = two ? k_attend_f3<8, true> : k_attend_f3<8, false>; break;
+        case 12: fn = two ? k_attend_f3<12, true> : k_attend_f3<12, false>; break;
+        case 16: fn = two ? k_attend_f3<16, true> : k_attend_f3<16, false>; break;
+        default: return {DSMIL_E_UNSUPPORTED, 0, 0};
+    }
+#ifdef DSMIL_EXPERIMENTS
+#define F3_DBG(n) case n: fn = k_attend_f3<16, false, n>; break;
+    if (a.K == 512 && a.C == 1) switch (expt().f3_dbg) { F3_DBG(1) F3_DBG(2) F3_DBG(3) F3_DBG(4) F3_DBG(5) default: break; }
+#undef F3_DBG
+#endif
+    return launch_runs(fn, F3_THREADS, f3_lds_bytes(a.K), F3_BM, F3_MAX_WG, 0, a, max_rows, total_rows, n_bags, st, rowmax);
+}
+
 // batches of fp32 bags: resident 64-row tiles, fp16 two-plane MFMA (agg_f2.h)
-int launch_attend_f2(const AttendArgs& a, const float* rowmax, long long max_rows, int n_bags, hipStream_t st) {
+int launch_f2(const AttendArgs& a, const float* rowmax, long long max_rows, int n_bags, hipStream_t st) {
     void (*fn)(AttendArgs, const float*, int, int) = nullptr;
     switch (a.K / 32) {
         case 4: fn = k_attend_f2<4>; break;
@@ -1533,153 +1665,87 @@ int launch_attend_f2(const AttendArgs& a, const float* rowmax, long long max_row
         default: return DSMIL_E_UNSUPPORTED;
     }
 #ifdef DSMIL_EXPERIMENTS   // timing-only ablations of the K = 512 form (tools/f2_ablate.py)
-    static const int abl = expt_env("DSMIL_F2_ABL");
-    switch (a.K == 512 ? abl : 0) {
-        case 1: fn = k_attend_f2<16, 1>; break;
-        case 2: fn = k_attend_f2<16, 2>; break;
-        case 3: fn = k_attend_f2<16, 3>; break;
-        case 4: fn = k_attend_f2<16, 4>; break;
-        case 7: fn = k_attend_f2<16, 7>; break;
-        case 8: fn = k_attend_f2<16, 8>; break;
-        case 16: fn = k_attend_f2<16, 16>; break;
-        case 31: fn = k_attend_f2<16, 31>; break;
-        case 32: fn = k_attend_f2<16, 32>; break;
-        case 64: fn = k_attend_f2<16, 64>; break;
-        case 128: fn = k_attend_f2<16, 128>; break;
-        case 192: fn = k_attend_f2<16, 192>; break;
-        case 256: fn = k_attend_f2<16, 256>; break;
+#define F2_ABL(n) case n: fn = k_attend_f2<16, n>; break;
+    switch (a.K == 512 ? expt().f2_abl : 0) {
+        F2_ABL(1) F2_ABL(2) F2_ABL(3) F2_ABL(4) F2_ABL(7) F2_ABL(8) F2_ABL(16) F2_ABL(31) F2_ABL(32) F2_ABL(64) F2_ABL(128) F2_ABL(192) F2_ABL(256)
         default: break;
     }
+#undef F2_ABL
 #endif
-    if (!dsmil_lds::allow((const void*)fn, F2_LDS_BYTES)) return DSMIL_E_LAUNCH;
     const int tiles_per_bag = (int)((max_rows + F2_BM - 1) / F2_BM);
     const long long n_items = (long long)tiles_per_bag * n_bags;
     if (n_items > 0x7fffffffLL) return DSMIL_E_UNSUPPORTED;
-    int cus = persistent_grid(1 << 20);
-#ifdef DSMIL_EXPERIMENTS
-    static const int f2_grid = expt_env("DSMIL_F2_GRID");
-    if (f2_grid > 0) cus = f2_grid;
-#endif
+    const int cus = expt().f2_grid > 0 ? expt().f2_grid : persistent_grid(1 << 20);
     const long long grid = n_items < cus ? n_items : cus;   // persistent: one workgroup per CU (148 KiB of LDS each)
-    const int slot = dsmil_prof::begin(dsmil_prof::CH_ATTEND, st);
-    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(F2_THREADS), F2_LDS_BYTES, st, a, rowmax, tiles_per_bag, (int)n_items);
-    dsmil_prof::end(dsmil_prof::CH_ATTEND, slot, st);
-    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
+    return launch_attend_kernel(fn, dim3((unsigned)grid), F2_THREADS, F2_LDS_BYTES, st, a, rowmax, tiles_per_bag, (int)n_items);
 }
 
-// batches of fp32 bags, two-layer query, C <= 2: 32-row tiles, the query weights resident in registers (agg_f3.h)
-template <int NK1>
-int launch_attend_f3_k(const AttendArgs& a, const float* rowmax, long long max_rows, long long total_rows, int n_bags, hipStream_t st, int* seg_per, int* seg_T) {
-    void (*fn)(AttendArgs, const float*, int, int, int) = a.C == 2 ? k_attend_f3<NK1, true> : k_attend_f3<NK1, false>;
-#ifdef DSMIL_EXPERIMENTS
-    static const int f3_dbg = expt_env("DSMIL_F3_DBG");
-    if (NK1 == 16 && a.C == 1 && f3_dbg == 1) fn = k_attend_f3<16, false, 1>;
-    if (NK1 == 16 && a.C == 1 && f3_dbg == 2) fn = k_attend_f3<16, false, 2>;
-    if (NK1 == 16 && a.C == 1 && f3_dbg == 3) fn = k_attend_f3<16, false, 3>;
-    if (NK1 == 16 && a.C == 1 && f3_dbg == 4) fn = k_attend_f3<16, false, 4>;
-    if (NK1 == 16 && a.C == 1 && f3_dbg == 5) fn = k_attend_f3<16, false, 5>;
-#endif
-    constexpr int lds = f3_lds_bytes(32 * NK1);
-    if (!dsmil_lds::allow((const void*)fn, lds)) return DSMIL_E_LAUNCH;
-    const int cus = persistent_grid(F3_MAX_WG);
-    // ragged batch (a.tile_pre): the items are the real tiles — at most total_rows / 32 + n_bags of them (the kernel reads the
-    // exact count from tile_pre[n_bags]); uniform: tiles_per_bag items per bag
-    const long long tiles_per_bag = a.tile_pre ? 0 : (max_rows + F3_BM - 1) / F3_BM;
-    const long long n_items = a.tile_pre ? total_rows / F3_BM + n_bags : tiles_per_bag * n_bags;
-    if (n_items > 0x7fffffffLL) return DSMIL_E_UNSUPPORTED;
-    const long long per = (n_items + cus - 1) / cus;   // contiguous runs of tile items per workgroup (k_attend_bf16_res's scheme)
-    const unsigned grid = (unsigned)((n_items + per - 1) / per);
-    *seg_per = (int)per;
-    *seg_T = (int)tiles_per_bag;
-    const int slot = dsmil_prof::begin(dsmil_prof::CH_ATTEND, st);
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(F3_THREADS), lds, st, a, rowmax, (int)tiles_per_bag, (int)n_items, (int)per);
-    dsmil_prof::end(dsmil_prof::CH_ATTEND, slot, st);
-    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
-}
-int launch_attend_f3(const AttendArgs& a, const float* rowmax, long long max_rows, long long total_rows, int n_bags, hipStream_t st, int* seg_per, int* seg_T) {
-    switch (a.K / 32) {
-        case 4: return launch_attend_f3_k<4>(a, rowmax, max_rows, total_rows, n_bags, st, seg_per, seg_T);
-        case 8: return launch_attend_f3_k<8>(a, rowmax, max_rows, total_rows, n_bags, st, seg_per, seg_T);
-        case 12: return launch_attend_f3_k<12>(a, rowmax, max_rows, total_rows, n_bags, st, seg_per, seg_T);
-        case 16: return launch_attend_f3_k<16>(a, rowmax, max_rows, total_rows, n_bags, st, seg_per, seg_T);
-        default: return DSMIL_E_UNSUPPORTED;
-    }
-}
-
-int mlp_mode() {
-#ifdef DSMIL_EXPERIMENTS
-    static const int mode = [] {
-        const char* e = getenv("DSMIL_MLP");
-        if (!e) return 6;
-        if (!strcmp(e, "f32")) return 0;
-        if (!strcmp(e, "s9")) return 9;
-        return 6;
-    }();
-    return mode;
-#else
-    return 6;
-#endif
-}
-
-int launch_attend_bf16_dma(AttendArgs a, long long max_rows, int n_bags, hipStream_t st) {
-    constexpr int NW = 4, BM = NW * 32;
-    const size_t lds = (size_t)(2 * BD_WCHUNK_F4 + 3 * BM * 8) * 16;   // 32 KiB weights + 48 KiB features = 80 KiB: 2 per CU
-    if (!dsmil_lds::allow((const void*)k_query_attend_bf16_dma<NW>, (int)lds)) return DSMIL_E_LAUNCH;
-    const int K64 = (a.K + 63) / 64 * 64;
-    a.wpk = a.wpk + (size_t)QD * K64 + QD * QD;   // the fragment image sits behind the row-major one
-    dim3 grid((unsigned)((max_rows + BM - 1) / BM), (unsigned)n_bags);
-    const int slot = dsmil_prof::begin(dsmil_prof::CH_ATTEND, st);
-    hipLaunchKernelGGL((k_query_attend_bf16_dma<NW>), grid, dim3(NW * 64), lds, st, a);
-    dsmil_prof::end(dsmil_prof::CH_ATTEND, slot, st);
-    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
-}
-
-// The tile-resident kernel (agg_res.h): persistent, one 320-thread workgroup per CU.  Needs the whole K of a
-// 128-row tile in LDS and this wave's weight slice in registers: instantiated for K = 512 and K = 256, values == features,
-// C <= 2; everything else keeps the ring kernels.
-bool bf16_res_ok(const AttendArgs& a) {
-    return (a.K == 512 || a.K == 256) && a.Kv == a.K && a.vals == a.feats && a.C <= 2;
-}
-template <int NCH>
-void (*bf16_res_fn(const AttendArgs& a))(AttendArgs, int, int, int) {
-    return a.C == 2 ? (a.nonlinear ? k_attend_bf16_res<NCH, true, true> : k_attend_bf16_res<NCH, true, false>)
-                    : (a.nonlinear ? k_attend_bf16_res<NCH, false, true> : k_attend_bf16_res<NCH, false, false>);
-}
-int launch_attend_bf16_res(AttendArgs a, long long max_rows, long long total_rows, int n_bags, hipStream_t st, int* seg_per, int* seg_T) {
-    const int cus = persistent_grid(RS_MAX_WG);
-    typedef void (*res_fn)(AttendArgs, int, int, int);
-    res_fn fn = a.K == 512 ? bf16_res_fn<8>(a) : bf16_res_fn<4>(a);
+// bf16 batches: the tile-resident kernel (agg_res.h), persistent, one 320-thread workgroup per CU
+Attended launch_bf16_res(const AttendArgs& a, long long max_rows, long long total_rows, int n_bags, hipStream_t st) {
+    void (*fn)(AttendArgs, int, int, int);
+#define RES_FN(nch) (a.C == 2 ? (a.nonlinear ? k_attend_bf16_res<nch, true, true> : k_attend_bf16_res<nch, true, false>) \
+                              : (a.nonlinear ? k_attend_bf16_res<nch, false, true> : k_attend_bf16_res<nch, false, false>))
+    fn = a.K == 512 ? RES_FN(8) : RES_FN(4);
+#undef RES_FN
 #ifdef DSMIL_EXPERIMENTS
     if (a.K == 512 && a.C == 2 && a.nonlinear && (a.expt & 1024)) fn = k_attend_bf16_res<8, true, true, 1>;
     if (a.K == 512 && a.C == 2 && a.nonlinear && (a.expt & 2048)) fn = k_attend_bf16_res<8, true, true, 2>;
 #endif
-    if (!dsmil_lds::allow((const void*)fn, RS_LDS_BYTES)) return DSMIL_E_LAUNCH;
-    const int K64 = (a.K + 63) / 64 * 64;
-    a.wpk = a.wpk + (size_t)QD * K64 + QD * QD;   // the fragment image sits behind the row-major one
-    const long long tiles_per_bag = a.tile_pre ? 1 : (max_rows + RS_BM - 1) / RS_BM;   // (ragged: unused by the kernel)
-    const long long n_items = a.tile_pre ? total_rows / RS_BM + n_bags : tiles_per_bag * n_bags;
-    if (n_items > 0x7fffffffLL) return DSMIL_E_UNSUPPORTED;
-    // contiguous runs of tile items per workgroup: consecutive tiles belong to the same bag and share one partial
-    const long long per = (n_items + cus - 1) / cus;
-    const unsigned grid = (unsigned)((n_items + per - 1) / per);
-    *seg_per = (int)per;
-    *seg_T = (int)tiles_per_bag;
-    const int slot = dsmil_prof::begin(dsmil_prof::CH_ATTEND, st);
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(RS_THREADS), RS_LDS_BYTES, st, a, (int)tiles_per_bag, (int)n_items, (int)per);
-    dsmil_prof::end(dsmil_prof::CH_ATTEND, slot, st);
-    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
+    return launch_runs(fn, RS_THREADS, RS_LDS_BYTES, RS_BM, RS_MAX_WG, 1, a, max_rows, total_rows, n_bags, st);
 }
 
-template <int NW>
-int launch_attend_bf16(const AttendArgs& a, long long max_rows, int n_bags, hipStream_t st) {
+// the tiled kernels: one workgroup of nw waves per nw * 32 rows of a bag, grid (tiles of the longest bag) x bags
+template <int NW, int VEC, int NP, bool XE = false, int TU = 8>
+int launch_split(const AttendArgs& a, dim3 grid, hipStream_t st) {
     constexpr int BM = NW * 32;
-    const size_t lds = (size_t)(2 * W_TILE + 2 * BM * LDK) * sizeof(float);
-    if (!dsmil_lds::allow((const void*)k_query_attend_bf16<NW>, (int)lds)) return DSMIL_E_LAUNCH;
-    dim3 grid((unsigned)((max_rows + BM - 1) / BM), (unsigned)n_bags);
-    const int slot = dsmil_prof::begin(dsmil_prof::CH_ATTEND, st);
-    hipLaunchKernelGGL((k_query_attend_bf16<NW>), grid, dim3(NW * 64), lds, st, a);
-    dsmil_prof::end(dsmil_prof::CH_ATTEND, slot, st);
-    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
+    const size_t lds = (VEC == 4 ? (size_t)(3 * S3_CHUNK_F4 * 4 + 2 * BM * 32) * sizeof(float)
+                                 : (size_t)(2 * S3_CHUNK_F4 * 4 + 2 * BM * LDK) * sizeof(float)) + (size_t)expt().lds_pad;
+    return launch_attend_kernel(k_query_attend_split<NW, VEC, NP, XE, TU>, grid, NW * 64, lds, st, a);
+}
+
+Attended launch_attend(const Route& r, AttendArgs a, const float* rowmax, long long max_rows, long long total_rows, int n_bags,
+                       hipStream_t st) {
+    const int BM = r.attend_nw * 32, threads = r.attend_nw * 64;
+    const dim3 grid((unsigned)((max_rows + BM - 1) / (BM ? BM : 1)), (unsigned)n_bags);
+    const size_t lds_ring = (size_t)(2 * W_TILE + 2 * BM * LDK) * sizeof(float);
+    const bool n4 = r.attend_nw == 4, vec4 = r.attend_vec == 4;
+    auto plain = [](int rc) { return Attended{rc, 0, 0}; };
+    switch (r.attend) {
+        case DSMIL_ATTEND_F3: return launch_f3(a, rowmax, max_rows, total_rows, n_bags, st);
+        case DSMIL_ATTEND_F2: return plain(launch_f2(a, rowmax, max_rows, n_bags, st));
+        case DSMIL_ATTEND_BF16_RES:
+        case DSMIL_ATTEND_BF16_DMA:
+            a.wpk = a.wpk + (size_t)QD * ((a.K + 63) / 64 * 64) + QD * QD;   // the fragment image sits behind the row-major one
+            if (r.attend == DSMIL_ATTEND_BF16_RES) return launch_bf16_res(a, max_rows, total_rows, n_bags, st);
+            // 32 KiB weights + 48 KiB features = 80 KiB: 2 per CU
+            return plain(launch_attend_kernel(k_query_attend_bf16_dma<4>, dim3((unsigned)((max_rows + 127) / 128), (unsigned)n_bags), 256,
+                                              (size_t)(2 * BD_WCHUNK_F4 + 3 * 128 * 8) * 16, st, a));
+        case DSMIL_ATTEND_BF16_RING:
+            return plain(n4 ? launch_attend_kernel(k_query_attend_bf16<4>, grid, threads, lds_ring, st, a)
+                            : launch_attend_kernel(k_query_attend_bf16<1>, grid, threads, lds_ring, st, a));
+        case DSMIL_ATTEND_SPLIT:
+#ifdef DSMIL_EXPERIMENTS   // DSMIL_MLP=s9 and the ablation variants: not instantiated in the product library
+            if (r.attend_np == 9) return plain(n4 ? (vec4 ? launch_split<4, 4, 9>(a, grid, st) : launch_split<4, 1, 9>(a, grid, st))
+                                                  : (vec4 ? launch_split<1, 4, 9>(a, grid, st) : launch_split<1, 1, 9>(a, grid, st)));
+            if (r.attend_tu == 16) return plain(launch_split<4, 4, 6, false, 16>(a, grid, st));
+            if (r.attend_tu == 32) return plain(launch_split<4, 4, 6, false, 32>(a, grid, st));
+            if (r.attend_xe) return plain(n4 ? launch_split<4, 4, 6, true>(a, grid, st) : launch_split<1, 4, 6, true>(a, grid, st));
+#endif
+            return plain(n4 ? (vec4 ? launch_split<4, 4, 6>(a, grid, st) : launch_split<4, 1, 6>(a, grid, st))
+                            : (vec4 ? launch_split<1, 4, 6>(a, grid, st) : launch_split<1, 1, 6>(a, grid, st)));
+        case DSMIL_ATTEND_HS:   // (the first C workgroups of a grid row produce the critical query when it runs in this launch)
+            return plain(launch_attend_kernel(k_attend_hs<6>, dim3((unsigned)((max_rows + HS_BM - 1) / HS_BM + (a.qm_flag ? a.C : 0)), (unsigned)n_bags),
+                                              HS_THREADS, (size_t)HS_LDS_BYTES + (size_t)expt().lds_pad, st, a));
+        case DSMIL_ATTEND_F32:
+#ifdef DSMIL_EXPERIMENTS   // DSMIL_NW=8
+            if (r.attend_nw == 8) return plain(launch_attend_kernel(k_query_attend<8, 4>, grid, threads, lds_ring, st, a));
+#endif
+            return plain(n4 ? (vec4 ? launch_attend_kernel(k_query_attend<4, 4>, grid, threads, lds_ring, st, a)
+                                    : launch_attend_kernel(k_query_attend<4, 1>, grid, threads, lds_ring, st, a))
+                            : (vec4 ? launch_attend_kernel(k_query_attend<1, 4>, grid, threads, lds_ring, st, a)
+                                    : launch_attend_kernel(k_query_attend<1, 1>, grid, threads, lds_ring, st, a)));
+        default: return plain(DSMIL_E_INVALID);
+    }
 }
 
 }  // namespace
@@ -1692,17 +1758,16 @@ int dsmil_fc_forward_rows(const float* feats, int64_t total_rows, int32_t K, int
     long long blocks = (total_rows + 3) / 4;
     if (blocks > 4096) blocks = 4096;
     const bool v4 = (K % 4 == 0) && (((uintptr_t)feats | (uintptr_t)fc_w) % 16 == 0);
-    if (v4) hipLaunchKernelGGL(k_fc<4>, dim3((unsigned)blocks), dim3(256), 0, st, feats, fc_w, fc_b, classes, (long long)total_rows, K, C, rowmap);
-    else hipLaunchKernelGGL(k_fc<1>, dim3((unsigned)blocks), dim3(256), 0, st, feats, fc_w, fc_b, classes, (long long)total_rows, K, C, rowmap);
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, st, feats, fc_w, fc_b, classes, (long long)total_rows, K, C, rowmap); };
+    if (v4) go(k_fc<4>); else go(k_fc<1>);
     return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 
 void dsmil_agg_forward_leftovers(void* ws, int32_t n_bags, int64_t total_rows, int32_t K, int32_t Kv, int32_t C,
-                                 const void** packed_split, const float** qmax, const float** pred_part, int* pred_blocks) {
-    const WsLayout L = ws_layout(n_bags, total_rows, total_rows, K, Kv, C, pick_nw(n_bags, total_rows) * 32);
+                                 const float** qmax, const float** pred_part, int* pred_blocks) {
+    const WsLayout L = ws_layout(n_bags, total_rows, total_rows, K, Kv, C);   // (max_rows <= total_rows bounds the chunk count)
     if (pred_part) *pred_part = (const float*)((char*)ws + L.pred_part);
     if (pred_blocks) *pred_blocks = (int)L.nchunk_max;
-    if (packed_split) *packed_split = (pick_nw(n_bags, total_rows) != 8 && mlp_mode()) ? (const void*)((char*)ws + L.wsplit) : nullptr;
     if (qmax) *qmax = (const float*)((char*)ws + L.qmax);
 }
 
@@ -1743,26 +1808,23 @@ const char* dsmil_strerror(int code) {
 
 int dsmil_agg_tile_rows(int32_t n_bags, int64_t total_rows) { return pick_nw(n_bags, total_rows) * 32; }
 
+int dsmil_agg_forward_route(const dsmil_agg_call* call, dsmil_agg_route* route) {
+    if (!call || !route) return DSMIL_E_INVALID;
+    if (call->n_bags <= 0 || call->total_rows <= 0 || call->max_rows <= 0 || call->max_rows > call->total_rows) return DSMIL_E_INVALID;
+    if (call->K <= 0 || call->Kv <= 0 || call->C <= 0) return DSMIL_E_INVALID;
+    *route = pick_route(*call);
+    return DSMIL_OK;
+}
+
 size_t dsmil_agg_workspace_bytes(int32_t n_bags, int64_t total_rows, int32_t K, int32_t Kv,
                                  int32_t C) {
-    (void)K;
     if (n_bags <= 0 || total_rows <= 0 || Kv <= 0 || C <= 0) return 0;
-    // max_rows <= total_rows bounds the chunk count; tile rows as the launcher will pick them
-    return ws_layout(n_bags, total_rows, total_rows, K, Kv, C, pick_nw(n_bags, total_rows) * 32).total;
+    return ws_layout(n_bags, total_rows, total_rows, K, Kv, C).total;   // max_rows <= total_rows bounds the chunk count
 }
 
 int dsmil_fc_forward(const float* feats, int64_t total_rows, int32_t K, int32_t C,
                      const float* fc_w, const float* fc_b, float* classes, void* stream) {
     return dsmil_fc_forward_rows(feats, total_rows, K, C, fc_w, fc_b, classes, nullptr, stream);
-}
-
-__global__ void k_set_offsets2(int64_t* off, long long N) { off[0] = 0; off[1] = N; }
-
-// 16-B vector loads on every fp32 operand of the forward
-static bool fwd_v4(const void* feats, const void* vals, const dsmil_agg_params* p) {
-    return (p->K % 4 == 0) && (p->Kv % 4 == 0) &&
-           (((uintptr_t)feats | (uintptr_t)vals | (uintptr_t)p->q0_w | (uintptr_t)p->fc_w |
-             (uintptr_t)(p->nonlinear ? p->q2_w : p->q0_w)) % 16 == 0);
 }
 
 struct ShardCtl {
@@ -1774,6 +1836,21 @@ struct ShardCtl {
     const TrainPrologueJob* job = nullptr;   // carried by the logits launch (dsmil_agg_forward_nopred)
     const void* packed_f2 = nullptr;         // dsmil_agg_opts::packed_f2 (k_attend_f2's weight image, prepared by the caller)
 };
+
+// a forward call as the route function sees it (several_streams and cus are left 0: see agg_forward_impl / pick_route)
+static Call describe_call(const void* feats, const void* vals, int32_t n_bags, int64_t total_rows, int64_t max_rows,
+                          const dsmil_agg_params* p, bool bf16, bool classes_given, const ShardCtl& sh, const void* packed_split,
+                          const int64_t* rowmap) {
+    Call c{};
+    c.total_rows = total_rows; c.max_rows = max_rows; c.n_bags = n_bags;
+    c.K = p->K; c.Kv = p->Kv; c.C = p->C; c.nonlinear = p->nonlinear;
+    c.bf16 = bf16;
+    c.aligned = aligned_bits(feats, vals, p, sh.crit_rows);
+    c.classes_given = classes_given; c.vals_separate = vals != feats; c.row_map = rowmap != nullptr;
+    c.packed_split = packed_split != nullptr; c.packed_f2 = sh.packed_f2 != nullptr;
+    c.phase = sh.phase; c.skip_pred = sh.skip_pred; c.prologue_job = sh.job != nullptr;
+    return c;
+}
 
 static int agg_forward_impl(const void* feats, const void* vals, const int64_t* offsets,
                             int32_t n_bags, int64_t total_rows, int64_t max_rows, const dsmil_agg_params* p,
@@ -1800,15 +1877,13 @@ static int agg_forward_impl(const void* feats, const void* vals, const int64_t* 
     if (bf16 && ((K % 8) || (Kv % 4) || ((uintptr_t)feats % 16) || ((uintptr_t)vals % 8) ||
                  ((uintptr_t)packed_bf16 % 16)))
         return DSMIL_E_UNSUPPORTED;
-    const int NW = pick_nw(n_bags, total_rows);
-    const int BM = NW * 32;
-    const WsLayout L = ws_layout(n_bags, total_rows, max_rows, K, Kv, C, BM);
+    const WsLayout L = ws_layout(n_bags, total_rows, max_rows, K, Kv, C);
     if (ws_bytes < L.total) return DSMIL_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     char* w8 = (char*)ws;
     if (sh.phase) {  // a lone shard: its {0, N} offsets live in the workspace
         int64_t* off2 = (int64_t*)(w8 + L.off2);
-        hipLaunchKernelGGL(k_set_offsets2, dim3(1), dim3(1), 0, st, off2, (long long)total_rows);
+        hipLaunchKernelGGL(k_set_offsets, dim3(1), dim3(1), 0, st, off2, (long long)total_rows);
         if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
         offsets = off2;
     }
@@ -1821,183 +1896,107 @@ static int agg_forward_impl(const void* feats, const void* vals, const int64_t* 
     const float* f32 = (const float*)feats;
     const bf16_t* b16 = (const bf16_t*)feats;
 
-    const bool v4 = bf16 || fwd_v4(feats, vals, p);
-    const bool w4 = (K % 4 == 0) && (((uintptr_t)p->q0_w | (uintptr_t)p->fc_w) % 16 == 0);
+    Call call = describe_call(feats, vals, n_bags, total_rows, max_rows, p, bf16, classes_in != nullptr, sh, packed_split, rowmap);
+    if (pipe_shape(call)) call.several_streams = several_streams_recently(st);   // (recorded whatever dsmil_agg_logits_form says)
+    const Route r = pick_route(call);
     AttendArgs a{feats, vals, (const bf16_t*)packed_bf16, offsets, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, A,
-                 part_ml, part_B, K, Kv, C, p->nonlinear, 0, 0, rowmap};
-#ifdef DSMIL_EXPERIMENTS
-    static const int expt = expt_env("DSMIL_EXPT"), logits_old = expt_env("DSMIL_LOGITS_OLD"), no_hs = expt_env("DSMIL_NO_HS"),
-                     no_qmi = expt_env("DSMIL_NO_QMI"), no_f2 = expt_env("DSMIL_NO_F2");
-    a.expt = expt;
-#else
-    constexpr int logits_old = 0, no_hs = 0, no_qmi = 0, no_f2 = 0;
-#endif
-    int seg_per = 0, seg_T = 0;   // k_attend_bf16_res: partials per (workgroup, bag), see k_finish
-    bool lean_tail = false;       // the bf16 batch path whose logits / q_max / combine kernels fit beside a resident attend workgroup
-    int hs_bm = 0;                // k_attend_hs: rows per tile (the partial slots follow it)
+                 part_ml, part_B, K, Kv, C, p->nonlinear, expt().bits, 0, rowmap};
+    // Tried and rejected here (round 1, numbers in DESIGN.md §3): (a) chunking the batch and running chunk c+1's HBM-bound logits
+    // on a helper stream under chunk c's MFMA-bound attend, and (b) one persistent launch pulling logits/attend work items from a
+    // device queue with in-launch release/acquire hand-offs.  Both were slower than these plain back-to-back launches.
+    float* rowmax = r.rowmax ? (float*)(w8 + L.rowmax) : nullptr;
+    int* qflag = r.qmax == DSMIL_QMAX_INLINE ? (int*)(w8 + L.qflag) : nullptr;
+    int *tile_pre_a = nullptr, *tile_pre_l = nullptr;
+    if (r.ragged) {
+        tile_pre_a = (int*)(w8 + L.tile_pre);
+        tile_pre_l = tile_pre_a + (n_bags + 1);
+        hipLaunchKernelGGL(k_tile_prefix, dim3(1), dim3(1024), 0, st, offsets, n_bags, r.tile_attend, r.tile_logits, tile_pre_a, tile_pre_l);
+        if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    }
+    // 1. instance logits + arg-max partials
     {
-        // Tried and rejected here (round 1, numbers in DESIGN.md §3): (a) chunking the batch and running
-        // chunk c+1's HBM-bound logits on a helper stream under chunk c's MFMA-bound attend, and (b) one
-        // persistent launch pulling logits/attend work items from a device queue with in-launch
-        // release/acquire hand-offs.  Both were slower than these plain back-to-back launches.
-        const int b0 = 0, nb = n_bags;
-        // 1. instance logits + arg-max partials
-        // rows per workgroup of the logits pass: 32 instead of R0 when there are few rows (the 32-row-tile regime of pick_nw)
-        // and the streaming kernel runs
-        const bool stream_ok = !classes_in && !logits_old && ((bf16 && (K % 8 == 0)) || (!bf16 && v4));
-        // bf16 batches of K = 512 rows: the continuous-pipeline logits kernel that fits beside a resident k_attend_bf16_res
-        // workgroup of another stream (k_logits_pipe); its workgroups take more rows (they are dispatched one at a time into
-        // the one free slot of a CU) and its k_qmax launch is 4 waves wide so that it fits the same slot
-        const bool lpipe = bf16 && stream_ok && !logits_old && K == 512 && C <= 2 && NW == 4 && sh.phase == 0 &&
-                           !rowmap && max_rows < 0x7fffffffLL && coresident_wanted(st);
-        const int r0 = lpipe ? PIPE_R0 : (NW == 1 && stream_ok && sh.phase != 2) ? 32 : R0;
-        const int qmax_t = lpipe ? PIPE_QT : QMAX_T;
-        lean_tail = lpipe;
-        // few rows, fp32: k_attend_hs (below); with the streaming logits kernel before it, the critical row's query runs
-        // inside the attend launch (AttendArgs::qm_flag) instead of as k_qmax between the two
-        bool use_hs = !bf16 && NW == 1 && v4 && !no_hs && mlp_mode() == 6;
-#ifdef DSMIL_EXPERIMENTS
-        if (a.expt & 8) use_hs = false;
-#endif
-        // batches (128-row regime), fp32, v = Identity, K a multiple of 128 up to 512: resident 64-row tiles on the fp16 two-plane
-        // form (agg_f2.h); it needs the row maxima the streaming logits kernel leaves behind
-        const bool use_f2 = !bf16 && NW == 4 && v4 && !no_f2 && mlp_mode() == 6 && stream_ok && sh.phase == 0 && vals == feats &&
-                            (K % 128 == 0) && K <= 16 * F2_MAXSTEPS && g_use_f2.load(std::memory_order_relaxed);
-        float* rowmax = use_f2 ? (float*)(w8 + L.rowmax) : nullptr;
-        const bool qm_inline = use_hs && stream_ok && sh.phase == 0 && !no_qmi && g_inline_query.load(std::memory_order_relaxed) &&
-                               hs_inline_fits(max_rows, nb, C);
-        int* qflag = qm_inline ? (int*)(w8 + L.qflag) : nullptr;
-        dim3 grid((unsigned)((max_rows + r0 - 1) / r0), (unsigned)nb);
-        // RAGGED batch in the 128-row regime (the persistent attend kernels and the streaming logits pass): the work lists are the
-        // real tiles (prefix per bag: k_tile_prefix), not n_bags x the tiles of the longest bag
-        int* tile_pre_a = nullptr;
-        int* tile_pre_l = nullptr;
-        if (NW == 4 && stream_ok && sh.phase == 0 && (long long)max_rows * nb != (long long)total_rows &&
-            total_rows / 32 + nb < 0x7fffffffLL) {
-            tile_pre_a = (int*)(w8 + L.tile_pre);
-            tile_pre_l = tile_pre_a + (nb + 1);
-            hipLaunchKernelGGL(k_tile_prefix, dim3(1), dim3(1024), 0, st, offsets, nb, bf16 ? RS_BM : F3_BM, r0, tile_pre_a, tile_pre_l);
-            if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+        const dim3 grid = r.ragged ? dim3((unsigned)(total_rows / r.r0 + n_bags), 1u)   // (an upper bound of the real tiles)
+                                   : dim3((unsigned)((max_rows + r.r0 - 1) / r.r0), (unsigned)n_bags);
+        auto argmax = [&](auto kern, auto* x) {
+            hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, x, offsets, p->fc_w, p->fc_b, classes_in, classes_out, part_val, part_idx, K, C, 0, rowmap);
+        };
+        auto pipe = [&](auto kern) {
+            hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, b16, offsets, p->fc_w, p->fc_b, classes_out, part_val, part_idx, 0, r.r0, tile_pre_l, n_bags);
+        };
+        auto strm = [&](auto kern, auto* x, int kstep) {   // LDS: the FCLayer rows, padded per kstep (32 fp32 / 64 bf16 elements)
+            const size_t ldsw = (size_t)r.logits_cp * (((K + kstep - 1) / kstep + 1) * kstep) * sizeof(float);
+            const TrainPrologueJob job = r.prologue ? *sh.job : TrainPrologueJob{};
+            const dim3 gridj(grid.x + (unsigned)job.blocks, grid.y);   // (a training step is one bag: never the flat grid)
+            hipLaunchKernelGGL(kern, gridj, dim3(256), ldsw, st, x, offsets, p->fc_w, p->fc_b, classes_out, part_val, part_idx, K, C, 0, rowmap, r.r0, qflag, job, rowmax, tile_pre_l, n_bags);
+        };
+        const bool two = r.logits_cp == 2, vec4 = r.logits_vec == 4;
+        switch (r.logits) {
+            case DSMIL_LOGITS_GIVEN: argmax(k_logits_argmax<1, true, float>, f32); break;
+            case DSMIL_LOGITS_PIPE: if (two) pipe(k_logits_pipe<2>); else pipe(k_logits_pipe<1>); break;
+            case DSMIL_LOGITS_STREAM:
+                if (bf16) { if (two) strm(k_logits_stream<2, bf16_t>, b16, 64); else strm(k_logits_stream<1, bf16_t>, b16, 64); }
+                else { if (two) strm(k_logits_stream<2, float>, f32, 32); else strm(k_logits_stream<1, float>, f32, 32); }
+                break;
+            case DSMIL_LOGITS_ARGMAX:
+                if (bf16) { if (vec4) argmax(k_logits_argmax<4, false, bf16_t>, b16); else argmax(k_logits_argmax<1, false, bf16_t>, b16); }
+                else { if (vec4) argmax(k_logits_argmax<4, false, float>, f32); else argmax(k_logits_argmax<1, false, float>, f32); }
+                break;
+            default: break;
         }
-        const dim3 grid_l = tile_pre_l ? dim3((unsigned)(total_rows / r0 + nb), 1u) : grid;   // (an upper bound of the real tiles)
-        if (sh.phase == 2) {}  // the caller already knows the bag-wide critical rows
-        else if (classes_in) hipLaunchKernelGGL((k_logits_argmax<1, true, float>), grid, dim3(256), 0, st, f32, offsets, p->fc_w, p->fc_b, classes_in, classes_out, part_val, part_idx, K, C, b0, rowmap);
-        else if (bf16 && (K % 8 == 0) && !logits_old) {
-            const size_t ldsw = (size_t)(C >= 2 ? 2 : 1) * (((K + 63) / 64 + 1) * 64) * sizeof(float);
-            // batches of K = 512 rows: the continuous-pipeline form that fits beside a resident k_attend_bf16_res workgroup
-            if (lpipe) {
-                if (C == 2) hipLaunchKernelGGL(k_logits_pipe<2>, grid_l, dim3(256), 0, st, b16, offsets, p->fc_w, p->fc_b, classes_out, part_val, part_idx, b0, r0, tile_pre_l, nb);
-                else hipLaunchKernelGGL(k_logits_pipe<1>, grid_l, dim3(256), 0, st, b16, offsets, p->fc_w, p->fc_b, classes_out, part_val, part_idx, b0, r0, tile_pre_l, nb);
-            }
-            else if (C >= 2) hipLaunchKernelGGL((k_logits_stream<2, bf16_t>), grid_l, dim3(256), ldsw, st, b16, offsets, p->fc_w, p->fc_b, classes_out, part_val, part_idx, K, C, b0, rowmap, r0, (int*)nullptr, TrainPrologueJob{}, (float*)nullptr, tile_pre_l, nb);
-            else hipLaunchKernelGGL((k_logits_stream<1, bf16_t>), grid_l, dim3(256), ldsw, st, b16, offsets, p->fc_w, p->fc_b, classes_out, part_val, part_idx, K, C, b0, rowmap, r0, (int*)nullptr, TrainPrologueJob{}, (float*)nullptr, tile_pre_l, nb);
-        }
-        else if (bf16 && w4) hipLaunchKernelGGL((k_logits_argmax<4, false, bf16_t>), grid, dim3(256), 0, st, b16, offsets, p->fc_w, p->fc_b, classes_in, classes_out, part_val, part_idx, K, C, b0, rowmap);
-        else if (bf16) hipLaunchKernelGGL((k_logits_argmax<1, false, bf16_t>), grid, dim3(256), 0, st, b16, offsets, p->fc_w, p->fc_b, classes_in, classes_out, part_val, part_idx, K, C, b0, rowmap);
-        else if (v4 && !logits_old) {
-            const size_t ldsw = (size_t)(C >= 2 ? 2 : 1) * (((K + 31) / 32 + 1) * 32) * sizeof(float);
-            const TrainPrologueJob job = sh.job ? *sh.job : TrainPrologueJob{};
-            dim3 gridj(grid_l.x + (unsigned)job.blocks, grid_l.y);   // (a training step is one bag: never the flat grid)
-            if (C >= 2) hipLaunchKernelGGL((k_logits_stream<2, float>), gridj, dim3(256), ldsw, st, f32, offsets, p->fc_w, p->fc_b, classes_out, part_val, part_idx, K, C, b0, rowmap, r0, qflag, job, rowmax, tile_pre_l, nb);
-            else hipLaunchKernelGGL((k_logits_stream<1, float>), gridj, dim3(256), ldsw, st, f32, offsets, p->fc_w, p->fc_b, classes_out, part_val, part_idx, K, C, b0, rowmap, r0, qflag, job, rowmax, tile_pre_l, nb);
-        }
-        else if (v4) hipLaunchKernelGGL((k_logits_argmax<4, false, float>), grid, dim3(256), 0, st, f32, offsets, p->fc_w, p->fc_b, classes_in, classes_out, part_val, part_idx, K, C, b0, rowmap);
-        else hipLaunchKernelGGL((k_logits_argmax<1, false, float>), grid, dim3(256), 0, st, f32, offsets, p->fc_w, p->fc_b, classes_in, classes_out, part_val, part_idx, K, C, b0, rowmap);
         if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
-        // 2. critical instance + its query
-        dim3 gq((unsigned)nb, (unsigned)C);
-        if (sh.phase == 1) {
-            if (v4) hipLaunchKernelGGL((k_qmax<4, float>), gq, dim3(QMAX_T), 0, st, f32, offsets, part_val, part_idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, idx, K, C, p->nonlinear, b0, 1, sh.best_val, rowmap, r0);
-            else hipLaunchKernelGGL((k_qmax<1, float>), gq, dim3(QMAX_T), 0, st, f32, offsets, part_val, part_idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, idx, K, C, p->nonlinear, b0, 1, sh.best_val, rowmap, r0);
-            return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
-        }
-        if (qm_inline) {   // produced by the first C workgroups of every grid row of k_attend_hs
-            a.qm_flag = qflag; a.qm_part_val = part_val; a.qm_part_idx = part_idx; a.qm_idx = idx; a.qm_r0 = r0;
-        }
-        else if (sh.phase == 2) {
-            const bool r4 = (K % 4 == 0) && ((uintptr_t)sh.crit_rows % 16 == 0) && (((uintptr_t)p->q0_w) % 16 == 0);
-            if (r4) hipLaunchKernelGGL((k_qmax<4, float>), gq, dim3(QMAX_T), 0, st, sh.crit_rows, offsets, part_val, part_idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, idx, K, C, p->nonlinear, b0, 2, (float*)nullptr);
-            else hipLaunchKernelGGL((k_qmax<1, float>), gq, dim3(QMAX_T), 0, st, sh.crit_rows, offsets, part_val, part_idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, idx, K, C, p->nonlinear, b0, 2, (float*)nullptr);
-        }
-        else if (bf16 && w4) hipLaunchKernelGGL((k_qmax<4, bf16_t>), gq, dim3(qmax_t), 0, st, b16, offsets, part_val, part_idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, idx, K, C, p->nonlinear, b0, 0, (float*)nullptr, rowmap, r0);
-        else if (bf16) hipLaunchKernelGGL((k_qmax<1, bf16_t>), gq, dim3(qmax_t), 0, st, b16, offsets, part_val, part_idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, idx, K, C, p->nonlinear, b0, 0, (float*)nullptr, rowmap, r0);
-        else if (v4) hipLaunchKernelGGL((k_qmax<4, float>), gq, dim3(QMAX_T), 0, st, f32, offsets, part_val, part_idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, idx, K, C, p->nonlinear, b0, 0, (float*)nullptr, rowmap, r0);
-        else hipLaunchKernelGGL((k_qmax<1, float>), gq, dim3(QMAX_T), 0, st, f32, offsets, part_val, part_idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, idx, K, C, p->nonlinear, b0, 0, (float*)nullptr, rowmap, r0);
+    }
+    // 2. critical instance + its query
+    if (r.qmax == DSMIL_QMAX_INLINE) {   // produced by the first C workgroups of every grid row of k_attend_hs
+        a.qm_flag = qflag; a.qm_part_val = part_val; a.qm_part_idx = part_idx; a.qm_idx = idx; a.qm_r0 = r.r0;
+    } else {
+        auto go = [&](auto kern, auto* x) {   // (mode = the shard phase; a shard's critical rows are not behind a row map)
+            hipLaunchKernelGGL(kern, dim3((unsigned)n_bags, (unsigned)C), dim3(r.qmax_threads), 0, st, x, offsets, part_val, part_idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b,
+                               qmax, idx, K, C, p->nonlinear, 0, sh.phase, sh.best_val, sh.phase == 2 ? nullptr : rowmap, r.r0);
+        };
+        const float* x = sh.phase == 2 ? sh.crit_rows : f32;
+        if (bf16 && !sh.phase) { if (r.qmax_vec == 4) go(k_qmax<4, bf16_t>, b16); else go(k_qmax<1, bf16_t>, b16); }
+        else { if (r.qmax_vec == 4) go(k_qmax<4, float>, x); else go(k_qmax<1, float>, x); }
         if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
-        // 3. query MLP on MFMA + scores + tile softmax + weighted value sum
-        int rc;
-        seg_per = seg_T = 0;
-        const int mode = (NW == 8) ? 0 : mlp_mode();
-        if (use_f2 && sh.packed_f2) {
-            a.wpk = (const bf16_t*)sh.packed_f2;  // the caller cut the weights once (dsmil_agg_pack_f2)
-        } else if (use_f2) {
-            _Float16* wf2 = (_Float16*)(w8 + L.wf2);
-            hipLaunchKernelGGL(k_pack_agg_f2, dim3(64), dim3(256), 0, st, p->q0_w, p->nonlinear ? p->q2_w : nullptr, wf2, K, 2 * ((K + 31) / 32));
-            if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
-            a.wpk = (const bf16_t*)wf2;
-        } else if (!bf16 && mode && packed_split) {
-            a.wpk = (const bf16_t*)packed_split;  // the caller cut the weights once (dsmil_agg_pack_split)
-        } else if (!bf16 && mode) {
+        if (sh.phase == 1) return DSMIL_OK;
+    }
+    // 3. the weight image: the caller's (cut once per weight set: dsmil_agg_pack_f2 / dsmil_agg_pack_split), or cut into the workspace
+    switch (r.image) {
+        case DSMIL_IMAGE_F2_CALLER: a.wpk = (const bf16_t*)sh.packed_f2; break;
+        case DSMIL_IMAGE_SPLIT_CALLER: a.wpk = (const bf16_t*)packed_split; break;
+        case DSMIL_IMAGE_F2_CUT:
+        case DSMIL_IMAGE_SPLIT_CUT: {
+            const float* w2 = p->nonlinear ? p->q2_w : nullptr;
             const int nks = 2 * ((K + 31) / 32);
-            bf16_t* wsplit = (bf16_t*)(w8 + L.wsplit);
-            hipLaunchKernelGGL(k_pack_agg_split, dim3(64), dim3(256), 0, st, p->q0_w, p->nonlinear ? p->q2_w : nullptr, wsplit, K, nks);
+            a.wpk = (const bf16_t*)(w8 + (r.image == DSMIL_IMAGE_F2_CUT ? L.wf2 : L.wsplit));
+            if (r.image == DSMIL_IMAGE_F2_CUT) hipLaunchKernelGGL(k_pack_agg_f2, dim3(64), dim3(256), 0, st, p->q0_w, w2, (_Float16*)a.wpk, K, nks);
+            else hipLaunchKernelGGL(k_pack_agg_split, dim3(64), dim3(256), 0, st, p->q0_w, w2, (bf16_t*)a.wpk, K, nks);
             if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
-            a.wpk = wsplit;
+            break;
         }
-        bool bf16_dma = bf16 && NW == 4;   // feature rows are 16-B aligned on this path (K % 8 == 0, checked above)
-#ifdef DSMIL_EXPERIMENTS
-        if (a.expt & 256) bf16_dma = false;
-#endif
-        bool bf16_res = bf16_dma && bf16_res_ok(a);
-#ifdef DSMIL_EXPERIMENTS
-        if (a.expt & 512) bf16_res = false;
-#endif
-        const bool use_f3 = use_f2 && p->nonlinear && C <= 2 && g_use_f2.load(std::memory_order_relaxed) == 2;
-        // ragged batch on a persistent kernel: the item list is the real tiles (prefix per bag), not max_rows-padded bags
-        if (tile_pre_a && (use_f3 || bf16_res)) {
-            a.tile_pre = tile_pre_a;
-            a.n_bags = nb;
-        }
-        if (use_f3) { rc = launch_attend_f3(a, rowmax, max_rows, total_rows, nb, st, &seg_per, &seg_T); hs_bm = F3_BM; }
-        else if (use_f2) { rc = launch_attend_f2(a, rowmax, max_rows, nb, st); hs_bm = F2_BM; }
-        else if (bf16_res) rc = launch_attend_bf16_res(a, max_rows, total_rows, nb, st, &seg_per, &seg_T);
-        else if (bf16_dma) rc = launch_attend_bf16_dma(a, max_rows, nb, st);
-        else if (bf16) rc = (NW == 4) ? launch_attend_bf16<4>(a, max_rows, nb, st) : launch_attend_bf16<1>(a, max_rows, nb, st);
-#ifdef DSMIL_EXPERIMENTS   // DSMIL_MLP=s9 and the ablation variants: not instantiated in the product library
-        else if (mode == 9 && NW == 4) rc = v4 ? launch_attend_split<4, 4, 9>(a, max_rows, nb, st) : launch_attend_split<4, 1, 9>(a, max_rows, nb, st);
-        else if (mode == 9) rc = v4 ? launch_attend_split<1, 4, 9>(a, max_rows, nb, st) : launch_attend_split<1, 1, 9>(a, max_rows, nb, st);
-        else if (mode == 6 && NW == 4 && v4 && (a.expt & 16)) rc = launch_attend_split<4, 4, 6, false, 16>(a, max_rows, nb, st);
-        else if (mode == 6 && NW == 4 && v4 && (a.expt & 32)) rc = launch_attend_split<4, 4, 6, false, 32>(a, max_rows, nb, st);
-        else if (mode == 6 && NW == 4 && v4 && (a.expt & 8)) rc = launch_attend_split<4, 4, 6, true>(a, max_rows, nb, st);
-        else if (mode == 6 && NW == 1 && v4 && (a.expt & 8)) rc = launch_attend_split<1, 4, 6, true>(a, max_rows, nb, st);
-#endif
-        else if (mode == 6 && NW == 4) rc = v4 ? launch_attend_split<4, 4, 6>(a, max_rows, nb, st) : launch_attend_split<4, 1, 6>(a, max_rows, nb, st);
-        else if (use_hs) { rc = launch_attend_hs(a, max_rows, nb, st); hs_bm = HS_BM; }   // few rows: hidden units split over the SIMDs
-        else if (mode == 6) rc = v4 ? launch_attend_split<1, 4, 6>(a, max_rows, nb, st) : launch_attend_split<1, 1, 6>(a, max_rows, nb, st);
-        else if (NW == 8) rc = launch_attend<8, 4>(a, max_rows, nb, st);
-        else if (NW == 4) rc = v4 ? launch_attend<4, 4>(a, max_rows, nb, st) : launch_attend<4, 1>(a, max_rows, nb, st);
-        else rc = v4 ? launch_attend<1, 4>(a, max_rows, nb, st) : launch_attend<1, 1>(a, max_rows, nb, st);
-        if (rc != DSMIL_OK) return rc;
+        default: break;   // the bf16 image came with the call (a.wpk); k_query_attend reads the fp32 weights themselves
     }
-    // 4. combine (skipped under the stamp-trace knob, which leaves its stamps in A)
-    if (!DSMIL_EXPT_ON(a, 64)) {
-        dim3 grid((unsigned)L.nchunk_max, (unsigned)n_bags);
-        if (Kv % 4 == 0 && lean_tail && seg_per && !hs_bm)
-            hipLaunchKernelGGL((k_finish<4, 2>), grid, dim3(256), 0, st, offsets, part_ml, part_B, p->fcc_w, A, B, pred_part, Kv, C, RS_BM, sh.ml_out, seg_per, seg_T, a.tile_pre);
-        else if (Kv % 4 == 0)
-            hipLaunchKernelGGL(k_finish<4>, grid, dim3(256), 0, st, offsets, part_ml, part_B, p->fcc_w, A, B, pred_part, Kv, C, hs_bm ? hs_bm : (seg_per ? RS_BM : BM), sh.ml_out, seg_per, seg_T, a.tile_pre);
-        else
-            hipLaunchKernelGGL(k_finish<1>, grid, dim3(256), 0, st, offsets, part_ml, part_B, p->fcc_w, A, B, pred_part, Kv, C, BM, sh.ml_out, 0, 0);
-        if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
-        if (sh.phase == 2 || sh.skip_pred) return DSMIL_OK;  // the bag head runs after the cross-shard merge / in the caller's next launch
-        // (folding this sum into k_finish's last block per bag — a device-scope fence + ticket in every block — was tried:
-        // 11 -> 52 us for 64 bags, the fences wait for the 5 MB of attention the blocks have just written)
-        const int n = n_bags * C;
-        hipLaunchKernelGGL(k_pred, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pred_part,
-                           p->fcc_b, pred, C, (int)L.nchunk_max, n_bags);
-        if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
-    }
-    return DSMIL_OK;
+    // 4. query MLP on MFMA + scores + tile softmax + weighted value sum
+    if (r.ragged_attend) { a.tile_pre = tile_pre_a; a.n_bags = n_bags; }
+    const Attended att = launch_attend(r, a, rowmax, max_rows, total_rows, n_bags, st);
+    if (att.rc != DSMIL_OK) return att.rc;
+    // 5. combine
+    if (r.finish == DSMIL_FINISH_NONE) return DSMIL_OK;
+    auto finish = [&](auto kern, int per, int T, const int* tile_pre) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)L.nchunk_max, (unsigned)n_bags), dim3(256), 0, st, offsets, part_ml, part_B, p->fcc_w, A, B, pred_part, Kv, C,
+                           r.finish_rows, sh.ml_out, per, T, tile_pre);
+    };
+    if (r.finish == DSMIL_FINISH_LEAN) finish(k_finish<4, 2>, att.per, att.T, a.tile_pre);
+    else if (r.finish == DSMIL_FINISH_VEC4) finish(k_finish<4>, att.per, att.T, a.tile_pre);
+    else finish(k_finish<1>, 0, 0, nullptr);
+    if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    if (!r.pred) return DSMIL_OK;
+    // 6. the bag head
+    // (folding this sum into k_finish's last block per bag — a device-scope fence + ticket in every block — was tried:
+    // 11 -> 52 us for 64 bags, the fences wait for the 5 MB of attention the blocks have just written)
+    const int n = n_bags * C;
+    hipLaunchKernelGGL(k_pred, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pred_part,
+                       p->fcc_b, pred, C, (int)L.nchunk_max, n_bags);
+    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 
 int dsmil_agg_forward(const float* feats, const float* vals, const int64_t* offsets,
@@ -2093,13 +2092,14 @@ int dsmil_agg_forward_ex(const float* feats, const float* vals, const int64_t* o
 }
 
 }  // extern "C"
+// the route of the training step's forward (one bag, v = Identity, no bag head) has a logits launch that can carry the job
 bool dsmil_agg_forward_carries_prologue(const float* feats, int64_t total_rows, const dsmil_agg_params* p) {
-#ifdef DSMIL_EXPERIMENTS
-    static const int off = expt_env("DSMIL_LOGITS_OLD") | expt_env("DSMIL_NO_PROLOGUE_ROLE");
-    if (off) return false;
-#endif
-    (void)total_rows;
-    return feats && p && p->fc_w && fwd_v4(feats, feats, p);   // = the fp32 k_logits_stream launch of agg_forward_impl
+    if (expt().no_prologue_role || !feats || !p || !p->fc_w) return false;
+    ShardCtl sh;
+    sh.skip_pred = true;
+    Call c = describe_call(feats, feats, 1, total_rows, total_rows, p, false, false, sh, nullptr, nullptr);
+    c.prologue_job = 1;
+    return pick_route(c).prologue != 0;
 }
 int dsmil_agg_forward_nopred(const float* feats, const int64_t* offsets, int64_t total_rows, const dsmil_agg_params* p,
                              const dsmil_agg_opts* opts, float* classes_out, float* A, float* B, int64_t* idx, void* ws,
@@ -2113,6 +2113,7 @@ int dsmil_agg_forward_nopred(const float* feats, const int64_t* offsets, int64_t
                             opts ? opts->row_map : nullptr);
 }
 extern "C" {
+
 
 // ---- fused training objective of one bag (train_tcga.py:67-71) -----------------------------------------
 // loss = 0.5 BCEWithLogits(pred, y) + 0.5 BCEWithLogits(max_n classes[n,:], y)   (mean over the C classes each),

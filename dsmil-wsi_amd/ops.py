@@ -324,10 +324,14 @@ def agg_forward(feats, lengths, w, classes_in=None, vals=None, nonlinear=True, o
                                           _stream(dev))
         else:
             split = _split_params(keep[2], keep[4], nonlinear, dev)
-            # batches in the 128-row-tile regime take k_attend_f3 / k_attend_f2 (K a multiple of 128 up to 512, v = Identity): its weight image
+            # the route of this call (the library's one decision): k_attend_f3 / k_attend_f2 read their own weight image
             f2 = None
-            if (split is not None and L.dsmil_agg_tile_rows(n_bags, total) == 128 and K % 128 == 0 and K <= 512 and vals is feats
-                    and classes_in is None):
+            ptrs = [feats, vals, keep[0], keep[2], keep[4] if nonlinear else None]
+            route = _native.forward_route(
+                total_rows=total, max_rows=max(lengths), n_bags=n_bags, K=K, Kv=Kv, C=C, nonlinear=1 if nonlinear else 0,
+                aligned=7 if all(t is None or t.data_ptr() % 16 == 0 for t in ptrs) else 0, classes_given=classes_in is not None,
+                vals_separate=vals is not feats, row_map=row_map is not None, packed_split=split is not None)
+            if _native.ATTEND[route.attend] in ("f3", "f2"):
                 f2 = _f2_params(keep[2], keep[4], nonlinear, dev)
             opts = _native.AggOpts(split.data_ptr() if split is not None else 0,
                                    row_map.data_ptr() if row_map is not None else 0,

@@ -522,6 +522,70 @@ int dsmil_abi_version(void);
 /* Rows per workgroup the launcher picks for the dominant kernel (k_query_attend). */
 int dsmil_agg_tile_rows(int32_t n_bags, int64_t total_rows);
 
+/* ---- the aggregator forward's route: which kernels a call takes ----------------------------------------------------------
+ * Every forward entry point (dsmil_agg_forward, _ex, _bf16, dsmil_agg_shard_argmax, dsmil_agg_shard_attend, the training
+ * step) describes its call as a dsmil_agg_call and launches what the ONE route function of the library (pick_route,
+ * csrc/agg_fwd.hip) answers for it.  dsmil_agg_forward_route asks the same function without touching a device, a stream or
+ * the library's record of recent streams.  It reads the run-time knobs as they stand (dsmil_agg_batch_form,
+ * dsmil_agg_inline_query, dsmil_agg_logits_form).  Diagnostic: the values below name kernels of THIS library build.
+ * Added without a change of DSMIL_ABI_VERSION (it stays 6, no existing signature moved): a caller finds it by symbol. */
+typedef struct dsmil_agg_call {
+    int64_t total_rows, max_rows;
+    int32_t n_bags, K, Kv, C, nonlinear;
+    int32_t bf16;            /* dsmil_agg_forward_bf16 (features, values stored as bf16) */
+    int32_t aligned;         /* 16-byte alignment of the fp32 operands, bit 0: feats, vals, fc_w, q0_w and q2_w (all of them);
+                              * bit 1: fc_w and q0_w; bit 2: crit_rows and q0_w (dsmil_agg_shard_attend) */
+    int32_t classes_given;   /* classes_in != NULL */
+    int32_t vals_separate;   /* vals != NULL and != feats */
+    int32_t row_map;         /* dsmil_agg_opts::row_map != NULL */
+    int32_t packed_split;    /* dsmil_agg_opts::packed_split != NULL */
+    int32_t packed_f2;       /* dsmil_agg_opts::packed_f2 != NULL */
+    int32_t phase;           /* 0 a whole forward, 1 dsmil_agg_shard_argmax, 2 dsmil_agg_shard_attend */
+    int32_t skip_pred;       /* the training step: the bag head is left to the caller's next launch */
+    int32_t prologue_job;    /* the training step: the logits launch is asked to carry the prologue job */
+    int32_t several_streams; /* the library has recently been called on more than one stream (dsmil_agg_logits_form(1)) */
+    int32_t cus;             /* compute units of the device; 0 = ask the current device */
+} dsmil_agg_call;
+
+enum { DSMIL_LOGITS_NONE = 0, DSMIL_LOGITS_GIVEN, DSMIL_LOGITS_STREAM, DSMIL_LOGITS_PIPE, DSMIL_LOGITS_ARGMAX };
+enum { DSMIL_QMAX_LAUNCH = 0, DSMIL_QMAX_INLINE, DSMIL_QMAX_SHARD1, DSMIL_QMAX_SHARD2 };
+enum { DSMIL_IMAGE_NONE = 0, DSMIL_IMAGE_F2_CALLER, DSMIL_IMAGE_F2_CUT, DSMIL_IMAGE_SPLIT_CALLER, DSMIL_IMAGE_SPLIT_CUT,
+       DSMIL_IMAGE_BF16 };
+enum { DSMIL_ATTEND_NONE = 0, DSMIL_ATTEND_F3, DSMIL_ATTEND_F2, DSMIL_ATTEND_BF16_RES, DSMIL_ATTEND_BF16_DMA,
+       DSMIL_ATTEND_BF16_RING, DSMIL_ATTEND_SPLIT, DSMIL_ATTEND_HS, DSMIL_ATTEND_F32 };
+enum { DSMIL_FINISH_NONE = 0, DSMIL_FINISH_LEAN, DSMIL_FINISH_VEC4, DSMIL_FINISH_SCALAR };
+
+typedef struct dsmil_agg_route {
+    int32_t nw;             /* tile regime: 4 = 128-row workgroups, 1 = 32-row (dsmil_agg_tile_rows / 32) */
+    int32_t r0;             /* rows per workgroup of the logits pass (= the tile of the arg-max partials) */
+    int32_t logits;         /* DSMIL_LOGITS_*: none (shard phase 2) / k_logits_argmax on given classes / k_logits_stream /
+                             * k_logits_pipe / k_logits_argmax */
+    int32_t logits_vec;     /* k_logits_argmax: 4 = 16-byte loads, 1 = scalar */
+    int32_t logits_cp;      /* k_logits_stream, k_logits_pipe: classes per pass (1 or 2) */
+    int32_t prologue;       /* the logits launch carries the training step's prologue job */
+    int32_t rowmax;         /* the logits launch leaves max |x| per row (k_attend_f2 / k_attend_f3) */
+    int32_t qmax;           /* DSMIL_QMAX_*: k_qmax launch / inside k_attend_hs / the shard phases' forms of k_qmax */
+    int32_t qmax_vec;       /* k_qmax: 4 or 1 */
+    int32_t qmax_threads;   /* k_qmax: 1024, or 256 behind k_logits_pipe */
+    int32_t ragged;         /* k_tile_prefix runs: the logits pass works from the list of real tiles */
+    int32_t ragged_attend;  /* ... and so does the (persistent) attend kernel */
+    int32_t tile_attend;    /* k_tile_prefix: rows per tile of the attend list ... */
+    int32_t tile_logits;    /* ... and of the logits list */
+    int32_t image;          /* DSMIL_IMAGE_*: the weight image the attend kernel reads and who cuts it */
+    int32_t attend;         /* DSMIL_ATTEND_* */
+    int32_t attend_nw;      /* waves per 32 rows x this = rows per tile of the ring / split / f32 kernels (4 or 1) */
+    int32_t attend_vec;     /* split / f32 kernels: 4 = DMA tile, 1 = register-staged tile */
+    int32_t attend_np;      /* split kernel: plane products (6; 9 in experiment builds) */
+    int32_t attend_xe;      /* experiment builds: ablation forms of the split kernel (0 in the product library) */
+    int32_t attend_tu;
+    int32_t finish;         /* DSMIL_FINISH_*: k_finish<4, 2> / k_finish<4> / k_finish<1>; none under the stamp-trace knob */
+    int32_t finish_rows;    /* rows per partial tile k_finish is told */
+    int32_t pred;           /* k_pred runs */
+} dsmil_agg_route;
+
+/* Fills *route for *call.  DSMIL_E_INVALID for null pointers or non-positive sizes, else DSMIL_OK.  HOST function. */
+int dsmil_agg_forward_route(const dsmil_agg_call* call, dsmil_agg_route* route);
+
 /* Measurement hooks (bench.py's roofline leg; no reference counterpart).  While enabled, every
  * launch of a dominant kernel is bracketed by hipEventRecord on its own launch stream (up to 4096
  * launches per channel: 0 = k_query_attend of the aggregator, 1 = k_conv of the embedder);
