@@ -34,6 +34,9 @@
 //                        exactly what it launched before
 // dsmil_agg_train_step chains forward -> loss head -> this backward -> one Adam kernel over all eight tensors:
 // one C call per train_tcga.py:60-75 step.
+// dsmil_agg_backward_bags (agg_bwd_bags.h, included below) is this backward over a BATCH of bags stored back to back: the
+// row kernels above run over all rows of the batch, the per-bag steps get a batched form (k_bwd_rows / k_bwd_rows_hs with
+// BAGS = true walk a grid of tile slots, slot_owner).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -216,14 +219,11 @@ __global__ void k_train_prologue(const float* __restrict__ q0_w, const float* __
 
 // ---- k_bwd_qrow: q_c = q(x[idx_c]) (dsmil.py:53-54), one workgroup per class ------------------
 template <int VEC>
-__global__ __launch_bounds__(256) void k_bwd_qrow(
-    const float* __restrict__ feats, const int64_t* __restrict__ idx, const float* __restrict__ q0_w,
-    const float* __restrict__ q0_b, const float* __restrict__ q2_w, const float* __restrict__ q2_b,
-    float* __restrict__ qmax, int K, int nonlinear, const int64_t* __restrict__ rowmap) {
-    const int c = blockIdx.x;
+__device__ __forceinline__ void qrow_body(const float* __restrict__ x, const float* __restrict__ q0_w,
+                                          const float* __restrict__ q0_b, const float* __restrict__ q2_w,
+                                          const float* __restrict__ q2_b, float* __restrict__ out, int K, int nonlinear) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     __shared__ float s_h[QD];
-    const float* x = feats + phys_row(rowmap, idx[c]) * (long long)K;
     for (int jb = 0; jb < 32; jb += 8) {
         float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         const float* wr = q0_w + (long long)(wave * 32 + jb) * K;
@@ -245,7 +245,6 @@ __global__ __launch_bounds__(256) void k_bwd_qrow(
         }
     }
     __syncthreads();
-    float* out = qmax + (long long)c * QD;
     if (!nonlinear) {
         if (threadIdx.x < QD) out[threadIdx.x] = s_h[threadIdx.x];
         return;
@@ -256,6 +255,14 @@ __global__ __launch_bounds__(256) void k_bwd_qrow(
         const float a = wave_sum(fmaf(h0, wr[lane], h1 * wr[lane + 64])) + q2_b[wave * 32 + jj];
         if (lane == 0) out[wave * 32 + jj] = tanhf(a);
     }
+}
+template <int VEC>
+__global__ __launch_bounds__(256) void k_bwd_qrow(
+    const float* __restrict__ feats, const int64_t* __restrict__ idx, const float* __restrict__ q0_w,
+    const float* __restrict__ q0_b, const float* __restrict__ q2_w, const float* __restrict__ q2_b,
+    float* __restrict__ qmax, int K, int nonlinear, const int64_t* __restrict__ rowmap) {
+    const int c = blockIdx.x;
+    qrow_body<VEC>(feats + phys_row(rowmap, idx[c]) * (long long)K, q0_w, q0_b, q2_w, q2_b, qmax + (long long)c * QD, K, nonlinear);
 }
 
 // ---- k_bwd_rows ----------------------------------------------------------------------------
@@ -270,7 +277,23 @@ struct BwdRowsArgs {
     float* Hbuf;          // [N,128]
     float* Qbuf;          // [N,128]
     float* gqp;           // [ceil(N/32), C, 128]: per 32-row wave tile, sum_n gs[n,c] Q[n,:]
+    int n_bags;           // BAGS kernels (agg_bwd_bags.h): at.offsets has n_bags + 1 entries, Dv / at.qmax one set per bag
 };
+
+// BAGS kernels: a 1-D grid of tile SLOTS over a batch of bags stored back to back.  Bag b owns the slots from
+// slot0(b) = offsets[b] / BM + b on: consecutive bags' ranges never overlap (a bag of n rows needs ceil(n / BM) <=
+// slot0(b+1) - slot0(b) slots) and the batch needs at most total_rows / BM + n_bags of them, so a ragged batch launches its
+// REAL tiles plus at most one idle slot per bag — no prefix pass, no grid sized by the longest bag.  Largest b with
+// slot0(b) <= slot (uniform address: scalar loads, once per workgroup).
+__device__ __forceinline__ int slot_owner(const int64_t* off_, int n_bags, long long slot, int bm) {
+    const __attribute__((address_space(4))) int64_t* off = (const __attribute__((address_space(4))) int64_t*)(uintptr_t)off_;
+    int lo = 0, hi = n_bags;           // invariant: slot0(lo) <= slot < slot0(hi)   (slot0(n_bags) > every slot of the grid)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((long long)off[mid] / bm + mid <= slot) lo = mid; else hi = mid;
+    }
+    return lo;
+}
 
 // stores the hidden layer from the accumulator registers: register 4g+e of H[t] = unit 32t + 8g + 4hi + e of row l31
 struct StoreH {
@@ -338,37 +361,56 @@ __device__ __forceinline__ void halfwave_colsum64(const float (&v)[64], int l31,
     }
 }
 
-template <int NW, int VEC>
+template <int NW, int VEC, bool BAGS = false>
 __global__ __launch_bounds__(NW * 64, (NW == 1 ? 1 : 2)) void k_bwd_rows(BwdRowsArgs b) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const AttendArgs& a = b.at;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
-    const long long Nb = a.offsets[1] - a.offsets[0];
-    const long long row = (long long)blockIdx.x * (NW * 32) + wave * 32 + l31;
+    // BAGS: bag and tile of this slot; the bag's first row and first 32-row tile slot go into the (uniform) base pointers,
+    // so that the per-lane state is the one-bag kernel's: rows are bag-local throughout.  One bag: all zero.
+    int bag = 0, tile = (int)blockIdx.x;
+    long long off0 = 0, t32_0 = 0;
+    if constexpr (BAGS) {
+        bag = slot_owner(a.offsets, b.n_bags, blockIdx.x, NW * 32);
+        off0 = a.offsets[bag];
+        tile = (int)((long long)blockIdx.x - (off0 / (NW * 32) + bag));
+        t32_0 = off0 / 32 + bag;
+    }
+    const int C = a.C;
+    const float* pA = b.A + off0 * C;
+    const float* pgA = b.gA + off0 * C;
+    const float* pg_A = b.g_A ? b.g_A + off0 * C : nullptr;
+    float* pgs = b.gs + off0 * C;
+    float* pgz2 = b.gz2 + off0 * QD;
+    float* pQ = b.Qbuf + off0 * QD;
+    float* pgqp = b.gqp + t32_0 * C * QD;
+    const float* Dv = b.Dv + (long long)bag * C;
+    const float* qmax = a.qmax + (long long)bag * C * QD;
+    const long long Nb = a.offsets[bag + 1] - a.offsets[bag];
+    const long long row = (long long)tile * (NW * 32) + wave * 32 + l31;
     const bool valid = row < Nb;
     f32x16 Q[4];
-    const StoreH hook{a.nonlinear ? b.Hbuf : nullptr, row, valid && a.nonlinear, hi};
+    const StoreH hook{a.nonlinear ? b.Hbuf + off0 * QD : nullptr, row, valid && a.nonlinear, hi};
     if constexpr (VEC == 4) {
-        if (!mlp_tile_split_dma<NW, NP_BWD, false>(a, 0, (int)blockIdx.x, smem, Q, hook)) return;
+        if (!mlp_tile_split_dma<NW, NP_BWD, false>(a, bag, tile, smem, Q, hook)) return;
     } else {
-        if (!mlp_tile_split<NW, VEC, NP_BWD>(a, 0, (int)blockIdx.x, smem, Q, hook)) return;
+        if (!mlp_tile_split<NW, VEC, NP_BWD>(a, bag, tile, smem, Q, hook)) return;
     }
     const long long rc = valid ? row : Nb - 1;
-    const int C = a.C;
     const float scale = 0.08838834764831845f;  // 1/sqrt(128)
     f32x16 G[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) G[t][r] = 0.f;
-    const long long wtile = (long long)blockIdx.x * NW + wave;         // this wave's 32-row tile
+    const long long wtile = (long long)tile * NW + wave;               // this wave's 32-row tile
     const bool wave_live = wtile * 32 < Nb;                            // (uniform per wave)
     for (int c = 0; c < C; ++c) {
-        float ga = b.gA[rc * C + c];
-        if (b.g_A) ga += b.g_A[rc * C + c];
-        const float gsc = valid ? b.A[rc * C + c] * (ga - b.Dv[c]) * scale : 0.f;
-        if (valid && hi == 0) b.gs[row * C + c] = gsc;
-        const float* qm = a.qmax + (long long)c * QD;
+        float ga = pgA[rc * C + c];
+        if (pg_A) ga += pg_A[rc * C + c];
+        const float gsc = valid ? pA[rc * C + c] * (ga - Dv[c]) * scale : 0.f;
+        if (valid && hi == 0) pgs[row * C + c] = gsc;
+        const float* qm = qmax + (long long)c * QD;
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -387,7 +429,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 1 ? 1 : 2)) void k_bwd_rows(BwdRows
         halfwave_colsum64(v, l31, s0, s1);
         if (wave_live) {
             const int i = 2 * l31, t = i >> 4, r = i & 15;              // indices i, i+1 = registers r, r+1 of tile t
-            float* o = b.gqp + (wtile * C + c) * QD + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * hi;
+            float* o = pgqp + (wtile * C + c) * QD + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * hi;
             o[0] = s0;
             o[1] = s1;
         }
@@ -406,8 +448,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 1 ? 1 : 2)) void k_bwd_rows(BwdRows
                 qv[e] = q;
             }
             const long long o = row * QD + 32 * t + 8 * g + 4 * hi;
-            *reinterpret_cast<f32x4*>(b.gz2 + o) = gz;
-            *reinterpret_cast<f32x4*>(b.Qbuf + o) = qv;
+            *reinterpret_cast<f32x4*>(pgz2 + o) = gz;
+            *reinterpret_cast<f32x4*>(pQ + o) = qv;
         }
 }
 
@@ -465,31 +507,42 @@ __device__ __forceinline__ float halfwave_colsum16(const float (&v)[16], int l31
     return a1 + __shfl_xor(a1, 1, 64);
 }
 
+template <bool BAGS = false>
 __global__ __launch_bounds__(HS_THREADS, 2) void k_bwd_rows_hs(BwdRowsArgs b) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const AttendArgs& a = b.at;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
-    const long long Nb = a.offsets[1] - a.offsets[0];
+    int bag = 0, tile = (int)blockIdx.x;      // BAGS: see k_bwd_rows
+    long long off0 = 0, t32_0 = 0;
+    if constexpr (BAGS) {
+        bag = slot_owner(a.offsets, b.n_bags, blockIdx.x, HS_BM);
+        off0 = a.offsets[bag];
+        tile = (int)((long long)blockIdx.x - (off0 / HS_BM + bag));
+        t32_0 = off0 / 32 + bag;
+    }
+    const long long Nb = a.offsets[bag + 1] - a.offsets[bag];
     f32x16 Hw[HS_RG], Qw[HS_RG];
-    if (!mlp_tile_hs<NP_BWD>(a, 0, (int)blockIdx.x, smem, Hw, Qw)) return;
+    if (!mlp_tile_hs<NP_BWD>(a, bag, tile, smem, Hw, Qw)) return;
+    const float* Dv = b.Dv + (long long)bag * a.C;
     const int C = a.C, u0 = 32 * wave + 4 * hi;     // reg 4q+e <-> unit u0 + 8q + e
     const float scale = 0.08838834764831845f;       // 1/sqrt(128)
 #pragma unroll
     for (int g = 0; g < HS_RG; ++g) {
-        const long long row = (long long)blockIdx.x * HS_BM + 32 * g + l31;
-        const long long t32 = (long long)blockIdx.x * HS_RG + g;     // this group's 32-row tile
-        if (t32 * 32 >= Nb) break;                                   // (block-uniform)
-        const bool valid = row < Nb;
-        const long long rc = valid ? row : Nb - 1;
+        const long long lrow = (long long)tile * HS_BM + 32 * g + l31;   // bag-local
+        const long long l32 = (long long)tile * HS_RG + g;           // this group's 32-row tile of the bag
+        if (l32 * 32 >= Nb) break;                                   // (block-uniform)
+        const bool valid = lrow < Nb;
+        const long long row = off0 + lrow, t32 = t32_0 + l32;        // row / tile slot of the batch
+        const long long rc = valid ? row : off0 + Nb - 1;
         float G[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) G[r] = 0.f;
         for (int c = 0; c < C; ++c) {
             float ga = b.gA[rc * C + c];
             if (b.g_A) ga += b.g_A[rc * C + c];
-            const float gsc = valid ? b.A[rc * C + c] * (ga - b.Dv[c]) * scale : 0.f;
+            const float gsc = valid ? b.A[rc * C + c] * (ga - Dv[c]) * scale : 0.f;
             if (valid && hi == 0 && wave == 0) b.gs[row * C + c] = gsc;
-            const float* qm = a.qmax + (long long)c * QD + u0;
+            const float* qm = a.qmax + ((long long)bag * C + c) * QD + u0;
             float v[16];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -528,9 +581,9 @@ __global__ __launch_bounds__(HS_THREADS, 2) void k_bwd_rows_hs(BwdRowsArgs b) {
 
 // g_q[c] = sum over the 32-row tiles of their partials (fixed order); gz2[idx_c] += g_q[c] (1 - Q[idx_c]^2): q_c IS row
 // idx_c of Q, so its gradient joins that row.  One workgroup of 1024 threads = 128 units x 8 strided tile groups.
-__global__ __launch_bounds__(1024) void k_bwd_critical(const int64_t* __restrict__ idx, const float* __restrict__ gqp,
-                                                       const float* __restrict__ Qbuf, float* __restrict__ gz2,
-                                                       float* __restrict__ gq, long long ntile, int C, int nonlinear) {
+__device__ __forceinline__ void critical_body(const int64_t* __restrict__ idx, const float* __restrict__ gqp,
+                                              const float* __restrict__ Qbuf, float* __restrict__ gz2,
+                                              float* __restrict__ gq, long long ntile, int C, int nonlinear) {
     __shared__ float red[8][QD];
     const int j = threadIdx.x & (QD - 1), grp = threadIdx.x >> 7;
     for (int c = 0; c < C; ++c) {
@@ -547,6 +600,11 @@ __global__ __launch_bounds__(1024) void k_bwd_critical(const int64_t* __restrict
             gz2[o] += g * (nonlinear ? (1.f - q * q) : 1.f);   // classes run in order: two classes may share a row
         }
     }
+}
+__global__ __launch_bounds__(1024) void k_bwd_critical(const int64_t* __restrict__ idx, const float* __restrict__ gqp,
+                                                       const float* __restrict__ Qbuf, float* __restrict__ gz2,
+                                                       float* __restrict__ gq, long long ntile, int C, int nonlinear) {
+    critical_body(idx, gqp, Qbuf, gz2, gq, ntile, C, nonlinear);
 }
 
 // ---- k_bwd_gh: gH = (gz2 W2) [H > 0] — forward GEMM-1 pipeline with X := gz2, W := W2^T ------------
@@ -1164,12 +1222,13 @@ BwdWs bwd_layout(long long N, int K, int Kv, int C, int nonlinear) {
 }
 
 template <typename KernelT, typename ArgT>
-int launch_tile_kernel(KernelT kern, const ArgT& arg, int nw, bool dma, long long N, hipStream_t st) {
+int launch_tile_kernel(KernelT kern, const ArgT& arg, int nw, bool dma, long long N, hipStream_t st, long long slots = 0) {
     const int BM = nw * 32;
     const size_t lds = dma ? (size_t)(3 * S3_CHUNK_F4 * 4 + 2 * BM * 32) * sizeof(float)
                            : (size_t)(2 * S3_CHUNK_F4 * 4 + 2 * BM * LDK) * sizeof(float);
     if (!dsmil_lds::allow((const void*)kern, (int)lds)) return DSMIL_E_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((N + BM - 1) / BM)), dim3(nw * 64), lds, st, arg);
+    // (slots: the tile slots of a batch of bags, agg_bwd_bags.h; else the tiles of N rows)
+    hipLaunchKernelGGL(kern, dim3((unsigned)(slots ? slots : (N + BM - 1) / BM)), dim3(nw * 64), lds, st, arg);
     return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 
@@ -1272,7 +1331,7 @@ int agg_backward_impl(const float* feats, const float* vals, int64_t N, const ds
         return hipGetLastError() == hipSuccess ? (int)DSMIL_OK : (int)DSMIL_E_LAUNCH;
     };
     if (nw == 4) rc = v4 ? launch_tile_kernel(k_bwd_rows<4, 4>, br, 4, true, N, st) : launch_tile_kernel(k_bwd_rows<4, 1>, br, 4, false, N, st);
-    else if (v4) rc = launch_hs(k_bwd_rows_hs, br);
+    else if (v4) rc = launch_hs(k_bwd_rows_hs<false>, br);
     else rc = launch_tile_kernel(k_bwd_rows<1, 1>, br, 1, false, N, st);
     if (rc) return rc;
     // 5. gradient of the critical queries joins their rows
@@ -1381,6 +1440,8 @@ StepWs step_layout(long long N, int K, int C, int nonlinear) {
 
 }  // namespace
 
+#include "agg_bwd_bags.h"
+
 extern "C" {
 
 size_t dsmil_agg_backward_workspace_bytes(int64_t N, int32_t K, int32_t Kv, int32_t C) {
@@ -1416,6 +1477,30 @@ int dsmil_agg_backward_rows(const float* feats, const float* vals, int64_t N, co
                             void* stream, float* g_feats) {
     return agg_backward_impl(feats, vals, N, p, A, Bm, idx, g_classes, g_max, g_pred, g_A, g_B, g, g_vals, rowmap,
                              ws, ws_bytes, stream, nullptr, nullptr, false, nullptr, nullptr, false, g_feats);
+}
+
+size_t dsmil_agg_backward_bags_workspace_bytes(int32_t n_bags, int64_t total_rows, int32_t K, int32_t Kv, int32_t C) {
+    if (n_bags <= 0 || total_rows <= 0 || K <= 0 || Kv <= 0 || C <= 0) return 0;
+    return bags_layout(n_bags, total_rows, K, Kv, C, 1).total;   // the nonlinear layout is the larger one
+}
+
+int dsmil_agg_backward_bags(const float* feats, const float* vals, const int64_t* offsets, int32_t n_bags,
+                            int64_t total_rows, int64_t max_rows, const dsmil_agg_params* p, const float* A,
+                            const float* Bm, const int64_t* idx, const float* g_classes, const float* g_max,
+                            const float* g_pred, const float* g_A, const float* g_B, const dsmil_agg_grads* g,
+                            float* g_vals, const int64_t* rowmap, void* ws, size_t ws_bytes, void* stream, float* g_feats) {
+    return agg_backward_bags_impl(feats, vals, offsets, n_bags, total_rows, max_rows, p, A, Bm, idx, g_classes, g_max, g_pred,
+                                  g_A, g_B, g, g_vals, rowmap, ws, ws_bytes, stream, g_feats);
+}
+
+int dsmil_agg_loss_head_bags(const float* classes, const int64_t* offsets, const float* pred, const int64_t* idx,
+                             const float* labels, int32_t n_bags, int32_t C, float* loss, float* max_pred, float* g_pred,
+                             float* g_max, void* stream) {
+    if (!classes || !offsets || !pred || !idx || !labels || !loss || n_bags < 1 || C <= 0) return DSMIL_E_INVALID;
+    if (C > 64) return DSMIL_E_UNSUPPORTED;
+    hipLaunchKernelGGL(k_loss_head_bags, dim3((unsigned)n_bags), dim3(64), 0, (hipStream_t)stream, classes, offsets, pred, idx,
+                       labels, C, loss, max_pred, g_pred, g_max);
+    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 
 int dsmil_adam_step(int32_t n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,

@@ -1,0 +1,398 @@
+// agg_bwd_bags.h — the aggregator backward over a BATCH of bags stored back to back (dsmil_agg_backward_bags) and the
+// batched loss head (dsmil_agg_loss_head_bags).  Included from agg_bwd.hip, behind the one-bag kernels it builds on.
+//
+// What train_tcga.py:60-73 does for one bag, applied to n_bags bags with ONE summed gradient (minibatch training; the
+// reference steps once per bag).  Every per-ROW kernel of the one-bag backward already only knows rows: k_bwd_gh,
+// k_tn_split, k_tn_small, k_bwd_reduce's fixed-order sums run over total_rows unchanged, so the contraction over the
+// instances sums over the whole batch in one pass.  What is per BAG gets a batched form here:
+//   k_bags_rowbag     rowbag[n] = the bag of row n (binary search of the offsets, once per call)
+//   k_bags_prep       one workgroup per bag: gB[b], D[b,c] — k_bwd_prep's block 0, bag by bag
+//   k_bags_ga         gA[n,:] = V[n,:] gB[bag(n)]^T — k_fc's row product with the row's own weights
+//   k_bags_qrow       q_max[b,c] = q(x[offsets[b] + idx[b,c]]): qrow_body, one workgroup per (bag, class)
+//   k_bwd_rows<.., BAGS> / k_bwd_rows_hs<BAGS>   the one-bag tile kernels over a 1-D grid of tile SLOTS (slot_owner,
+//                     agg_bwd.hip: the real tiles of a ragged batch plus at most one idle slot per bag); a tile never spans
+//                     two bags, reads its bag's q_max and D and writes gs, gz2, H, Q, gqp at batch row positions
+//   k_bags_critical   one workgroup per bag: critical_body on the bag's own slice — it sums only its bag's gqp tiles and
+//                     touches only rows offsets[b] + idx[b,c] of gz2
+//   k_bags_head       fixed-order sums over the bags: g_fcc_w, g_fcc_b and the sparse FCLayer term (n_bags * C critical rows)
+//   k_bags_gvals      g_vals[n,:] = A[n,:] gB[bag(n)]
+//   k_bags_gx         (agg_gx.h) gx_tile with the row's own gB / idx / g_max in the tail
+// Launch boundaries order the steps; no atomics, no hand-offs inside a launch, every sum in a fixed order: two runs give the
+// same bits, and a batch of ONE bag gives the bits of dsmil_agg_backward_rows (same arithmetic per element, same tile regime).
+//
+// Tile regime (from total_rows alone, so that it is the one-bag rule at n_bags = 1): total_rows / 128 >= 512 -> the four-wave
+// 128-row tile (k_bwd_rows<4,*>, k_bwd_gh<4>); fewer rows -> the hidden-split 64-row tile (k_bwd_rows_hs, k_bwd_gh_hs), or
+// the one-wave register-staged tile when the rows are not 16-B aligned (K % 4 != 0).  n_bags only adds idle slots.
+#pragma once
+
+namespace {
+
+// the largest batch dsmil_agg_backward_bags accepts: every grid of the call (tile slots, 4-element groups of g_vals, the
+// 128 x 64 tiles of g_feats) then fits 2^31 - 1 workgroups for K, Kv <= 8192, and R, S of k_tn_split stay ints
+constexpr long long BAGS_MAX_ROWS = 1LL << 30;
+
+__global__ __launch_bounds__(256) void k_bags_rowbag(const int64_t* __restrict__ offsets, int n_bags, long long T,
+                                                     int* __restrict__ rowbag) {
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= T) return;
+    int lo = 0, hi = n_bags;           // invariant: offsets[lo] <= r < offsets[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((long long)offsets[mid] <= r) lo = mid; else hi = mid;
+    }
+    rowbag[r] = lo;
+}
+
+// one workgroup per bag: k_bwd_prep's block 0 (the same sums in the same order)
+__global__ __launch_bounds__(256) void k_bags_prep(
+    const float* __restrict__ fcc_w, const float* __restrict__ Bm, const float* __restrict__ g_pred,
+    const float* __restrict__ g_B, const float* __restrict__ A, const float* __restrict__ g_A,
+    const int64_t* __restrict__ offsets, float* __restrict__ gB, float* __restrict__ Dv, float* __restrict__ zero128,
+    int Kv, int C) {
+    __shared__ float red[4];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const long long off0 = offsets[b], N = offsets[b + 1] - off0;
+    const long long bk = (long long)b * C * Kv;
+    const float* gp = g_pred + (long long)b * C;
+    for (int c = 0; c < C; ++c) {
+        float dpart = 0.f;
+        for (int k = tid; k < Kv; k += 256) {
+            float g = g_B ? g_B[bk + c * Kv + k] : 0.f;
+            for (int o = 0; o < C; ++o) g = fmaf(gp[o], fcc_w[((long long)o * C + c) * Kv + k], g);
+            gB[bk + c * Kv + k] = g;
+            dpart = fmaf(g, Bm[bk + c * Kv + k], dpart);
+        }
+        if (g_A)
+            for (long long n = tid; n < N; n += 256) dpart = fmaf(A[(off0 + n) * C + c], g_A[(off0 + n) * C + c], dpart);
+        const float d = block_sum_256(dpart, red);
+        if (tid == 0) Dv[(long long)b * C + c] = d;
+    }
+    if (b == 0 && tid < QD) zero128[tid] = 0.f;
+}
+
+// gA[n,c] = <V[n,:], gB[bag(n),c,:]>: agg_fwd.hip k_fc with the row's own weights (b := 0)
+template <int VEC>
+__global__ __launch_bounds__(256) void k_bags_ga(const float* __restrict__ vals, const float* __restrict__ gB,
+                                                 const int* __restrict__ rowbag, float* __restrict__ gA, long long N, int Kv,
+                                                 int C, const int64_t* __restrict__ rowmap) {
+    const int lane = threadIdx.x & 63;
+    const long long wid = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long nw = (long long)gridDim.x * 4;
+    for (long long r = wid; r < N; r += nw) {
+        const float* x = vals + phys_row(rowmap, r) * Kv;
+        const float* w = gB + (long long)rowbag[r] * C * Kv;
+        for (int c = 0; c < C; ++c) {
+            float acc = 0.f;
+            for (int k0 = 0; k0 < Kv; k0 += 256) {
+                const int k = k0 + lane * 4;
+                const f32x4 xv = load4<VEC>(x, k, Kv);
+                const f32x4 wv = load4<VEC>(w + (long long)c * Kv, k, Kv);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc = fmaf(xv[e], wv[e], acc);
+            }
+            acc = wave_sum(acc) + 0.f;
+            if (lane == 0) gA[r * C + c] = acc;
+        }
+    }
+}
+
+// one workgroup per (bag, class)
+template <int VEC>
+__global__ __launch_bounds__(256) void k_bags_qrow(
+    const float* __restrict__ feats, const int64_t* __restrict__ offsets, const int64_t* __restrict__ idx,
+    const float* __restrict__ q0_w, const float* __restrict__ q0_b, const float* __restrict__ q2_w,
+    const float* __restrict__ q2_b, float* __restrict__ qmax, int K, int C, int nonlinear, const int64_t* __restrict__ rowmap) {
+    const long long bc = blockIdx.x;
+    const long long row = (long long)offsets[bc / C] + (long long)idx[bc];
+    qrow_body<VEC>(feats + phys_row(rowmap, row) * (long long)K, q0_w, q0_b, q2_w, q2_b, qmax + bc * QD, K, nonlinear);
+}
+
+// one workgroup per bag; its slice of gqp starts at the bag's first 32-row tile slot (k_bwd_rows: offsets[b] / 32 + b)
+__global__ __launch_bounds__(1024) void k_bags_critical(const int64_t* __restrict__ offsets, const int64_t* __restrict__ idx,
+                                                        const float* __restrict__ gqp, const float* __restrict__ Qbuf,
+                                                        float* __restrict__ gz2, float* __restrict__ gq, int C, int nonlinear) {
+    const int b = blockIdx.x;
+    const long long off0 = offsets[b], Nb = offsets[b + 1] - off0;
+    critical_body(idx + (long long)b * C, gqp + (off0 / 32 + b) * C * QD, Qbuf + off0 * QD, gz2 + off0 * QD,
+                  gq + (long long)b * C * QD, (Nb + 31) / 32, C, nonlinear);
+}
+
+// Sums over the bags, bag 0 first (a lone bag: k_bwd_prep's / k_bwd_reduce's values as they are):
+//   g_fc_w[c,k] (+)= sum_b g_max[b,c] x[offsets[b] + idx[b,c], k],  g_fc_b[c] (+)= sum_b g_max[b,c]      (g_max != null)
+//   g_fcc_w[o,c,k] = sum_b g_pred[b,o] B[b,c,k],                    g_fcc_b[o] = sum_b g_pred[b,o]
+struct BagsHeadArgs {
+    const float* feats; const int64_t* offsets; const int64_t* idx; const float* g_max; const int64_t* rowmap;
+    float* g_fc_w; float* g_fc_b;
+    const float* g_pred; const float* Bm; float* g_fcc_w; float* g_fcc_b;
+    int n_bags, K, Kv, C, accumulate;
+};
+__global__ __launch_bounds__(256) void k_bags_head(BagsHeadArgs a) {
+    const int C = a.C;
+    const long long nf = a.g_max ? (long long)C * a.K + C : 0, nw = (long long)C * C * a.Kv;
+    long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < nf) {
+        if (i < (long long)C * a.K) {
+            const int c = (int)(i / a.K), k = (int)(i - (long long)c * a.K);
+            const float v = a.g_max[c] * a.feats[phys_row(a.rowmap, a.idx[c]) * (long long)a.K + k];   // bag 0: offsets[0] == 0
+            float g = a.accumulate ? a.g_fc_w[i] + v : v;
+            for (int b = 1; b < a.n_bags; ++b) {
+                const long long row = (long long)a.offsets[b] + (long long)a.idx[(long long)b * C + c];
+                g += a.g_max[(long long)b * C + c] * a.feats[phys_row(a.rowmap, row) * (long long)a.K + k];
+            }
+            a.g_fc_w[i] = g;
+        } else {
+            const int c = (int)(i - (long long)C * a.K);
+            float g = a.accumulate ? a.g_fc_b[c] + a.g_max[c] : a.g_max[c];
+            for (int b = 1; b < a.n_bags; ++b) g += a.g_max[(long long)b * C + c];
+            a.g_fc_b[c] = g;
+        }
+        return;
+    }
+    i -= nf;
+    if (i < nw) {
+        const long long ck = (long long)C * a.Kv;
+        const int o = (int)(i / ck);
+        const long long e = i - (long long)o * ck;
+        float g = a.g_pred[o] * a.Bm[e];
+        for (int b = 1; b < a.n_bags; ++b) g += a.g_pred[(long long)b * C + o] * a.Bm[(long long)b * ck + e];
+        a.g_fcc_w[i] = g;
+        return;
+    }
+    i -= nw;
+    if (i < C) {
+        float g = a.g_pred[i];
+        for (int b = 1; b < a.n_bags; ++b) g += a.g_pred[(long long)b * C + i];
+        a.g_fcc_b[i] = g;
+    }
+}
+
+// g_vals[n][k] = sum_c A[n][c] gB[bag(n)][c][k]
+template <int VEC>
+__global__ void k_bags_gvals(const float* __restrict__ A, const float* __restrict__ gB, const int* __restrict__ rowbag,
+                             float* __restrict__ gv, long long N, int Kv, int C) {
+    const int k4n = (Kv + 3) / 4;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N * k4n) return;
+    const long long n = i / k4n;
+    const int k = (int)(i - n * k4n) * 4;
+    const float* gb = gB + (long long)rowbag[n] * C * Kv;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < C; ++c) acc += A[n * C + c] * load4<VEC, float>(gb + (long long)c * Kv, k, Kv);
+    if constexpr (VEC == 4) {
+        *reinterpret_cast<f32x4*>(gv + n * Kv + k) = acc;
+    } else {
+        for (int e = 0; e < 4; ++e)
+            if (k + e < Kv) gv[n * Kv + k + e] = acc[e];
+    }
+}
+
+// the training objective of every bag of a batch: k_loss_head (agg_fwd.hip), one wave per bag
+__global__ __launch_bounds__(64) void k_loss_head_bags(const float* __restrict__ classes, const int64_t* __restrict__ offsets,
+                                                       const float* __restrict__ pred, const int64_t* __restrict__ idx,
+                                                       const float* __restrict__ label, int C, float* __restrict__ loss,
+                                                       float* __restrict__ max_pred, float* __restrict__ g_pred,
+                                                       float* __restrict__ g_max) {
+    const int c = threadIdx.x, b = blockIdx.x;
+    const long long bc = (long long)b * C + c;
+    float l = 0.f;
+    if (c < C) {
+        const float y = label[bc];
+        const float zb = pred[bc], zm = classes[((long long)offsets[b] + (long long)idx[bc]) * C + c];
+        // BCEWithLogits(z, y) = max(z,0) - z y + log1p(exp(-|z|))  (torch's stable form)
+        const float lb = fmaxf(zb, 0.f) - zb * y + log1pf(expf(-fabsf(zb)));
+        const float lm = fmaxf(zm, 0.f) - zm * y + log1pf(expf(-fabsf(zm)));
+        l = 0.5f * (lb + lm) / (float)C;
+        const float sb = 1.f / (1.f + expf(-zb)), sm = 1.f / (1.f + expf(-zm));
+        if (max_pred) max_pred[bc] = zm;
+        if (g_pred) g_pred[bc] = 0.5f * (sb - y) / (float)C;
+        if (g_max) g_max[bc] = 0.5f * (sm - y) / (float)C;
+    }
+    l = wave_sum(l);   // C <= 64: one wave
+    if (threadIdx.x == 0) loss[b] = l;
+}
+
+// workspace: the one-bag layout over total_rows with one gB / D / q_max / g_q set per bag, the idle tile slots in gqp,
+// and the row -> bag table
+struct BagsWs {
+    size_t gB, Dv, zero, qmax, gq, gA, gs, gz2, Hb, Qb, gH, gqp, wsplit, w2t, part0, part1, pb0, pb1, part, part_b, off, rowbag, total;
+    int splits, S, R, nx;
+};
+BagsWs bags_layout(int n_bags, long long T, int K, int Kv, int C, int nonlinear) {
+    const BwdWs one = bwd_layout(T, K, Kv, C, nonlinear);   // R, S of k_tn_split and k_tn_small's row ranges: from total_rows
+    BagsWs w;
+    w.splits = one.splits; w.S = one.S; w.R = one.R; w.nx = one.nx;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t p = o; o = al(o + bytes); return p; };
+    w.gB = take((size_t)n_bags * C * Kv * 4);
+    w.Dv = take((size_t)n_bags * C * 4);
+    w.zero = take(QD * 4);
+    w.qmax = take((size_t)n_bags * C * QD * 4);
+    w.gq = take((size_t)n_bags * C * QD * 4);
+    w.gA = take((size_t)T * C * 4);
+    w.gs = take((size_t)T * C * 4);
+    w.gz2 = take((size_t)T * QD * 4);
+    w.Hb = take((size_t)T * QD * 4);
+    w.Qb = take((size_t)T * QD * 4);
+    w.gH = take((size_t)T * QD * 4);
+    w.gqp = take((size_t)(T / 32 + n_bags + 1) * C * QD * 4);
+    w.wsplit = take((size_t)(2 * ((K + 31) / 32) + 8) * S3_CHUNK_F4 * 16);
+    w.w2t = take((size_t)8 * S3_CHUNK_F4 * 16);
+    w.part0 = take((size_t)w.S * QD * K * 4);
+    w.part1 = take((size_t)w.S * QD * QD * 4);
+    w.pb0 = take((size_t)w.S * QD * 4);
+    w.pb1 = take((size_t)w.S * QD * 4);
+    w.part = take((size_t)w.splits * (C > 4 ? C : 4) * (K > QD ? K : QD) * 4);
+    w.part_b = take((size_t)w.splits * QD * 4);
+    w.off = take(2 * sizeof(int64_t));
+    w.rowbag = take((size_t)T * 4);
+    w.total = o;
+    return w;
+}
+
+int agg_backward_bags_impl(const float* feats, const float* vals, const int64_t* offsets, int32_t n_bags, int64_t T,
+                           int64_t max_rows, const dsmil_agg_params* p, const float* A, const float* Bm, const int64_t* idx,
+                           const float* g_classes, const float* g_max, const float* g_pred, const float* g_A,
+                           const float* g_B, const dsmil_agg_grads* g, float* g_vals, const int64_t* rowmap, void* ws,
+                           size_t ws_bytes, void* stream, float* g_feats) {
+    // the checks of agg_backward_impl, in its order
+    if (!feats || !offsets || !p || !A || !Bm || !idx || !g_pred || !g || !ws) return DSMIL_E_INVALID;
+    if (g_max && (!g->fc_w || !g->fc_b)) return DSMIL_E_INVALID;
+    if (n_bags < 1 || T < n_bags || max_rows < 1 || max_rows > T || p->K <= 0 || p->Kv <= 0 || p->C <= 0) return DSMIL_E_INVALID;
+    if (!p->q0_w || !p->q0_b || !p->fcc_w || (p->nonlinear && (!p->q2_w || !p->q2_b))) return DSMIL_E_INVALID;
+    if (!g->q0_w || !g->q0_b || !g->fcc_w || !g->fcc_b || (p->nonlinear && (!g->q2_w || !g->q2_b))) return DSMIL_E_INVALID;
+    if (g_classes && (!g->fc_w || !g->fc_b)) return DSMIL_E_INVALID;
+    if (g_feats && (g_classes || g_max) && !p->fc_w) return DSMIL_E_INVALID;
+    if (!vals) vals = feats;
+    if (vals == feats && p->Kv != p->K) return DSMIL_E_INVALID;
+    if (T > BAGS_MAX_ROWS) return DSMIL_E_UNSUPPORTED;
+    if (((uintptr_t)ws % 256) || ((uintptr_t)p->q0_b % 16) || (p->nonlinear && ((uintptr_t)p->q2_b % 16))) return DSMIL_E_ALIGN;
+    const int K = p->K, Kv = p->Kv, C = p->C;
+    const BagsWs L = bags_layout(n_bags, T, K, Kv, C, p->nonlinear);
+    if (ws_bytes < L.total) return DSMIL_E_WORKSPACE;
+    const long long n4 = (long long)T * ((Kv + 3) / 4);
+    if ((n4 + 255) / 256 > 0x7fffffffLL || (long long)C * n_bags > 0x7fffffffLL) return DSMIL_E_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    char* w8 = (char*)ws;
+    float* gB = (float*)(w8 + L.gB); float* Dv = (float*)(w8 + L.Dv); float* zero = (float*)(w8 + L.zero);
+    float* qmax = (float*)(w8 + L.qmax); float* gq = (float*)(w8 + L.gq);
+    float* gA = (float*)(w8 + L.gA); float* gs = (float*)(w8 + L.gs); float* gz2 = (float*)(w8 + L.gz2);
+    float* Hb = (float*)(w8 + L.Hb); float* Qb = (float*)(w8 + L.Qb); float* gH = (float*)(w8 + L.gH);
+    float* gqp = (float*)(w8 + L.gqp);
+    bf16_t* wsplit = (bf16_t*)(w8 + L.wsplit); bf16_t* w2t = (bf16_t*)(w8 + L.w2t);
+    float* part0 = (float*)(w8 + L.part0); float* part1 = (float*)(w8 + L.part1);
+    float* pb0 = (float*)(w8 + L.pb0); float* pb1 = (float*)(w8 + L.pb1);
+    float* part = (float*)(w8 + L.part); float* part_b = (float*)(w8 + L.part_b);
+    int64_t* off1 = (int64_t*)(w8 + L.off);      // {0, total_rows}: the batch as one run of rows (k_bwd_gh)
+    int* rowbag = (int*)(w8 + L.rowbag);
+    const bool v4 = (K % 4 == 0) && (((uintptr_t)feats) % 16 == 0);
+    const bool w4 = (K % 4 == 0) && (((uintptr_t)feats | (uintptr_t)p->q0_w) % 16 == 0);
+    const bool v4v = (Kv % 4 == 0) && ((uintptr_t)vals % 16 == 0);
+    int rc;
+    // 0. plane-cut weights W1 | W2 and W2^T, the {0, total_rows} offsets; the row -> bag table
+    const int nks = 2 * ((K + 31) / 32);
+    hipLaunchKernelGGL(k_train_prologue, dim3(240), dim3(256), 0, st, p->q0_w, p->nonlinear ? p->q2_w : nullptr, wsplit, w2t, K, nks,
+                       off1, off1, (long long)T);
+    hipLaunchKernelGGL(k_bags_rowbag, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, offsets, n_bags, (long long)T, rowbag);
+    // 1. heads: gB, D per bag
+    hipLaunchKernelGGL(k_bags_prep, dim3((unsigned)n_bags), dim3(256), 0, st, p->fcc_w, Bm, g_pred, g_B, A, g_A, offsets, gB, Dv, zero, Kv, C);
+    if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    // 2. gA = V gB[bag]^T
+    {
+        long long blocks = ((long long)T + 3) / 4;
+        if (blocks > 4096) blocks = 4096;
+        if (v4v) hipLaunchKernelGGL(k_bags_ga<4>, dim3((unsigned)blocks), dim3(256), 0, st, vals, gB, rowbag, gA, (long long)T, Kv, C, rowmap);
+        else hipLaunchKernelGGL(k_bags_ga<1>, dim3((unsigned)blocks), dim3(256), 0, st, vals, gB, rowbag, gA, (long long)T, Kv, C, rowmap);
+    }
+    // 3. critical queries
+    if (w4) hipLaunchKernelGGL(k_bags_qrow<4>, dim3((unsigned)(C * n_bags)), dim3(256), 0, st, feats, offsets, idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, K, C, p->nonlinear, rowmap);
+    else hipLaunchKernelGGL(k_bags_qrow<1>, dim3((unsigned)(C * n_bags)), dim3(256), 0, st, feats, offsets, idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, K, C, p->nonlinear, rowmap);
+    if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    // 4. per-row part on MFMA, a 1-D grid of tile slots
+    const int nw = (T / 128 >= 512) ? 4 : 1;
+    BwdRowsArgs br{};
+    br.at = AttendArgs{feats, feats, wsplit, offsets, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, nullptr, nullptr, nullptr,
+                       K, K, C, p->nonlinear, 0, 0, rowmap};
+    br.A = A; br.gA = gA; br.g_A = g_A; br.Dv = Dv; br.gs = gs; br.gz2 = gz2; br.Hbuf = Hb; br.Qbuf = Qb; br.gqp = gqp;
+    br.n_bags = n_bags;
+    auto launch_hs = [&](auto kern, const auto& arg, long long blocks) {
+        if (!dsmil_lds::allow((const void*)kern, HS_LDS_BYTES)) return (int)DSMIL_E_LAUNCH;
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(HS_THREADS), HS_LDS_BYTES, st, arg);
+        return hipGetLastError() == hipSuccess ? (int)DSMIL_OK : (int)DSMIL_E_LAUNCH;
+    };
+    if (nw == 4) {
+        const long long slots = T / 128 + n_bags;
+        rc = v4 ? launch_tile_kernel(k_bwd_rows<4, 4, true>, br, 4, true, T, st, slots)
+                : launch_tile_kernel(k_bwd_rows<1, 1, true>, br, 1, false, T, st, T / 32 + n_bags);
+    } else if (v4) rc = launch_hs(k_bwd_rows_hs<true>, br, T / HS_BM + n_bags);
+    else rc = launch_tile_kernel(k_bwd_rows<1, 1, true>, br, 1, false, T, st, T / 32 + n_bags);
+    if (rc) return rc;
+    // 5. gradient of the critical queries joins their rows, bag by bag
+    hipLaunchKernelGGL(k_bags_critical, dim3((unsigned)n_bags), dim3(1024), 0, st, offsets, idx, gqp, Qb, gz2, gq, C, p->nonlinear);
+    if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    TnArgs tn{};
+    tn.X = feats; tn.rowmap = rowmap; tn.N = T; tn.K = K; tn.R = L.R; tn.nx = L.nx;
+    tn.nslab = L.nx + (p->nonlinear ? 2 : 0); tn.S = L.S;
+    tn.part0 = part0; tn.part1 = part1; tn.pb0 = pb0; tn.pb1 = pb1;
+    if (p->nonlinear) {
+        // 6. gH = (gz2 W2) [H > 0] over the rows of the batch
+        GhArgs gh{};
+        gh.at = AttendArgs{gz2, gz2, w2t, off1, nullptr, zero, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           QD, QD, C, 0, 0, 0, nullptr};
+        gh.Hbuf = Hb; gh.gH = gH;
+        rc = (nw == 4) ? launch_tile_kernel(k_bwd_gh<4>, gh, 4, true, T, st) : launch_hs(k_bwd_gh_hs, gh, (T + HS_BM - 1) / HS_BM);
+        if (rc) return rc;
+        tn.A0 = gH; tn.A1 = gz2; tn.Hb = Hb;
+    } else {
+        tn.A0 = gz2; tn.A1 = nullptr; tn.Hb = nullptr;
+    }
+    // 7. weight gradients: the contraction over ALL instance rows of the batch, then the fixed-order reduction
+#ifdef DSMIL_TRACE
+    tn.trace = nullptr;
+#endif
+    {
+        const dim3 gtn((unsigned)(tn.nslab * ((L.S + 7) / 8 * 8)));
+        if (v4 && rowmap) hipLaunchKernelGGL((k_tn_split<true, true>), gtn, dim3(256), 0, st, tn);
+        else if (v4) hipLaunchKernelGGL((k_tn_split<true, false>), gtn, dim3(256), 0, st, tn);
+        else if (rowmap) hipLaunchKernelGGL((k_tn_split<false, true>), gtn, dim3(256), 0, st, tn);
+        else hipLaunchKernelGGL((k_tn_split<false, false>), gtn, dim3(256), 0, st, tn);
+    }
+    if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    // 8. dense instance stream
+    if (g_classes) {
+        rc = tn_small(g_classes, feats, T, C, K, part, part_b, g->fc_w, g->fc_b, L.splits, w4, st, rowmap);
+        if (rc) return rc;
+    }
+    ReduceArgs ra{};
+    ra.part0 = part0; ra.part1 = part1; ra.pb0 = pb0; ra.pb1 = pb1;
+    ra.g_w0 = g->q0_w; ra.g_b0 = g->q0_b; ra.g_w1 = g->q2_w; ra.g_b1 = g->q2_b;
+    ra.S = L.S; ra.K = K; ra.nonlinear = p->nonlinear; ra.C = C;
+    const long long nred = (long long)QD * K + (p->nonlinear ? QD * QD + 2 * QD : QD);
+    hipLaunchKernelGGL(k_bwd_reduce, dim3((unsigned)((nred + 255) / 256)), dim3(256), 0, st, ra);
+    // the sums over the bags: bag head and the sparse FCLayer term
+    BagsHeadArgs ha{feats, offsets, idx, g_max, rowmap, g->fc_w, g->fc_b, g_pred, Bm, g->fcc_w, g->fcc_b, n_bags, K, Kv, C,
+                    g_classes ? 1 : 0};
+    const long long nhead = (g_max ? (long long)C * K + C : 0) + (long long)C * C * Kv + C;
+    hipLaunchKernelGGL(k_bags_head, dim3((unsigned)((nhead + 255) / 256)), dim3(256), 0, st, ha);
+    if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    // 9. gradient of the value rows
+    if (g_vals) {
+        if (v4v && (uintptr_t)g_vals % 16 == 0)
+            hipLaunchKernelGGL(k_bags_gvals<4>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, A, gB, rowbag, g_vals, (long long)T, Kv, C);
+        else
+            hipLaunchKernelGGL(k_bags_gvals<1>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, A, gB, rowbag, g_vals, (long long)T, Kv, C);
+        if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    }
+    // 10. gradient of the input rows
+    if (g_feats) {
+        GxArgs gx{};
+        gx.L = p->nonlinear ? gH : gz2; gx.W = p->q0_w; gx.out = g_feats; gx.N = T; gx.J = QD; gx.K = K; gx.lvec = 1;
+        gx.gc = g_classes; gx.Wf = p->fc_w; gx.A = vals == feats ? A : nullptr; gx.gB = gB; gx.idx = idx; gx.gmax = g_max;
+        gx.C = (g_classes || g_max || vals == feats) ? C : 0;
+        gx.rowbag = rowbag; gx.offsets = offsets;
+        if (!gx_launch<false, true>(gx, st)) return DSMIL_E_UNSUPPORTED;
+        if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    }
+    return DSMIL_OK;
+}
+
+}  // namespace

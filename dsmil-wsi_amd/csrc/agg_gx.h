@@ -51,9 +51,13 @@ struct GxArgs {
     const int64_t* idx;          // [C] critical rows (gmax)
     const float* gmax;           // [C] sparse max-stream gradient, or null
     int C;
+    // BAGS (a batch of bags stored back to back, agg_bwd_bags.h): gB [n_bags, C, K], idx / gmax [n_bags, C] (idx bag-local),
+    // rowbag[n] = the bag of row n, offsets [n_bags + 1]
+    const int* rowbag;
+    const int64_t* offsets;
 };
 
-template <bool MASK>
+template <bool MASK, bool BAGS = false>
 __device__ __forceinline__ void gx_tile(const GxArgs& a) {
     __shared__ __attribute__((aligned(16))) unsigned sA[3 * GX_BM * GX_LDW];
     __shared__ __attribute__((aligned(16))) unsigned sB[3 * GX_BN * GX_LDW];
@@ -175,6 +179,29 @@ __device__ __forceinline__ void gx_tile(const GxArgs& a) {
     const int col = col0 + 32 * ct + l31;
     if (col >= a.K) return;
     const int mb = 64 * up + 4 * hi;
+    if constexpr (BAGS) {
+        // the same tail with the row's OWN bag behind every per-bag operand: per element the classes run in the same order
+        // with the same two FMAs, so a batch of one bag gives the one-bag kernel's bits
+        const bool fcs = a.gc || a.gmax;
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt)
+            for (int r = 0; r < 16; ++r) {
+                long long row = row0 + mb + 32 * tt + (r & 3) + 8 * (r >> 2);
+                row = row < a.N ? row : a.N - 1;
+                const long long bc0 = (long long)a.rowbag[row] * a.C;
+                const long long lrow = row - (long long)a.offsets[a.rowbag[row]];
+                float v = acc[tt][r];
+                for (int c = 0; c < a.C; ++c) {
+                    if (fcs) {
+                        float cf = a.gc ? a.gc[row * a.C + c] : 0.f;
+                        if (a.gmax && lrow == (long long)a.idx[bc0 + c]) cf += a.gmax[bc0 + c];
+                        v = fmaf(cf, a.Wf[(long long)c * a.K + col], v);
+                    }
+                    if (a.A) v = fmaf(a.A[row * a.C + c], a.gB[(bc0 + c) * a.K + col], v);
+                }
+                acc[tt][r] = v;
+            }
+    } else
     for (int c = 0; c < a.C; ++c) {   // the 2C-wide tail, class by class (fixed order)
         const bool fcs = a.gc || a.gmax;
         const float wf = fcs ? a.Wf[(long long)c * a.K + col] : 0.f;
@@ -213,15 +240,17 @@ __device__ __forceinline__ void gx_tile(const GxArgs& a) {
 
 __global__ __launch_bounds__(256, 2) void k_bwd_gx(GxArgs a) { gx_tile<false>(a); }
 __global__ __launch_bounds__(256, 2) void k_value_gx(GxArgs a) { gx_tile<true>(a); }
+__global__ __launch_bounds__(256, 2) void k_bags_gx(GxArgs a) { gx_tile<false, true>(a); }
 
 // fills the grid fields and launches; returns false when the grid does not fit
-template <bool MASK>
+template <bool MASK, bool BAGS = false>
 inline bool gx_launch(GxArgs a, hipStream_t st) {
     a.ntile = (int)((a.N + GX_BM - 1) / GX_BM);
     a.nslab = (a.K + GX_BN - 1) / GX_BN;
     const long long wgs = (long long)a.nslab * ((a.ntile + 7) / 8 * 8);
     if (wgs > 0x7fffffffLL) return false;
-    if constexpr (MASK) hipLaunchKernelGGL(k_value_gx, dim3((unsigned)wgs), dim3(256), 0, st, a);
+    if constexpr (BAGS) hipLaunchKernelGGL(k_bags_gx, dim3((unsigned)wgs), dim3(256), 0, st, a);
+    else if constexpr (MASK) hipLaunchKernelGGL(k_value_gx, dim3((unsigned)wgs), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_bwd_gx, dim3((unsigned)wgs), dim3(256), 0, st, a);
     return true;
 }

@@ -268,6 +268,75 @@ class MILNet(nn.Module):
             o += n
         return out
 
+    # -- minibatches: several bags per call, differentiable ----------------------------------------
+    def _batch_native(self, feats):
+        """Whether a batch of these rows takes the native batched forward + backward (_AggBatchFunction): the conditions
+        of ``forward``'s fused call, plus what dsmil_agg_backward_bags would reject (query biases off 16-byte alignment)."""
+        ic, bc = self.i_classifier, self.b_classifier
+        if not (isinstance(ic, FCLayer) and isinstance(bc, BClassifier)):
+            return False
+        if not (feats.is_cuda and feats.dtype == torch.float32 and feats.dim() == 2):
+            return False
+        w = bc._weights()
+        return all(t is None or t.data_ptr() % 16 == 0 for t in (w["q0_b"], w["q2_b"]))
+
+    def forward_batch(self, feats, lengths):
+        """``forward`` over a batch of bags stored back to back — differentiable, unlike ``forward_bags``.
+
+        feats [sum(lengths), K]; bag b owns rows sum(lengths[:b]) .. + lengths[b].  Returns
+        (classes [T,C], pred [n,C], A [T,C], B [n,C,Kv]): per bag what ``forward`` returns, laid end to end.  CUDA fp32 rows
+        of MILNet(FCLayer, BClassifier): ONE native batched forward and, under autograd, ONE native batched backward
+        (dsmil_agg_backward_bags) whose parameter gradients are summed over the bags; rows that require a gradient get it
+        from the same call; with passing_v the value projection and its backward run once over the concatenated rows.
+        Everything else (CPU tensors, other modules) runs the same mathematics bag by bag through ``forward``."""
+        lengths = [int(n) for n in lengths]
+        if sum(lengths) != feats.shape[0] or any(n <= 0 for n in lengths):
+            raise ValueError(f"bag lengths must be positive and sum to {feats.shape[0]} rows")
+        if self._batch_native(feats):
+            ic, bc = self.i_classifier, self.b_classifier
+            w = bc._weights()
+            lin = ic.fc[0]
+            return _AggBatchFunction.apply(feats, bc._values(feats), tuple(lengths), lin.weight, lin.bias, w["q0_w"],
+                                           w["q0_b"], w["q2_w"], w["q2_b"], w["fcc_w"], w["fcc_b"], bc.nonlinear)[0:4]
+        outs, o = [], 0
+        for n in lengths:
+            classes, pred, A, B = self.forward(feats[o:o + n])
+            outs.append((classes, pred.view(1, -1), A, B.view(1, B.shape[-2], B.shape[-1])))
+            o += n
+        return tuple(torch.cat([t[i] for t in outs], dim=0) for i in range(4))
+
+    def batch_loss(self, feats, lengths, labels, row_map=None, per_bag=False):
+        """The training objective of a BATCH of bags: loss = mean_b loss_b with loss_b the objective of ``bag_loss``
+        (train_tcga.py:64-71) for bag b — one optimiser step per batch is this project's addition, the reference steps once
+        per bag.  ``lengths`` count LOGICAL rows; ``row_map`` (int64 [sum(lengths)]) maps a logical row to a row of feats
+        (every bag's dropout_patches index list with the bag's offset added, concatenated).  labels [n,C].
+        Returns (loss [], pred [n,C], max_pred [n,C]) and, with per_bag, each bag's own loss [n] (detached) as a fourth value.
+        CUDA fp32 rows that need no gradient, v = Identity, C <= 64: one native batched forward + batched loss head, and one
+        native batched backward with the sparse max-stream gradient.  Otherwise the same objective from torch ops around
+        ``forward_batch``."""
+        lengths = [int(n) for n in lengths]
+        n = len(lengths)
+        labels = labels.reshape(n, -1)
+        bc = self.b_classifier
+        if (self._batch_native(feats) and not bc.passing_v and not feats.requires_grad
+                and self.i_classifier.fc[0].out_features <= 64):
+            if row_map is not None and row_map.numel():
+                torch._assert_async((row_map.min() >= 0) & (row_map.max() < feats.shape[0]), "row_map index out of range")
+            w = bc._weights()
+            lin = self.i_classifier.fc[0]
+            loss, pred, mx, each = _BatchLossFunction.apply(feats, labels, row_map, tuple(lengths), lin.weight, lin.bias,
+                                                            w["q0_w"], w["q0_b"], w["q2_w"], w["q2_b"], w["fcc_w"],
+                                                            w["fcc_b"], bc.nonlinear)
+            return (loss, pred, mx, each) if per_bag else (loss, pred, mx)
+        x = feats if row_map is None else feats.index_select(0, row_map)
+        ins, pred, _, _ = self.forward_batch(x, lengths)
+        mx = torch.stack([t.max(0)[0] for t in torch.split(ins, lengths, dim=0)])
+        y = labels.to(pred.dtype)
+        each = 0.5 * F.binary_cross_entropy_with_logits(pred, y, reduction="none").mean(1) + \
+            0.5 * F.binary_cross_entropy_with_logits(mx, y, reduction="none").mean(1)
+        loss = each.mean()
+        return (loss, pred, mx, each.detach()) if per_bag else (loss, pred, mx)
+
 
 # ---------------------------------------------------------------------------------------------
 # autograd glue
@@ -471,3 +540,66 @@ class _AggFunction(torch.autograd.Function):
             g_vals = A.mm(gB)
         return (g_x, g_cin, g_vals, g_fc_w, g_fc_b, g_q0_w, g_q0_b, g_q2_w, g_q2_b,
                 g_fcc_w, g_fcc_b, None)
+
+
+class _AggBatchFunction(torch.autograd.Function):
+    """_AggFunction over a batch of bags stored back to back: forward = dsmil_agg_forward_ex (n_bags bags), backward =
+    dsmil_agg_backward_bags — every parameter gradient summed over the bags in one native call, g_vals for a trainable v and
+    the gradient of the input rows from the same call."""
+
+    @staticmethod
+    def forward(ctx, feats, vals, lengths, fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, nonlinear):
+        det = lambda t: t.detach() if t is not None else None
+        w = {"fc_w": det(fc_w), "fc_b": det(fc_b), "q0_w": det(q0_w), "q0_b": det(q0_b),
+             "q2_w": det(q2_w), "q2_b": det(q2_b), "fcc_w": det(fcc_w), "fcc_b": det(fcc_b)}
+        classes, pred, A, B, idx = ops.agg_forward(feats.detach(), lengths, w, vals=det(vals), nonlinear=nonlinear)
+        ctx.nonlinear, ctx.lengths, ctx.has_vals = nonlinear, lengths, vals is not None
+        ctx.save_for_backward(feats, vals, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx)
+        ctx.mark_non_differentiable(idx)
+        return classes, pred, A, B, idx
+
+    @staticmethod
+    def backward(ctx, g_cls, g_pred, g_A, g_B, _g_idx):
+        feats, vals, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx = ctx.saved_tensors
+        C = fcc_w.shape[0]
+        if g_pred is None:
+            g_pred = torch.zeros((len(ctx.lengths), C), device=feats.device)
+        w = {"fc_w": fc_w, "fc_b": None, "q0_w": q0_w, "q0_b": q0_b, "q2_w": q2_w, "q2_b": q2_b,
+             "fcc_w": fcc_w, "fcc_b": None}
+        want_x = ctx.needs_input_grad[0]
+        same = ctx.has_vals and vals.data_ptr() == feats.data_ptr()
+        want_v = ctx.has_vals and ctx.needs_input_grad[1] and not (want_x and same)
+        g = ops.agg_backward_bags(feats, ctx.lengths, w, A, B, idx, g_pred, g_classes=g_cls, g_A=g_A, g_B=g_B,
+                                  vals=vals if ctx.has_vals else None, nonlinear=ctx.nonlinear, want_g_vals=want_v,
+                                  want_g_feats=want_x)
+        return (g.get("feats"), g.get("vals"), None, g.get("fc_w"), g.get("fc_b"), g["q0_w"], g["q0_b"],
+                g.get("q2_w"), g.get("q2_b"), g["fcc_w"], g["fcc_b"], None)
+
+
+class _BatchLossFunction(torch.autograd.Function):
+    """_BagLossFunction over a batch: forward = the batched dsmil_agg_forward_ex (row map) + dsmil_agg_loss_head_bags,
+    loss = the mean of the bags' losses; backward = dsmil_agg_backward_bags with the sparse max-stream gradient."""
+
+    @staticmethod
+    def forward(ctx, feats, labels, row_map, lengths, fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, nonlinear):
+        det = lambda t: t.detach() if t is not None else None
+        w = {"fc_w": det(fc_w), "fc_b": det(fc_b), "q0_w": det(q0_w), "q0_b": det(q0_b),
+             "q2_w": det(q2_w), "q2_b": det(q2_b), "fcc_w": det(fcc_w), "fcc_b": det(fcc_b)}
+        classes, pred, A, B, idx = ops.agg_forward(feats.detach(), lengths, w, nonlinear=nonlinear, row_map=row_map)
+        each, max_pred, g_pred, g_max = ops.agg_loss_head_bags(classes, lengths, pred, idx, labels.detach())
+        ctx.nonlinear, ctx.lengths = nonlinear, lengths
+        ctx.save_for_backward(feats, row_map, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx, g_pred, g_max)
+        ctx.mark_non_differentiable(pred, max_pred, each)
+        return each.mean(), pred, max_pred, each
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_pred, _g_max, _g_each):
+        feats, row_map, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx, g_pred, g_max = ctx.saved_tensors
+        w = {"fc_w": fc_w, "fc_b": None, "q0_w": q0_w, "q0_b": q0_b, "q2_w": q2_w, "q2_b": q2_b,
+             "fcc_w": fcc_w, "fcc_b": None}
+        # every gradient is linear in (g_pred, g_max); the mean over the bags is a factor 1 / n on each bag's own
+        scale = g_loss / len(ctx.lengths)
+        g = ops.agg_backward_bags(feats, ctx.lengths, w, A, B, idx, g_pred * scale, g_max=g_max * scale, row_map=row_map,
+                                  nonlinear=ctx.nonlinear)
+        return (None, None, None, None, g["fc_w"], g["fc_b"], g["q0_w"], g["q0_b"], g.get("q2_w"), g.get("q2_b"),
+                g["fcc_w"], g["fcc_b"], None)

@@ -615,6 +615,81 @@ def agg_backward(feats, w, A, B, idx, g_pred, g_classes=None, g_A=None, g_B=None
     return out
 
 
+def agg_loss_head_bags(classes, lengths, pred, idx, labels, offsets=None):
+    """dsmil_agg_loss_head_bags: the objective of ``agg_loss_head`` for every bag of a batch stored back to back, one
+    launch.  classes [total,C], pred / idx / labels [n_bags,C] (the batched forward's outputs; labels 0/1).  Returns
+    (loss [n_bags], max_pred [n_bags,C], g_pred [n_bags,C], g_max [n_bags,C]) — the gradients of each bag's OWN loss."""
+    classes = _f32c(classes, "classes")
+    n, C = len(lengths), classes.shape[1]
+    pred = _f32c(pred.reshape(n, C), "pred")
+    labels = _f32c(labels.reshape(n, C).to(torch.float32), "labels")
+    idx = _i64c(idx.reshape(n, C), "idx")
+    dev = classes.device
+    off = offsets if offsets is not None else offsets_tensor(lengths, dev)
+    loss = torch.empty((n,), dtype=torch.float32, device=dev)
+    max_pred, g_pred, g_max = (torch.empty((n, C), dtype=torch.float32, device=dev) for _ in range(3))
+    with torch.cuda.device(dev):
+        rc = _native.lib().dsmil_agg_loss_head_bags(_ptr(classes), _ptr(off), _ptr(pred), _ptr(idx), _ptr(labels), n, C,
+                                                    _ptr(loss), _ptr(max_pred), _ptr(g_pred), _ptr(g_max), _stream(dev))
+    _native.check(rc, "dsmil_agg_loss_head_bags")
+    return loss, max_pred, g_pred, g_max
+
+
+def agg_backward_bags(feats, lengths, w, A, B, idx, g_pred, g_classes=None, g_A=None, g_B=None, vals=None, nonlinear=True,
+                      want_g_vals=False, g_max=None, row_map=None, want_g_feats=False, offsets=None):
+    """dsmil_agg_backward_bags: the backward of ``agg_forward`` over a BATCH of bags stored back to back (minibatch
+    training: one summed gradient over the bags).  ``lengths``: the bags' LOGICAL row counts; A [total,C], B [n,C,Kv],
+    idx [n,C] = the batched forward's outputs; g_pred [n,C], g_max [n,C] or None, g_classes / g_A [total,C], g_B [n,C,Kv]
+    (None = zero).  Returns the dict of ``agg_backward``: every parameter gradient summed over the bags, ``vals`` /
+    ``feats`` (on request) laid end to end in logical row order."""
+    feats = _f32c(feats, "feats")
+    dev = feats.device
+    total, K = feats.shape
+    row_map = _i64c(row_map, "row_map")
+    if row_map is not None:
+        total = int(row_map.numel())
+    lengths = [int(n) for n in lengths]
+    if sum(lengths) != total or any(n <= 0 for n in lengths):
+        raise ValueError(f"bag lengths must be positive and sum to {total}")
+    n = len(lengths)
+    vals = feats if vals is None else _f32c(vals, "vals")
+    Kv = vals.shape[1]
+    fcc_w = _f32c(w["fcc_w"], "fcc_w")
+    C = fcc_w.shape[0]
+    keep = [_f32c(w.get(k), k) for k in ("fc_w", "fc_b", "q0_w", "q0_b", "q2_w", "q2_b", "fcc_w", "fcc_b")]
+    p = _native.AggParams(*[(t.data_ptr() if t is not None else 0) for t in keep], K, Kv, C, 1 if nonlinear else 0)
+    A = _f32c(A, "A"); B = _f32c(B, "B")
+    idx = _i64c(idx.reshape(n, C), "idx")
+    g_pred = _f32c(g_pred.reshape(n, C), "g_pred")
+    g_classes = _f32c(g_classes, "g_classes"); g_A = _f32c(g_A, "g_A"); g_B = _f32c(g_B, "g_B")
+    g_max = _f32c(g_max.reshape(n, C), "g_max") if g_max is not None else None
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    out = {"q0_w": new(Q_DIM, K), "q0_b": new(Q_DIM), "fcc_w": new(C, C, Kv), "fcc_b": new(C)}
+    if nonlinear:
+        out["q2_w"], out["q2_b"] = new(Q_DIM, Q_DIM), new(Q_DIM)
+    if g_classes is not None or g_max is not None:
+        out["fc_w"], out["fc_b"] = new(C, K), new(C)
+    g = _native.AggGrads(*[(out[k].data_ptr() if k in out else 0)
+                           for k in ("fc_w", "fc_b", "q0_w", "q0_b", "q2_w", "q2_b", "fcc_w", "fcc_b")])
+    g_vals = new(total, Kv) if want_g_vals else None
+    g_feats = new(total, K) if want_g_feats else None
+    off = offsets if offsets is not None else offsets_tensor(lengths, dev)
+    L = _native.lib()
+    ws = _workspace(dev, L.dsmil_agg_backward_bags_workspace_bytes(n, total, K, Kv, C))
+    with torch.cuda.device(dev):
+        rc = L.dsmil_agg_backward_bags(_ptr(feats), _ptr(vals), _ptr(off), n, total, max(lengths), ctypes.byref(p), _ptr(A),
+                                       _ptr(B), _ptr(idx), _ptr(g_classes), _ptr(g_max), _ptr(g_pred), _ptr(g_A), _ptr(g_B),
+                                       ctypes.byref(g), _ptr(g_vals), _ptr(row_map), _ptr(ws), ws.numel(), _stream(dev),
+                                       _ptr(g_feats))
+    _native.check(rc, "dsmil_agg_backward_bags")
+    del keep
+    if want_g_feats:
+        out["feats"] = g_feats
+    if want_g_vals:
+        out["vals"] = g_vals
+    return out
+
+
 def agg_train_step(feats, label, params, exp_avg, exp_avg_sq, step, lr, betas, eps, weight_decay, nonlinear=True,
                    row_map=None, loss_out=None):
     """dsmil_agg_train_step: one train_tcga.py:60-75 step (forward, 0.5 BCE(bag) + 0.5 BCE(max instance), backward,

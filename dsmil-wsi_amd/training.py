@@ -117,6 +117,21 @@ def bag_loss(milnet, criterion, bag_feats, bag_label, row_map=None):
     return loss, bag_prediction, max_prediction
 
 
+def batch_loss(milnet, criterion, feats, lengths, labels, row_map=None):
+    """The objective of a group of bags stored back to back (``bags_per_step`` > 1): mean over the bags of ``bag_loss``'s
+    objective.  Returns (loss, pred [n,C], max_pred [n,C], each bag's own loss [n], detached).  Stock criterion and a model
+    with ``batch_loss``: MILNet.batch_loss (native on the GPU); otherwise the same expression from torch ops, bag by bag."""
+    if _is_plain_bce(criterion) and hasattr(milnet, "batch_loss"):
+        return milnet.batch_loss(feats, lengths, labels, row_map, per_bag=True)
+    x = feats if row_map is None else feats.index_select(0, row_map)
+    each, preds, maxes = [], [], []
+    for bag, label in zip(torch.split(x, [int(n) for n in lengths], dim=0), labels.reshape(len(lengths), -1)):
+        loss, bag_prediction, max_prediction = bag_loss(milnet, criterion, bag, label)
+        each.append(loss); preds.append(bag_prediction.view(1, -1)); maxes.append(max_prediction.view(1, -1))
+    each = torch.stack(each)
+    return each.mean(), torch.cat(preds), torch.cat(maxes), each.detach()
+
+
 class FusedTrainStep:
     """train_tcga.py:60-75 as ONE native call per bag (dsmil_agg_train_step): forward, the two-BCE objective, backward and
     the Adam update of all parameter tensors are enqueued by a single C call — the Python side of a step is that call plus
@@ -236,6 +251,35 @@ class LossReadback:
         self.n += 1
         return prev
 
+    def push_many(self, losses):
+        """The same hand-over for a 1-D tensor (the per-bag losses of one minibatch step): returns the previous call's
+        values as a list of floats (None on the first call)."""
+        if not self.cuda:
+            prev, self.pending = self.pending, [float(v) for v in losses.detach()]
+            return prev
+        if not hasattr(self, "many"):
+            self.many, self.many_ev, self.many_n = [None, None], [torch.cuda.Event(), torch.cuda.Event()], 0
+        k = self.many_n & 1
+        self.many[k] = torch.empty(losses.numel(), dtype=torch.float32, pin_memory=True)
+        self.many[k].copy_(losses.detach().reshape(-1), non_blocking=True)
+        self.many_ev[k].record()
+        prev = None
+        if self.many_n > 0:
+            self.many_ev[k ^ 1].synchronize()
+            prev = self.many[k ^ 1].tolist()
+        self.many_n += 1
+        return prev
+
+    def flush_many(self):
+        if not self.cuda:
+            prev, self.pending = self.pending, None
+            return prev
+        if not getattr(self, "many_n", 0):
+            return None
+        k = (self.many_n - 1) & 1
+        self.many_ev[k].synchronize()
+        return self.many[k].tolist()
+
     def flush(self):
         if not self.cuda:
             prev, self.pending = self.pending, None
@@ -247,14 +291,56 @@ class LossReadback:
         return float(self.buf[k])
 
 
+def _train_groups(args, dirs, milnet, criterion, optimizer, cache, log, per_step):
+    """``train`` with ``bags_per_step`` > 1: consecutive bags of the shuffled order, per_step at a time (the last group may
+    be short), ONE summed objective (batch_loss: the mean of the bags' losses), one backward and one optimizer.step() per
+    group.  This is minibatch training — a different optimisation schedule from the reference's one step per bag."""
+    device = next(milnet.parameters()).device
+    readback = LossReadback(device)
+    losses, done = [], 0
+
+    def report(vals):
+        nonlocal done
+        for v in vals or ():
+            sys.stdout.write("\r Training bag [%d/%d] bag loss: %.4f" % (done, len(dirs), v))
+            done += 1
+    try:
+        for g0 in range(0, len(dirs), per_step):
+            bags, labels, maps, off, any_map = [], [], [], 0, False
+            for item in dirs[g0:g0 + per_step]:
+                bag_feats, bag_label = cache.get(item, args.feats_size)
+                rows = dropout_rows(bag_feats.size(0), 1 - args.dropout_patch, bag_feats.device)
+                any_map = any_map or rows is not None
+                maps.append((rows if rows is not None else torch.arange(bag_feats.size(0), device=bag_feats.device)) + off)
+                off += bag_feats.size(0)
+                bags.append(bag_feats); labels.append(bag_label.reshape(1, -1))
+            feats = torch.cat(bags, dim=0) if len(bags) > 1 else bags[0]
+            optimizer.zero_grad()
+            loss, _, _, each = batch_loss(milnet, criterion, feats, [int(m.numel()) for m in maps], torch.cat(labels),
+                                          torch.cat(maps) if any_map else None)
+            loss.backward()
+            optimizer.step()
+            losses.append(each)
+            if log:   # every bag's own loss, one step late
+                report(readback.push_many(each))
+    finally:
+        if log and dirs:
+            report(readback.flush_many())
+    return float(torch.cat(losses).sum().item()) / max(1, len(dirs)) if losses else 0.0
+
+
 def train(args, train_df, milnet, criterion, optimizer, cache=None, log=True):
-    """train_tcga.py:55-76: one optimiser step per bag, bags in random order."""
+    """train_tcga.py:55-76: one optimiser step per bag, bags in random order.  ``args.bags_per_step`` > 1 (not in the
+    reference): one step per group of that many bags instead (_train_groups)."""
     from sklearn.utils import shuffle
     milnet.train()
     device = next(milnet.parameters()).device
     cache = cache or BagCache(device)
     total_loss = 0.0
     dirs = shuffle(list(train_df))
+    per_step = int(getattr(args, "bags_per_step", 1) or 1)
+    if per_step > 1:
+        return _train_groups(args, dirs, milnet, criterion, optimizer, cache, log, per_step)
     losses = []
     # the whole step as one native call when the model / criterion / optimiser are the reference's (FusedTrainStep)
     fused = FusedTrainStep.create(milnet, criterion, optimizer) if getattr(args, "fused_step", True) else None

@@ -277,6 +277,40 @@ int dsmil_agg_backward_rows(const float* feats, const float* vals, int64_t N, co
                             const dsmil_agg_grads* g, float* g_vals, const int64_t* row_map, void* ws,
                             size_t ws_bytes, void* stream, float* g_feats);
 
+/* ---- aggregator backward over a BATCH of bags (minibatch training) -------------------------------------------------
+ * Replaces what autograd derives for `loss.backward()` in train_tcga.py:60-73 applied to SEVERAL bags whose losses are
+ * summed before one optimizer.step() (the reference steps once per bag, train_tcga.py:73; a batch is this project's
+ * addition): bag b owns rows offsets[b]..offsets[b+1]-1 of the batch, exactly as in dsmil_agg_forward_ex, and
+ * `A`, `B`, `idx` are that call's outputs for the same batch.
+ *   g_pred [n_bags, C], g_max [n_bags, C] or NULL (sparse: touches row offsets[b] + idx[b,c]), g_classes [total_rows, C],
+ *   g_A [total_rows, C], g_B [n_bags, C, Kv] (each NULL = zero): the upstream gradients
+ *   g       every parameter gradient = the SUM over the bags of what dsmil_agg_backward_rows gives for bag b alone (the
+ *           arg-max indices are constants), OVERWRITTEN; the NULL rules of dsmil_agg_backward_rows
+ *   g_vals [total_rows, Kv], g_feats [total_rows, K] (each NULL to skip): the per-bag results laid end to end
+ *   row_map int64 [total_rows] or NULL, as in dsmil_agg_opts; the per-row inputs and outputs are in LOGICAL order
+ *   max_rows  the largest bag length (host value, 1 <= max_rows <= total_rows; the launch grids are sized by the real
+ *           tiles of the batch, not by it)
+ * Checks run in the order of dsmil_agg_backward_rows — DSMIL_E_INVALID (NULL offsets, n_bags < 1, total_rows < n_bags
+ * included), then DSMIL_E_ALIGN, then DSMIL_E_WORKSPACE — all before any launch; total_rows > 2^30 -> DSMIL_E_UNSUPPORTED
+ * (behind the INVALID checks).  Every bag has at least one row.  The call allocates nothing, never synchronises, uses no
+ * atomics and sums in a fixed order (bags in order, then k_tn_split's row ranges in order): two runs give the same bits,
+ * and a batch of one bag gives the bits of dsmil_agg_backward_rows.  Any C >= 1, any K (K % 4 != 0 takes the
+ * register-staged tile).  csrc/agg_bwd_bags.h.
+ * dsmil_agg_loss_head_bags: the objective of dsmil_agg_loss_head (train_tcga.py:67-71) for every bag of the batch in one
+ * launch: labels [n_bags, C] -> loss [n_bags], max_pred / g_pred / g_max [n_bags, C] (each may be NULL except loss); the
+ * gradients are those of each bag's OWN loss (the caller scales them, e.g. by 1 / n_bags for a mean).  C <= 64.
+ * Added without a change of DSMIL_ABI_VERSION (it stays 6): detected by SYMBOL, like dsmil_agg_backward_rows. */
+size_t dsmil_agg_backward_bags_workspace_bytes(int32_t n_bags, int64_t total_rows, int32_t K, int32_t Kv, int32_t C);
+int dsmil_agg_backward_bags(const float* feats, const float* vals, const int64_t* offsets, int32_t n_bags,
+                            int64_t total_rows, int64_t max_rows, const dsmil_agg_params* p, const float* A,
+                            const float* B, const int64_t* idx, const float* g_classes, const float* g_max,
+                            const float* g_pred, const float* g_A, const float* g_B, const dsmil_agg_grads* g,
+                            float* g_vals, const int64_t* row_map, void* ws, size_t ws_bytes, void* stream,
+                            float* g_feats);
+int dsmil_agg_loss_head_bags(const float* classes, const int64_t* offsets, const float* pred, const int64_t* idx,
+                             const float* labels, int32_t n_bags, int32_t C, float* loss, float* max_pred,
+                             float* g_pred, float* g_max, void* stream);
+
 /* ---- the value stream of BClassifier(passing_v=True) (ABI 6) ---------------------------------------------------------
  * Replaces `V = self.v(feats)` of dsmil.py:48 with self.v = Sequential(Dropout, Linear(K, K), ReLU) (dsmil.py:35-39; the
  * dropout is the caller's: it hands in the rows it wants projected):  V[n, j] = max(0, sum_k feats[n, k] v_w[j, k] + v_b[j]),

@@ -27,6 +27,9 @@ def build_parser():
     p.add_argument("--average", type=bool, default=False, help="Average max-pooling and bag scores")
     p.add_argument("--eval_scheme", default="5-fold-cv", type=str,
                    help="[5-fold-cv | 5-fold-cv-standalone-test | 5-time-train+valid+test ]")
+    p.add_argument("--bags_per_step", default=1, type=int,
+                   help="Bags per optimiser step [1]; NOT a flag of the reference's train_tcga.py, which steps once per bag: "
+                        "with N > 1 the mean loss of N bags is stepped on at once (minibatch training, a different schedule)")
     return p
 
 
