@@ -17,6 +17,15 @@ from . import ops
 Q_DIM = 128
 
 
+def _wdict(fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, detach=False):
+    """The weight dict of ops.agg_forward / agg_backward, in ops.W_KEYS order (so ``*w.values()`` are the weight arguments
+    of the autograd Functions below)."""
+    ts = (fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b)
+    if detach:
+        ts = [None if t is None else t.detach() for t in ts]
+    return dict(zip(ops.W_KEYS, ts))
+
+
 class FCLayer(nn.Module):
     """dsmil.py:6-12."""
 
@@ -152,10 +161,8 @@ class BClassifier(nn.Module):
     def forward(self, feats, c):
         if not feats.is_cuda:
             return self._forward_cpu(feats, c)
-        vals = self._values(feats)
-        w = self._weights()
-        pred, A, B = _AggFunction.apply(feats, c, vals, None, None, w["q0_w"], w["q0_b"], w["q2_w"],
-                                        w["q2_b"], w["fcc_w"], w["fcc_b"], self.nonlinear)[1:4]
+        w = _wdict(None, None, **self._weights())
+        pred, A, B = _AggFunction.apply(feats, c, self._values(feats), None, *w.values(), self.nonlinear)[1:4]
         return pred, A, B
 
 
@@ -167,19 +174,28 @@ class MILNet(nn.Module):
         self.i_classifier = i_classifier
         self.b_classifier = b_classifier
 
+    def _fused(self, x=None):
+        """Whether the fused native calls (FCLayer's logits + the aggregator in one call sequence) apply: the two modules
+        are FCLayer + BClassifier and — given rows — ``x`` is a 2-D CUDA tensor whose dtype the value stream takes natively
+        (with passing_v: fp32 only).  Every caller adds its own further conditions."""
+        ic, bc = self.i_classifier, self.b_classifier
+        if not (isinstance(ic, FCLayer) and isinstance(bc, BClassifier)):
+            return False
+        return x is None or (x.is_cuda and x.dim() == 2 and (x.dtype == torch.float32 or not bc.passing_v))
+
+    def _lin_weights(self, detach=False):
+        """(FCLayer's nn.Linear, the eight-key weight dict of the fused native calls)."""
+        lin = self.i_classifier.fc[0]
+        return lin, _wdict(lin.weight, lin.bias, **self.b_classifier._weights(), detach=detach)
+
     def forward(self, x):
         ic, bc = self.i_classifier, self.b_classifier
-        native_v = (not bc.passing_v or x.dtype == torch.float32) if isinstance(bc, BClassifier) else False
-        if x.is_cuda and isinstance(ic, FCLayer) and isinstance(bc, BClassifier) and native_v and x.dim() == 2:
+        if self._fused(x):
             # one fused native call: instance logits + aggregator (dsmil.py:70-74); with passing_v the native value
             # projection runs in front of it and its result goes in as `vals` (bf16 rows keep the two-module route below);
             # rows that require a gradient get it from the native backward (k_bwd_gx, k_value_gx)
-            w = bc._weights()
-            lin = ic.fc[0]
-            classes, pred, A, B = _AggFunction.apply(x, None, bc._values(x), lin.weight, lin.bias, w["q0_w"],
-                                                     w["q0_b"], w["q2_w"], w["q2_b"], w["fcc_w"],
-                                                     w["fcc_b"], bc.nonlinear)[0:4]
-            return classes, pred, A, B
+            _, w = self._lin_weights()
+            return _AggFunction.apply(x, None, bc._values(x), None, *w.values(), bc.nonlinear)[0:4]
         feats, classes = ic(x)
         prediction_bag, A, B = bc(feats, classes)
         return classes, prediction_bag, A, B
@@ -187,12 +203,10 @@ class MILNet(nn.Module):
     def graphed(self, n_rows):
         """A hipGraph-replayed forward for bags of exactly ``n_rows`` rows (inference; weights frozen): returns a
         callable feats -> (classes, pred [1,C], A, B [1,C,K]).  Single-bag latency is launch-bound otherwise."""
-        ic, bc = self.i_classifier, self.b_classifier
-        if not (isinstance(ic, FCLayer) and isinstance(bc, BClassifier)):
+        if not self._fused():
             raise NotImplementedError("graphed forward: FCLayer + BClassifier")
-        w = {k: (v.detach() if v is not None else None) for k, v in bc._weights().items()}
-        lin = ic.fc[0]
-        w["fc_w"], w["fc_b"] = lin.weight.detach(), lin.bias.detach()
+        bc = self.b_classifier
+        lin, w = self._lin_weights(detach=True)
         # passing_v: the value projection is captured with the rest (inference: the dropout of bc.v is the identity)
         v_w, v_b = (bc.v[1].weight.detach(), bc.v[1].bias.detach()) if bc.passing_v else (None, None)
         g = ops.GraphedAggForward(w, n_rows, lin.in_features, nonlinear=bc.nonlinear, device=lin.weight.device,
@@ -215,20 +229,16 @@ class MILNet(nn.Module):
         everything else — a passing_v model and rows that require a gradient included, whose forward and backward are
         native all the same (value projection + aggregator + the row-gradient kernels) — composes the same objective
         around ``self(x)``."""
-        ic, bc = self.i_classifier, self.b_classifier
-        if (feats.is_cuda and feats.dtype == torch.float32 and feats.dim() == 2 and isinstance(ic, FCLayer)
-                and isinstance(bc, BClassifier) and not bc.passing_v and not feats.requires_grad
-                and ic.fc[0].out_features <= 64):   # dsmil_agg_loss_head: one wave of classes; more take the torch expression
+        bc = self.b_classifier
+        if (self._fused(feats) and feats.dtype == torch.float32 and not bc.passing_v and not feats.requires_grad
+                and self.i_classifier.fc[0].out_features <= 64):   # dsmil_agg_loss_head: one wave of classes; more take the torch expression
             if row_map is not None and row_map.numel():
                 # an out-of-range index would become an out-of-bounds device read in the row loads: checked once per
                 # bag on the device, surfaced with the step's only host sync (the loss .item() of train_tcga.py:74)
                 torch._assert_async((row_map.min() >= 0) & (row_map.max() < feats.shape[0]),
                                     "row_map index out of range")
-            w = bc._weights()
-            lin = ic.fc[0]
-            loss, pred, mx = _BagLossFunction.apply(feats, label, row_map, lin.weight, lin.bias, w["q0_w"], w["q0_b"],
-                                                    w["q2_w"], w["q2_b"], w["fcc_w"], w["fcc_b"], bc.nonlinear)
-            return loss, pred, mx
+            _, w = self._lin_weights()
+            return _BagLossFunction.apply(feats, label, row_map, None, *w.values(), bc.nonlinear)
         x = feats if row_map is None else feats.index_select(0, row_map)
         ins, bag, _, _ = self(x)
         mx, _ = torch.max(ins, 0)
@@ -244,8 +254,8 @@ class MILNet(nn.Module):
         ``bags`` is a list of [N_i, K] CUDA tensors, or a tuple (feats [sum N_i, K], lengths).
         Returns a list of (classes, pred, A, B) tuples shaped like ``forward``'s.  New capability
         (the reference loops one bag per iteration, train_tcga.py:92-99)."""
-        ic, bc = self.i_classifier, self.b_classifier
-        if not (isinstance(ic, FCLayer) and isinstance(bc, BClassifier)):
+        bc = self.b_classifier
+        if not self._fused():
             return [self.forward(b) for b in bags]
         if bc.passing_v and bags[0].dtype != torch.float32:
             return [self.forward(b) for b in bags]   # (the value layer on bf16-stored rows: the torch route, bag by bag)
@@ -254,14 +264,10 @@ class MILNet(nn.Module):
         else:
             lengths = [int(b.shape[0]) for b in bags]
             feats = torch.cat(list(bags), dim=0)
-        w = bc._weights()
-        lin = ic.fc[0]
-        w["fc_w"], w["fc_b"] = lin.weight, lin.bias
         # passing_v: ONE projection over the concatenated rows, then one aggregator call over the batch
         vals = bc._values(feats)
-        classes, pred, A, B, _ = ops.agg_forward(feats, lengths, {k: (v.detach() if v is not None else None)
-                                                                  for k, v in w.items()},
-                                                 vals=vals, nonlinear=bc.nonlinear)
+        classes, pred, A, B, _ = ops.agg_forward(feats, lengths, self._lin_weights(detach=True)[1], vals=vals,
+                                                 nonlinear=bc.nonlinear)
         out, o = [], 0
         for i, n in enumerate(lengths):
             out.append((classes[o:o + n], pred[i:i + 1], A[o:o + n], B[i:i + 1]))
@@ -270,14 +276,12 @@ class MILNet(nn.Module):
 
     # -- minibatches: several bags per call, differentiable ----------------------------------------
     def _batch_native(self, feats):
-        """Whether a batch of these rows takes the native batched forward + backward (_AggBatchFunction): the conditions
-        of ``forward``'s fused call, plus what dsmil_agg_backward_bags would reject (query biases off 16-byte alignment)."""
-        ic, bc = self.i_classifier, self.b_classifier
-        if not (isinstance(ic, FCLayer) and isinstance(bc, BClassifier)):
+        """Whether a batch of these rows takes the native batched forward + backward (_AggFunction with lengths): fp32 rows
+        under the conditions of ``forward``'s fused call, minus what dsmil_agg_backward_bags would reject (query biases off
+        16-byte alignment)."""
+        if not (self._fused(feats) and feats.dtype == torch.float32):
             return False
-        if not (feats.is_cuda and feats.dtype == torch.float32 and feats.dim() == 2):
-            return False
-        w = bc._weights()
+        w = self.b_classifier._weights()
         return all(t is None or t.data_ptr() % 16 == 0 for t in (w["q0_b"], w["q2_b"]))
 
     def forward_batch(self, feats, lengths):
@@ -293,11 +297,9 @@ class MILNet(nn.Module):
         if sum(lengths) != feats.shape[0] or any(n <= 0 for n in lengths):
             raise ValueError(f"bag lengths must be positive and sum to {feats.shape[0]} rows")
         if self._batch_native(feats):
-            ic, bc = self.i_classifier, self.b_classifier
-            w = bc._weights()
-            lin = ic.fc[0]
-            return _AggBatchFunction.apply(feats, bc._values(feats), tuple(lengths), lin.weight, lin.bias, w["q0_w"],
-                                           w["q0_b"], w["q2_w"], w["q2_b"], w["fcc_w"], w["fcc_b"], bc.nonlinear)[0:4]
+            bc = self.b_classifier
+            _, w = self._lin_weights()
+            return _AggFunction.apply(feats, None, bc._values(feats), tuple(lengths), *w.values(), bc.nonlinear)[0:4]
         outs, o = [], 0
         for n in lengths:
             classes, pred, A, B = self.forward(feats[o:o + n])
@@ -322,11 +324,8 @@ class MILNet(nn.Module):
                 and self.i_classifier.fc[0].out_features <= 64):
             if row_map is not None and row_map.numel():
                 torch._assert_async((row_map.min() >= 0) & (row_map.max() < feats.shape[0]), "row_map index out of range")
-            w = bc._weights()
-            lin = self.i_classifier.fc[0]
-            loss, pred, mx, each = _BatchLossFunction.apply(feats, labels, row_map, tuple(lengths), lin.weight, lin.bias,
-                                                            w["q0_w"], w["q0_b"], w["q2_w"], w["q2_b"], w["fcc_w"],
-                                                            w["fcc_b"], bc.nonlinear)
+            _, w = self._lin_weights()
+            loss, pred, mx, each = _BagLossFunction.apply(feats, labels, row_map, tuple(lengths), *w.values(), bc.nonlinear)
             return (loss, pred, mx, each) if per_bag else (loss, pred, mx)
         x = feats if row_map is None else feats.index_select(0, row_map)
         ins, pred, _, _ = self.forward_batch(x, lengths)
@@ -388,30 +387,41 @@ class _ValueProjFunction(torch.autograd.Function):
 class _BagLossFunction(torch.autograd.Function):
     """Forward = dsmil_agg_forward_ex (row map) + dsmil_agg_loss_head; backward = dsmil_agg_backward_ex with the sparse
     max-stream gradient.  Replaces, per training step, the row gather, torch.max, two BCEWithLogitsLoss graphs and the
-    dense [N,C] instance-logit gradient of train_tcga.py:64-72."""
+    dense [N,C] instance-logit gradient of train_tcga.py:64-72.  With ``lengths`` (a tuple) the same over a batch of bags
+    stored back to back: the batched forward + dsmil_agg_loss_head_bags, loss = the mean of the bags' losses (each bag's own
+    loss is a fourth output), backward = dsmil_agg_backward_bags."""
 
     @staticmethod
-    def forward(ctx, feats, label, row_map, fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, nonlinear):
-        det = lambda t: t.detach() if t is not None else None
-        w = {"fc_w": det(fc_w), "fc_b": det(fc_b), "q0_w": det(q0_w), "q0_b": det(q0_b),
-             "q2_w": det(q2_w), "q2_b": det(q2_b), "fcc_w": det(fcc_w), "fcc_b": det(fcc_b)}
-        N = int(row_map.numel()) if row_map is not None else feats.shape[0]
-        classes, pred, A, B, idx = ops.agg_forward(feats.detach(), [N], w, nonlinear=nonlinear, row_map=row_map)
-        loss, max_pred, g_pred, g_max = ops.agg_loss_head(classes, pred, idx, label.detach())
-        ctx.nonlinear = nonlinear
+    def forward(ctx, feats, label, row_map, lengths, fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, nonlinear):
+        w = _wdict(fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, detach=True)
+        if lengths is None:
+            N = int(row_map.numel()) if row_map is not None else feats.shape[0]
+            classes, pred, A, B, idx = ops.agg_forward(feats.detach(), [N], w, nonlinear=nonlinear, row_map=row_map)
+            loss, max_pred, g_pred, g_max = ops.agg_loss_head(classes, pred, idx, label.detach())
+            out = (loss, pred, max_pred)
+        else:
+            classes, pred, A, B, idx = ops.agg_forward(feats.detach(), lengths, w, nonlinear=nonlinear, row_map=row_map)
+            each, max_pred, g_pred, g_max = ops.agg_loss_head_bags(classes, lengths, pred, idx, label.detach())
+            out = (each.mean(), pred, max_pred, each)
+        ctx.nonlinear, ctx.lengths = nonlinear, lengths
         ctx.save_for_backward(feats, row_map, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx, g_pred, g_max)
-        ctx.mark_non_differentiable(pred, max_pred)
-        return loss, pred, max_pred
+        ctx.mark_non_differentiable(*out[1:])
+        return out
 
     @staticmethod
-    def backward(ctx, g_loss, _g_pred, _g_max):
+    def backward(ctx, g_loss, *_):
         feats, row_map, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx, g_pred, g_max = ctx.saved_tensors
-        w = {"fc_w": fc_w, "fc_b": None, "q0_w": q0_w, "q0_b": q0_b, "q2_w": q2_w, "q2_b": q2_b,
-             "fcc_w": fcc_w, "fcc_b": None}
-        # every parameter gradient is linear in (g_pred, g_max): the upstream scalar scales those two [C] vectors
-        g = ops.agg_backward(feats, w, A, B, idx, g_pred * g_loss, g_max=g_max * g_loss, row_map=row_map,
-                             nonlinear=ctx.nonlinear)
-        return (None, None, None, g["fc_w"], g["fc_b"], g["q0_w"], g["q0_b"], g.get("q2_w"), g.get("q2_b"),
+        w = _wdict(fc_w, None, q0_w, q0_b, q2_w, q2_b, fcc_w, None)
+        # every parameter gradient is linear in (g_pred, g_max): the upstream scalar scales those two vectors (a batch: the
+        # mean over the bags is a factor 1 / n on each bag's own)
+        if ctx.lengths is None:
+            g = ops.agg_backward(feats, w, A, B, idx, g_pred * g_loss, g_max=g_max * g_loss, row_map=row_map,
+                                 nonlinear=ctx.nonlinear)
+        else:
+            scale = g_loss / len(ctx.lengths)
+            g = ops.agg_backward_bags(feats, ctx.lengths, w, A, B, idx, g_pred * scale, g_max=g_max * scale, row_map=row_map,
+                                      nonlinear=ctx.nonlinear)
+        return (None, None, None, None, g["fc_w"], g["fc_b"], g["q0_w"], g["q0_b"], g.get("q2_w"), g.get("q2_b"),
                 g["fcc_w"], g["fcc_b"], None)
 
 
@@ -419,16 +429,17 @@ class _AggFunction(torch.autograd.Function):
     """Forward = dsmil_agg_forward (HIP).  Backward = analytic gradient of dsmil.py:46-62 (the
     arg-max indices are constants, as in the reference's autograd graph); it re-derives Q from
     the saved inputs (dsmil_agg_backward, csrc/agg_bwd.hip — SURVEY.md §8(f) row N1).  The gradient of the input rows,
-    when asked for, comes from the same native call (dsmil_agg_backward_rows, k_bwd_gx)."""
+    when asked for, comes from the same native call (dsmil_agg_backward_rows, k_bwd_gx).
+    ``lengths`` None: ONE bag.  A tuple of lengths: a batch of bags stored back to back (fp32 rows, no ``c_in``) — the batched
+    forward and, for the backward, dsmil_agg_backward_bags: every parameter gradient summed over the bags in one native call,
+    g_vals for a trainable v and the gradient of the input rows from the same call."""
 
     @staticmethod
-    def forward(ctx, feats, c_in, vals, fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, nonlinear):
+    def forward(ctx, feats, c_in, vals, lengths, fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, nonlinear):
         det = lambda t: t.detach() if t is not None else None
-        w = {"fc_w": det(fc_w), "fc_b": det(fc_b), "q0_w": det(q0_w), "q0_b": det(q0_b),
-             "q2_w": det(q2_w), "q2_b": det(q2_b), "fcc_w": det(fcc_w), "fcc_b": det(fcc_b)}
-        N = feats.shape[0]
-        classes, pred, A, B, idx = ops.agg_forward(feats.detach(), [N], w, classes_in=det(c_in),
-                                                   vals=det(vals), nonlinear=nonlinear)
+        w = _wdict(fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, detach=True)
+        classes, pred, A, B, idx = ops.agg_forward(feats.detach(), [feats.shape[0]] if lengths is None else lengths, w,
+                                                   classes_in=det(c_in), vals=det(vals), nonlinear=nonlinear)
         if feats.dtype == torch.bfloat16:
             # bf16-storage path (BASELINE config 2) is inference only; results keep the input dtype
             ctx.bf16 = True
@@ -436,7 +447,7 @@ class _AggFunction(torch.autograd.Function):
             ctx.mark_non_differentiable(*out, idx)
             return (*out, idx)
         ctx.bf16 = False
-        ctx.nonlinear = nonlinear
+        ctx.nonlinear, ctx.lengths = nonlinear, lengths
         ctx.has_cin = c_in is not None
         ctx.has_vals = vals is not None
         ctx.save_for_backward(feats, vals, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx)
@@ -447,7 +458,7 @@ class _AggFunction(torch.autograd.Function):
     def backward(ctx, g_cls, g_pred, g_A, g_B, _g_idx):
         if ctx.bf16:
             raise NotImplementedError("the bf16-storage aggregator path is inference only")
-        if not ctx.needs_input_grad[0] or _AggFunction._native_accepts(ctx):
+        if ctx.lengths is not None or not ctx.needs_input_grad[0] or _AggFunction._native_accepts(ctx):
             return _AggFunction._backward_native(ctx, g_cls, g_pred, g_A, g_B)
         return _AggFunction._backward_dense(ctx, g_cls, g_pred, g_A, g_B)
 
@@ -465,18 +476,19 @@ class _AggFunction(torch.autograd.Function):
         feats, vals, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx = ctx.saved_tensors
         C = fcc_w.shape[0]
         if g_pred is None:
-            g_pred = torch.zeros((1, C), device=feats.device)
-        w = {"fc_w": fc_w, "fc_b": None, "q0_w": q0_w, "q0_b": q0_b, "q2_w": q2_w, "q2_b": q2_b,
-             "fcc_w": fcc_w, "fcc_b": None}
+            g_pred = torch.zeros((1 if ctx.lengths is None else len(ctx.lengths), C), device=feats.device)
+        w = _wdict(fc_w, None, q0_w, q0_b, q2_w, q2_b, fcc_w, None)
         want_x = ctx.needs_input_grad[0]
         # (vals sharing feats' memory IS v = Identity to the kernels: the rows' gradient then already holds A gB)
         same = ctx.has_vals and vals.data_ptr() == feats.data_ptr()
         want_v = ctx.has_vals and ctx.needs_input_grad[2] and not (want_x and same)
-        g = ops.agg_backward(feats, w, A, B, idx, g_pred, g_classes=None if ctx.has_cin else g_cls,
-                             g_A=g_A, g_B=g_B[0] if g_B is not None else None,
-                             vals=vals if ctx.has_vals else None, nonlinear=ctx.nonlinear, want_g_vals=want_v,
-                             want_g_feats=want_x)
-        return (g.get("feats"), None, g.get("vals"), g.get("fc_w"), g.get("fc_b"), g["q0_w"], g["q0_b"],
+        kw = dict(g_classes=None if ctx.has_cin else g_cls, g_A=g_A, vals=vals if ctx.has_vals else None,
+                  nonlinear=ctx.nonlinear, want_g_vals=want_v, want_g_feats=want_x)
+        if ctx.lengths is None:
+            g = ops.agg_backward(feats, w, A, B, idx, g_pred, g_B=g_B[0] if g_B is not None else None, **kw)
+        else:
+            g = ops.agg_backward_bags(feats, ctx.lengths, w, A, B, idx, g_pred, g_B=g_B, **kw)
+        return (g.get("feats"), None, g.get("vals"), None, g.get("fc_w"), g.get("fc_b"), g["q0_w"], g["q0_b"],
                 g.get("q2_w"), g.get("q2_b"), g["fcc_w"], g["fcc_b"], None)
 
     @staticmethod
@@ -538,68 +550,5 @@ class _AggFunction(torch.autograd.Function):
                 g_x = g_x + A.mm(gB)
         if ctx.has_vals and ctx.needs_input_grad[2]:
             g_vals = A.mm(gB)
-        return (g_x, g_cin, g_vals, g_fc_w, g_fc_b, g_q0_w, g_q0_b, g_q2_w, g_q2_b,
+        return (g_x, g_cin, g_vals, None, g_fc_w, g_fc_b, g_q0_w, g_q0_b, g_q2_w, g_q2_b,
                 g_fcc_w, g_fcc_b, None)
-
-
-class _AggBatchFunction(torch.autograd.Function):
-    """_AggFunction over a batch of bags stored back to back: forward = dsmil_agg_forward_ex (n_bags bags), backward =
-    dsmil_agg_backward_bags — every parameter gradient summed over the bags in one native call, g_vals for a trainable v and
-    the gradient of the input rows from the same call."""
-
-    @staticmethod
-    def forward(ctx, feats, vals, lengths, fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, nonlinear):
-        det = lambda t: t.detach() if t is not None else None
-        w = {"fc_w": det(fc_w), "fc_b": det(fc_b), "q0_w": det(q0_w), "q0_b": det(q0_b),
-             "q2_w": det(q2_w), "q2_b": det(q2_b), "fcc_w": det(fcc_w), "fcc_b": det(fcc_b)}
-        classes, pred, A, B, idx = ops.agg_forward(feats.detach(), lengths, w, vals=det(vals), nonlinear=nonlinear)
-        ctx.nonlinear, ctx.lengths, ctx.has_vals = nonlinear, lengths, vals is not None
-        ctx.save_for_backward(feats, vals, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx)
-        ctx.mark_non_differentiable(idx)
-        return classes, pred, A, B, idx
-
-    @staticmethod
-    def backward(ctx, g_cls, g_pred, g_A, g_B, _g_idx):
-        feats, vals, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx = ctx.saved_tensors
-        C = fcc_w.shape[0]
-        if g_pred is None:
-            g_pred = torch.zeros((len(ctx.lengths), C), device=feats.device)
-        w = {"fc_w": fc_w, "fc_b": None, "q0_w": q0_w, "q0_b": q0_b, "q2_w": q2_w, "q2_b": q2_b,
-             "fcc_w": fcc_w, "fcc_b": None}
-        want_x = ctx.needs_input_grad[0]
-        same = ctx.has_vals and vals.data_ptr() == feats.data_ptr()
-        want_v = ctx.has_vals and ctx.needs_input_grad[1] and not (want_x and same)
-        g = ops.agg_backward_bags(feats, ctx.lengths, w, A, B, idx, g_pred, g_classes=g_cls, g_A=g_A, g_B=g_B,
-                                  vals=vals if ctx.has_vals else None, nonlinear=ctx.nonlinear, want_g_vals=want_v,
-                                  want_g_feats=want_x)
-        return (g.get("feats"), g.get("vals"), None, g.get("fc_w"), g.get("fc_b"), g["q0_w"], g["q0_b"],
-                g.get("q2_w"), g.get("q2_b"), g["fcc_w"], g["fcc_b"], None)
-
-
-class _BatchLossFunction(torch.autograd.Function):
-    """_BagLossFunction over a batch: forward = the batched dsmil_agg_forward_ex (row map) + dsmil_agg_loss_head_bags,
-    loss = the mean of the bags' losses; backward = dsmil_agg_backward_bags with the sparse max-stream gradient."""
-
-    @staticmethod
-    def forward(ctx, feats, labels, row_map, lengths, fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, nonlinear):
-        det = lambda t: t.detach() if t is not None else None
-        w = {"fc_w": det(fc_w), "fc_b": det(fc_b), "q0_w": det(q0_w), "q0_b": det(q0_b),
-             "q2_w": det(q2_w), "q2_b": det(q2_b), "fcc_w": det(fcc_w), "fcc_b": det(fcc_b)}
-        classes, pred, A, B, idx = ops.agg_forward(feats.detach(), lengths, w, nonlinear=nonlinear, row_map=row_map)
-        each, max_pred, g_pred, g_max = ops.agg_loss_head_bags(classes, lengths, pred, idx, labels.detach())
-        ctx.nonlinear, ctx.lengths = nonlinear, lengths
-        ctx.save_for_backward(feats, row_map, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx, g_pred, g_max)
-        ctx.mark_non_differentiable(pred, max_pred, each)
-        return each.mean(), pred, max_pred, each
-
-    @staticmethod
-    def backward(ctx, g_loss, _g_pred, _g_max, _g_each):
-        feats, row_map, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx, g_pred, g_max = ctx.saved_tensors
-        w = {"fc_w": fc_w, "fc_b": None, "q0_w": q0_w, "q0_b": q0_b, "q2_w": q2_w, "q2_b": q2_b,
-             "fcc_w": fcc_w, "fcc_b": None}
-        # every gradient is linear in (g_pred, g_max); the mean over the bags is a factor 1 / n on each bag's own
-        scale = g_loss / len(ctx.lengths)
-        g = ops.agg_backward_bags(feats, ctx.lengths, w, A, B, idx, g_pred * scale, g_max=g_max * scale, row_map=row_map,
-                                  nonlinear=ctx.nonlinear)
-        return (None, None, None, None, g["fc_w"], g["fc_b"], g["q0_w"], g["q0_b"], g.get("q2_w"), g.get("q2_b"),
-                g["fcc_w"], g["fcc_b"], None)

@@ -180,30 +180,46 @@ def fc_forward(feats, fc_w, fc_b):
 
 _bf16_cache = _LRU()
 _split_cache = _LRU()
+W_KEYS = ("fc_w", "fc_b", "q0_w", "q0_b", "q2_w", "q2_b", "fcc_w", "fcc_b")   # the field order of struct dsmil_agg_params
+
+
+def _cached(cache, key, dev, sources, make):
+    """The device buffers derived from one weight set, made once per ``key`` (the device and the (data_ptr, _version) of
+    every source tensor).  ``make()`` allocates and fills them on the current stream and returns them as a tuple.  The entry
+    is (buffers, sources, _Ready): it keeps ``sources`` alive, so that a freed parameter's address can never be mistaken
+    for a new one with the same version count, and a hit on another stream waits for the producer (_Ready.wait)."""
+    ent = cache.get(key)
+    if ent is None:
+        ent = cache.put(key, (make(), sources, _Ready(dev)))
+    else:
+        ent[2].wait(dev, *ent[0])
+    return ent[0]
+
+
+def _pack_image(dev, nbytes, entry, *args):
+    """A new uint8 device buffer of ``nbytes`` filled by the library's pack call ``entry``(*args, buffer, stream)."""
+    packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = getattr(_native.lib(), entry)(*args, _ptr(packed), _stream(dev))
+    _native.check(rc, entry)
+    return packed
 
 
 def _bf16_params(w, nonlinear, dev):
     """bf16 path: every weight/bias rounded to bf16 (what module.bfloat16() would hold), kept as
     fp32 tensors for the f32-accumulating stages + the packed bf16 MFMA operands.  Cached per
-    parameter set (data_ptr, _version); the entry keeps the source tensors alive so that a freed
-    parameter's address can never be mistaken for a new one with the same version count."""
-    names = ("fc_w", "fc_b", "q0_w", "q0_b", "q2_w", "q2_b", "fcc_w", "fcc_b")
-    key = (str(dev), bool(nonlinear)) + tuple(_tkey(w.get(k)) for k in names)
-    ent = _bf16_cache.get(key)
-    if ent is not None:
-        ent[3].wait(dev, ent[1], *[t for t in ent[0].values() if t is not None])
-        return ent[0], ent[1]
-    r = {k: (w[k].detach().to(torch.bfloat16).to(torch.float32).contiguous() if w.get(k) is not None else None)
-         for k in names}
-    L = _native.lib()
-    K = r["q0_w"].shape[1]
-    packed = torch.empty(L.dsmil_agg_packed_bf16_bytes(K), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.dsmil_agg_pack_bf16(_ptr(r["q0_w"]), _ptr(r["q2_w"] if nonlinear else None), K, _ptr(packed),
-                                   _stream(dev))
-    _native.check(rc, "dsmil_agg_pack_bf16")
-    _bf16_cache.put(key, (r, packed, [w.get(k) for k in names], _Ready(dev)))
-    return r, packed
+    parameter set (_cached)."""
+
+    def make():
+        r = [w[k].detach().to(torch.bfloat16).to(torch.float32).contiguous() if w.get(k) is not None else None
+             for k in W_KEYS]
+        q0_w, q2_w = r[2], r[4]
+        K = q0_w.shape[1]
+        return (_pack_image(dev, _native.lib().dsmil_agg_packed_bf16_bytes(K), "dsmil_agg_pack_bf16", _ptr(q0_w),
+                            _ptr(q2_w if nonlinear else None), K), *r)
+    key = (str(dev), bool(nonlinear)) + tuple(_tkey(w.get(k)) for k in W_KEYS)
+    packed, *r = _cached(_bf16_cache, key, dev, [w.get(k) for k in W_KEYS], make)
+    return dict(zip(W_KEYS, r)), packed
 
 
 def _split_params(q0_w, q2_w, nonlinear, dev):
@@ -213,36 +229,25 @@ def _split_params(q0_w, q2_w, nonlinear, dev):
     L = _native.lib()
     if L.dsmil_agg_mlp_form() == 0:
         return None
-    key = (str(dev), bool(nonlinear), _tkey(q0_w), _tkey(q2_w) if nonlinear else None)
-    ent = _split_cache.get(key)
-    if ent is not None:
-        ent[2].wait(dev, ent[0])
-        return ent[0]
-    K = q0_w.shape[1]
-    packed = torch.empty(L.dsmil_agg_packed_split_bytes(K, 1 if nonlinear else 0), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.dsmil_agg_pack_split(_ptr(q0_w), _ptr(q2_w if nonlinear else None), K, _ptr(packed), _stream(dev))
-    _native.check(rc, "dsmil_agg_pack_split")
-    _split_cache.put(key, (packed, [q0_w, q2_w], _Ready(dev)))
-    return packed
+    K, q2 = q0_w.shape[1], q2_w if nonlinear else None
+    key = (str(dev), bool(nonlinear), _tkey(q0_w), _tkey(q2))
+
+    def make():
+        nbytes = L.dsmil_agg_packed_split_bytes(K, 1 if nonlinear else 0)
+        return (_pack_image(dev, nbytes, "dsmil_agg_pack_split", _ptr(q0_w), _ptr(q2), K),)
+    return _cached(_split_cache, key, dev, [q0_w, q2_w], make)[0]
 
 
 def _f2_params(q0_w, q2_w, nonlinear, dev):
     """fp32 path, batches of bags (k_attend_f2, csrc/agg_f2.h): the query weights as two fp16 planes of their power-of-two
     scaled values in MFMA-fragment order (dsmil_agg_pack_f2), prepared once per weight set."""
-    L = _native.lib()
-    key = ("f2", str(dev), bool(nonlinear), _tkey(q0_w), _tkey(q2_w) if nonlinear else None)
-    ent = _split_cache.get(key)
-    if ent is not None:
-        ent[2].wait(dev, ent[0])
-        return ent[0]
-    K = q0_w.shape[1]
-    packed = torch.empty(L.dsmil_agg_packed_f2_bytes(K), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.dsmil_agg_pack_f2(_ptr(q0_w), _ptr(q2_w if nonlinear else None), K, _ptr(packed), _stream(dev))
-    _native.check(rc, "dsmil_agg_pack_f2")
-    _split_cache.put(key, (packed, [q0_w, q2_w], _Ready(dev)))
-    return packed
+    K, q2 = q0_w.shape[1], q2_w if nonlinear else None
+    key = ("f2", str(dev), bool(nonlinear), _tkey(q0_w), _tkey(q2))
+
+    def make():
+        nbytes = _native.lib().dsmil_agg_packed_f2_bytes(K)
+        return (_pack_image(dev, nbytes, "dsmil_agg_pack_f2", _ptr(q0_w), _ptr(q2), K),)
+    return _cached(_split_cache, key, dev, [q0_w, q2_w], make)[0]
 
 
 def _i64c(t, name):
@@ -251,6 +256,15 @@ def _i64c(t, name):
     if not t.is_cuda or t.dtype != torch.int64:
         raise RuntimeError(f"{name} must be an int64 CUDA(HIP) tensor")
     return t if t.is_contiguous() else t.contiguous()
+
+
+def _agg_params(w, K, Kv, nonlinear):
+    """struct dsmil_agg_params of the weight dict ``w``, the contiguous fp32 tensors it points into (in W_KEYS order; the
+    caller holds them until its call is enqueued) and C."""
+    keep = [_f32c(w.get(k), k) for k in W_KEYS]
+    C = w["fcc_w"].shape[0]
+    p = _native.AggParams(*[(t.data_ptr() if t is not None else 0) for t in keep], K, Kv, C, 1 if nonlinear else 0)
+    return p, keep, C
 
 
 def agg_forward(feats, lengths, w, classes_in=None, vals=None, nonlinear=True, offsets=None, row_map=None):
@@ -295,17 +309,13 @@ def agg_forward(feats, lengths, w, classes_in=None, vals=None, nonlinear=True, o
     packed = None
     if bf16:
         w, packed = _bf16_params(w, nonlinear, dev)
-    fcc_w = _f32c(w["fcc_w"], "fcc_w")
-    C = fcc_w.shape[0]
-    if fcc_w.shape[2] != Kv:
-        raise ValueError(f"fcc kernel_size {fcc_w.shape[2]} != value width {Kv}")
+    p, keep, C = _agg_params(w, K, Kv, nonlinear)
+    if w["fcc_w"].shape[2] != Kv:
+        raise ValueError(f"fcc kernel_size {w['fcc_w'].shape[2]} != value width {Kv}")
     if classes_in is not None:
         classes_in = _f32c(classes_in.float(), "classes_in")
         if tuple(classes_in.shape) != (total, C):
             raise ValueError(f"c must be [{total},{C}], got {tuple(classes_in.shape)}")
-    keep = [_f32c(w.get(k), k) for k in ("fc_w", "fc_b", "q0_w", "q0_b", "q2_w", "q2_b", "fcc_w", "fcc_b")]
-    p = _native.AggParams(*[(t.data_ptr() if t is not None else 0) for t in keep],
-                          K, Kv, C, 1 if nonlinear else 0)
     off = offsets if offsets is not None else offsets_tensor(lengths, dev)
     classes = classes_in if classes_in is not None else torch.empty((total, C), dtype=torch.float32, device=dev)
     A = torch.empty((total, C), dtype=torch.float32, device=dev)
@@ -349,19 +359,12 @@ def agg_forward(feats, lengths, w, classes_in=None, vals=None, nonlinear=True, o
 def _value_params(v_w, dev):
     """BClassifier.v's weight [Kv, K] as two fp16 planes of its power-of-two scaled values in MFMA-fragment order
     (dsmil_value_pack, csrc/agg_value.h), prepared once per weight set (cached like _f2_params)."""
-    L = _native.lib()
-    key = ("value", str(dev), _tkey(v_w))
-    ent = _split_cache.get(key)
-    if ent is not None:
-        ent[2].wait(dev, ent[0])
-        return ent[0]
     Kv, K = v_w.shape
-    packed = torch.empty(L.dsmil_value_packed_bytes(K, Kv), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.dsmil_value_pack(_ptr(v_w), K, Kv, _ptr(packed), _stream(dev))
-    _native.check(rc, "dsmil_value_pack")
-    _split_cache.put(key, (packed, [v_w], _Ready(dev)))
-    return packed
+
+    def make():
+        nbytes = _native.lib().dsmil_value_packed_bytes(K, Kv)
+        return (_pack_image(dev, nbytes, "dsmil_value_pack", _ptr(v_w), K, Kv),)
+    return _cached(_split_cache, ("value", str(dev), _tkey(v_w)), dev, [v_w], make)[0]
 
 
 def value_proj(feats, v_w, v_b, row_map=None):
@@ -485,14 +488,6 @@ class GraphedAggForward:
         return self.out   # the STATIC output tensors of the capture: valid until the next call (clone to keep)
 
 
-def _agg_params(w, K, Kv, nonlinear):
-    fcc_w = _f32c(w["fcc_w"], "fcc_w")
-    C = fcc_w.shape[0]
-    keep = [_f32c(w.get(k), k) for k in ("fc_w", "fc_b", "q0_w", "q0_b", "q2_w", "q2_b", "fcc_w", "fcc_b")]
-    p = _native.AggParams(*[(t.data_ptr() if t is not None else 0) for t in keep], K, Kv, C, 1 if nonlinear else 0)
-    return p, keep, C
-
-
 def agg_shard_argmax(feats, w, nonlinear=True):
     """dsmil_agg_shard_argmax: one rank's row range of an instance-sharded bag.
     Returns (classes [rows,C], best_val [C], best_idx [C] shard-local)."""
@@ -555,6 +550,62 @@ def agg_loss_head(classes, pred, idx, label):
     return loss.reshape(()), max_pred, g_pred, g_max
 
 
+def _agg_backward(lengths, offsets, feats, w, A, B, idx, g_pred, g_classes, g_A, g_B, vals, nonlinear, want_g_vals, g_max,
+                  row_map, want_g_feats):
+    """The body of agg_backward (``lengths`` None: ONE bag, dsmil_agg_backward_ex, or dsmil_agg_backward_rows for the input
+    rows' gradient) and of agg_backward_bags (a batch: dsmil_agg_backward_bags).  The entries launch different kernels."""
+    feats = _f32c(feats, "feats")
+    dev = feats.device
+    N, K = feats.shape
+    row_map = _i64c(row_map, "row_map")
+    if row_map is not None:
+        N = int(row_map.numel())
+    vals = feats if vals is None else _f32c(vals, "vals")
+    Kv = vals.shape[1]
+    p, keep, C = _agg_params(w, K, Kv, nonlinear)
+    A = _f32c(A, "A"); B = _f32c(B, "B")
+    g_classes = _f32c(g_classes, "g_classes"); g_A = _f32c(g_A, "g_A"); g_B = _f32c(g_B, "g_B")
+    L = _native.lib()
+    if lengths is None:
+        entry = "dsmil_agg_backward_rows" if want_g_feats else "dsmil_agg_backward_ex"
+        extent, per_bag = (N,), (-1,)
+        idx = idx.contiguous()
+        nbytes = L.dsmil_agg_backward_workspace_bytes(N, K, Kv, C)
+    else:
+        entry = "dsmil_agg_backward_bags"
+        lengths = [int(n) for n in lengths]
+        if sum(lengths) != N or any(n <= 0 for n in lengths):
+            raise ValueError(f"bag lengths must be positive and sum to {N}")
+        off = offsets if offsets is not None else offsets_tensor(lengths, dev)
+        extent, per_bag = (_ptr(off), len(lengths), N, max(lengths)), (len(lengths), C)
+        idx = _i64c(idx.reshape(per_bag), "idx")
+        nbytes = L.dsmil_agg_backward_bags_workspace_bytes(len(lengths), N, K, Kv, C)
+    g_pred = _f32c(g_pred.reshape(per_bag), "g_pred")
+    g_max = _f32c(g_max.reshape(per_bag), "g_max") if g_max is not None else None
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    out = {"q0_w": new(Q_DIM, K), "q0_b": new(Q_DIM), "fcc_w": new(C, C, Kv), "fcc_b": new(C)}
+    if nonlinear:
+        out["q2_w"], out["q2_b"] = new(Q_DIM, Q_DIM), new(Q_DIM)
+    if g_classes is not None or g_max is not None:
+        out["fc_w"], out["fc_b"] = new(C, K), new(C)
+    g = _native.AggGrads(*[(out[k].data_ptr() if k in out else 0) for k in W_KEYS])
+    g_vals = new(N, Kv) if want_g_vals else None
+    g_feats = new(N, K) if want_g_feats else None
+    ws = _workspace(dev, nbytes)
+    tail = () if entry == "dsmil_agg_backward_ex" else (_ptr(g_feats),)   # (the entry without the row-gradient argument)
+    with torch.cuda.device(dev):
+        rc = getattr(L, entry)(_ptr(feats), _ptr(vals), *extent, ctypes.byref(p), _ptr(A), _ptr(B), _ptr(idx), _ptr(g_classes),
+                               _ptr(g_max), _ptr(g_pred), _ptr(g_A), _ptr(g_B), ctypes.byref(g), _ptr(g_vals), _ptr(row_map),
+                               _ptr(ws), ws.numel(), _stream(dev), *tail)
+    _native.check(rc, entry)
+    del keep
+    if want_g_feats:
+        out["feats"] = g_feats
+    if want_g_vals:
+        out["vals"] = g_vals
+    return out
+
+
 def agg_backward(feats, w, A, B, idx, g_pred, g_classes=None, g_A=None, g_B=None, vals=None, nonlinear=True,
                  want_g_vals=False, g_max=None, row_map=None, want_g_feats=False):
     """dsmil_agg_backward: parameter gradients of FCLayer + BClassifier for ONE bag (what autograd
@@ -566,53 +617,8 @@ def agg_backward(feats, w, A, B, idx, g_pred, g_classes=None, g_A=None, g_B=None
     gradient of the input rows [N,K] in LOGICAL row order (dsmil_agg_backward_rows, one more launch: k_bwd_gx); with
     caller-supplied ``vals`` it leaves out the value stream's share (value_proj_backward_rows adds that).  A call without
     it is dsmil_agg_backward_ex as before."""
-    feats = _f32c(feats, "feats")
-    dev = feats.device
-    N, K = feats.shape
-    row_map = _i64c(row_map, "row_map")
-    if row_map is not None:
-        N = int(row_map.numel())
-    vals = feats if vals is None else _f32c(vals, "vals")
-    Kv = vals.shape[1]
-    fcc_w = _f32c(w["fcc_w"], "fcc_w")
-    C = fcc_w.shape[0]
-    keep = [_f32c(w.get(k), k) for k in ("fc_w", "fc_b", "q0_w", "q0_b", "q2_w", "q2_b", "fcc_w", "fcc_b")]
-    p = _native.AggParams(*[(t.data_ptr() if t is not None else 0) for t in keep],
-                          K, Kv, C, 1 if nonlinear else 0)
-    A = _f32c(A, "A"); B = _f32c(B, "B")
-    idx = idx.contiguous()
-    g_pred = _f32c(g_pred.reshape(-1), "g_pred")
-    g_classes = _f32c(g_classes, "g_classes"); g_A = _f32c(g_A, "g_A"); g_B = _f32c(g_B, "g_B")
-    g_max = _f32c(g_max.reshape(-1), "g_max") if g_max is not None else None
-    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-    out = {"q0_w": new(Q_DIM, K), "q0_b": new(Q_DIM), "fcc_w": new(C, C, Kv), "fcc_b": new(C)}
-    if nonlinear:
-        out["q2_w"], out["q2_b"] = new(Q_DIM, Q_DIM), new(Q_DIM)
-    if g_classes is not None or g_max is not None:
-        out["fc_w"], out["fc_b"] = new(C, K), new(C)
-    g = _native.AggGrads(*[(out[k].data_ptr() if k in out else 0)
-                           for k in ("fc_w", "fc_b", "q0_w", "q0_b", "q2_w", "q2_b", "fcc_w", "fcc_b")])
-    g_vals = new(N, Kv) if want_g_vals else None
-    L = _native.lib()
-    nbytes = L.dsmil_agg_backward_workspace_bytes(N, K, Kv, C)
-    ws = _workspace(dev, nbytes)
-    g_feats = new(N, K) if want_g_feats else None
-    with torch.cuda.device(dev):
-        if want_g_feats:
-            rc = L.dsmil_agg_backward_rows(_ptr(feats), _ptr(vals), N, ctypes.byref(p), _ptr(A), _ptr(B), _ptr(idx),
-                                           _ptr(g_classes), _ptr(g_max), _ptr(g_pred), _ptr(g_A), _ptr(g_B), ctypes.byref(g),
-                                           _ptr(g_vals), _ptr(row_map), _ptr(ws), ws.numel(), _stream(dev), _ptr(g_feats))
-        else:
-            rc = L.dsmil_agg_backward_ex(_ptr(feats), _ptr(vals), N, ctypes.byref(p), _ptr(A), _ptr(B), _ptr(idx),
-                                         _ptr(g_classes), _ptr(g_max), _ptr(g_pred), _ptr(g_A), _ptr(g_B), ctypes.byref(g),
-                                         _ptr(g_vals), _ptr(row_map), _ptr(ws), ws.numel(), _stream(dev))
-    _native.check(rc, "dsmil_agg_backward_rows" if want_g_feats else "dsmil_agg_backward_ex")
-    del keep
-    if want_g_feats:
-        out["feats"] = g_feats
-    if want_g_vals:
-        out["vals"] = g_vals
-    return out
+    return _agg_backward(None, None, feats, w, A, B, idx, g_pred, g_classes, g_A, g_B, vals, nonlinear, want_g_vals, g_max,
+                         row_map, want_g_feats)
 
 
 def agg_loss_head_bags(classes, lengths, pred, idx, labels, offsets=None):
@@ -642,52 +648,8 @@ def agg_backward_bags(feats, lengths, w, A, B, idx, g_pred, g_classes=None, g_A=
     idx [n,C] = the batched forward's outputs; g_pred [n,C], g_max [n,C] or None, g_classes / g_A [total,C], g_B [n,C,Kv]
     (None = zero).  Returns the dict of ``agg_backward``: every parameter gradient summed over the bags, ``vals`` /
     ``feats`` (on request) laid end to end in logical row order."""
-    feats = _f32c(feats, "feats")
-    dev = feats.device
-    total, K = feats.shape
-    row_map = _i64c(row_map, "row_map")
-    if row_map is not None:
-        total = int(row_map.numel())
-    lengths = [int(n) for n in lengths]
-    if sum(lengths) != total or any(n <= 0 for n in lengths):
-        raise ValueError(f"bag lengths must be positive and sum to {total}")
-    n = len(lengths)
-    vals = feats if vals is None else _f32c(vals, "vals")
-    Kv = vals.shape[1]
-    fcc_w = _f32c(w["fcc_w"], "fcc_w")
-    C = fcc_w.shape[0]
-    keep = [_f32c(w.get(k), k) for k in ("fc_w", "fc_b", "q0_w", "q0_b", "q2_w", "q2_b", "fcc_w", "fcc_b")]
-    p = _native.AggParams(*[(t.data_ptr() if t is not None else 0) for t in keep], K, Kv, C, 1 if nonlinear else 0)
-    A = _f32c(A, "A"); B = _f32c(B, "B")
-    idx = _i64c(idx.reshape(n, C), "idx")
-    g_pred = _f32c(g_pred.reshape(n, C), "g_pred")
-    g_classes = _f32c(g_classes, "g_classes"); g_A = _f32c(g_A, "g_A"); g_B = _f32c(g_B, "g_B")
-    g_max = _f32c(g_max.reshape(n, C), "g_max") if g_max is not None else None
-    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-    out = {"q0_w": new(Q_DIM, K), "q0_b": new(Q_DIM), "fcc_w": new(C, C, Kv), "fcc_b": new(C)}
-    if nonlinear:
-        out["q2_w"], out["q2_b"] = new(Q_DIM, Q_DIM), new(Q_DIM)
-    if g_classes is not None or g_max is not None:
-        out["fc_w"], out["fc_b"] = new(C, K), new(C)
-    g = _native.AggGrads(*[(out[k].data_ptr() if k in out else 0)
-                           for k in ("fc_w", "fc_b", "q0_w", "q0_b", "q2_w", "q2_b", "fcc_w", "fcc_b")])
-    g_vals = new(total, Kv) if want_g_vals else None
-    g_feats = new(total, K) if want_g_feats else None
-    off = offsets if offsets is not None else offsets_tensor(lengths, dev)
-    L = _native.lib()
-    ws = _workspace(dev, L.dsmil_agg_backward_bags_workspace_bytes(n, total, K, Kv, C))
-    with torch.cuda.device(dev):
-        rc = L.dsmil_agg_backward_bags(_ptr(feats), _ptr(vals), _ptr(off), n, total, max(lengths), ctypes.byref(p), _ptr(A),
-                                       _ptr(B), _ptr(idx), _ptr(g_classes), _ptr(g_max), _ptr(g_pred), _ptr(g_A), _ptr(g_B),
-                                       ctypes.byref(g), _ptr(g_vals), _ptr(row_map), _ptr(ws), ws.numel(), _stream(dev),
-                                       _ptr(g_feats))
-    _native.check(rc, "dsmil_agg_backward_bags")
-    del keep
-    if want_g_feats:
-        out["feats"] = g_feats
-    if want_g_vals:
-        out["vals"] = g_vals
-    return out
+    return _agg_backward(lengths, offsets, feats, w, A, B, idx, g_pred, g_classes, g_A, g_B, vals, nonlinear, want_g_vals,
+                         g_max, row_map, want_g_feats)
 
 
 def agg_train_step(feats, label, params, exp_avg, exp_avg_sq, step, lr, betas, eps, weight_decay, nonlinear=True,
@@ -782,34 +744,32 @@ RESNET_MAX_ABS_WEIGHT = 100.0   # < 65504 / (2^8 * 2.25): see _packed_resnet_wei
 def _packed_resnet_weights(convs, depth=18, precision=0):
     """Device buffer with the non-stem conv weights re-laid-out for the kernels (dsmil_resnet_pack:
     Winograd-transformed or [tap][Cout][Cin]).  Cached per weight set; rebuilt when any tensor was
-    modified in place (``_version``), re-assigned or moved (``data_ptr``).  The entry keeps the source
-    tensors alive: a freed weight's address cannot come back as a different model's weight."""
+    modified in place (``_version``), re-assigned or moved (``data_ptr``) — _cached."""
     dev = convs[0].device
     key = (str(dev), depth, int(precision)) + tuple(_tkey(w) for w in convs)
-    ent = _pack_cache.get(key)
-    if ent is not None:
-        ent[3].wait(dev, ent[0])
-        return ent[0]
-    L = _native.lib()
-    nbytes = L.dsmil_resnet_packed_bytes_ex(depth, int(precision))
-    if nbytes == 0:
-        raise ValueError(f"precision {precision} is not implemented for a depth-{depth} trunk "
-                         "(the bf16-activation trunk: ResNet-18 / 34 with InstanceNorm)")
-    buf = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
-    keep = [_f32c(w.detach(), "conv weight") for w in convs]
-    # The conv operands are cut into fp16 planes of the 2^8-scaled weights (csrc/resnet_fwd.hip, EMB_WSHIFT); a Winograd
-    # weight transform grows a 3x3 kernel by at most 2.25x, so |w| must stay below 65504 / (256 * 2.25) = 113.7 or a plane
-    # overflows to inf.  Checked ONCE per weight set (this function is cached on the weights' versions): one host read.
-    wmax = float(torch.stack([w.abs().amax() for w in keep]).amax())
-    if not wmax < RESNET_MAX_ABS_WEIGHT:   # (also catches NaN)
-        raise ValueError(f"conv weight magnitude {wmax:g} is outside the native embedder's range (|w| < {RESNET_MAX_ABS_WEIGHT:g}: "
-                         "its operands are fp16 planes of the 2^8-scaled weights)")
-    arr = (ctypes.c_void_p * len(keep))(*[t.data_ptr() for t in keep])
-    with torch.cuda.device(dev):
-        rc = L.dsmil_resnet_pack_ex(depth, arr, _ptr(buf), int(precision), _stream(dev))
-    _native.check(rc, "dsmil_resnet_pack_ex")
-    _pack_cache.put(key, (buf, keep, list(convs), _Ready(dev)))
-    return buf
+    keep = []   # the contiguous fp32 weights the pack call reads: the entry holds them next to the source tensors
+
+    def make():
+        L = _native.lib()
+        nbytes = L.dsmil_resnet_packed_bytes_ex(depth, int(precision))
+        if nbytes == 0:
+            raise ValueError(f"precision {precision} is not implemented for a depth-{depth} trunk "
+                             "(the bf16-activation trunk: ResNet-18 / 34 with InstanceNorm)")
+        buf = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
+        keep.extend(_f32c(w.detach(), "conv weight") for w in convs)
+        # The conv operands are cut into fp16 planes of the 2^8-scaled weights (csrc/resnet_fwd.hip, EMB_WSHIFT); a Winograd
+        # weight transform grows a 3x3 kernel by at most 2.25x, so |w| must stay below 65504 / (256 * 2.25) = 113.7 or a plane
+        # overflows to inf.  Checked ONCE per weight set (this function is cached on the weights' versions): one host read.
+        wmax = float(torch.stack([w.abs().amax() for w in keep]).amax())
+        if not wmax < RESNET_MAX_ABS_WEIGHT:   # (also catches NaN)
+            raise ValueError(f"conv weight magnitude {wmax:g} is outside the native embedder's range (|w| < {RESNET_MAX_ABS_WEIGHT:g}: "
+                             "its operands are fp16 planes of the 2^8-scaled weights)")
+        arr = (ctypes.c_void_p * len(keep))(*[t.data_ptr() for t in keep])
+        with torch.cuda.device(dev):
+            rc = L.dsmil_resnet_pack_ex(depth, arr, _ptr(buf), int(precision), _stream(dev))
+        _native.check(rc, "dsmil_resnet_pack_ex")
+        return (buf,)
+    return _cached(_pack_cache, key, dev, (keep, list(convs)), make)[0]
 
 
 _bn_cache = _LRU()
@@ -822,25 +782,21 @@ def _folded_bn(norms, dev):
     parameter / buffer versions)."""
     key = (str(dev),) + tuple((id(n), _tkey(n.running_mean), _tkey(n.running_var), _tkey(n.weight), _tkey(n.bias), n.eps)
                               for n in norms)
-    hit = _bn_cache.get(key)
-    if hit is not None:
-        hit[3].wait(dev, hit[0], hit[1])
-        return hit[0], hit[1]
-    ms, rs = [], []
-    for n in norms:
-        var = n.running_var.detach().to(dev, torch.float64)
-        mean = n.running_mean.detach().to(dev, torch.float64)
-        w = n.weight.detach().to(dev, torch.float64) if n.weight is not None else torch.ones_like(var)
-        b = n.bias.detach().to(dev, torch.float64) if n.bias is not None else torch.zeros_like(var)
-        r = w / torch.sqrt(var + n.eps)
-        if bool((r == 0).any()):
-            raise NotImplementedError("a BatchNorm channel with weight 0 cannot be folded into (x - m) * r")
-        ms.append(mean - b / r)
-        rs.append(r)
-    m = torch.cat(ms).to(torch.float32).contiguous()
-    r = torch.cat(rs).to(torch.float32).contiguous()
-    _bn_cache.put(key, (m, r, list(norms), _Ready(dev)))   # the modules stay alive: their ids stay unique
-    return m, r
+
+    def make():
+        ms, rs = [], []
+        for n in norms:
+            var = n.running_var.detach().to(dev, torch.float64)
+            mean = n.running_mean.detach().to(dev, torch.float64)
+            w = n.weight.detach().to(dev, torch.float64) if n.weight is not None else torch.ones_like(var)
+            b = n.bias.detach().to(dev, torch.float64) if n.bias is not None else torch.zeros_like(var)
+            r = w / torch.sqrt(var + n.eps)
+            if bool((r == 0).any()):
+                raise NotImplementedError("a BatchNorm channel with weight 0 cannot be folded into (x - m) * r")
+            ms.append(mean - b / r)
+            rs.append(r)
+        return torch.cat(ms).to(torch.float32).contiguous(), torch.cat(rs).to(torch.float32).contiguous()
+    return _cached(_bn_cache, key, dev, list(norms), make)   # (m, r); the modules stay alive: their ids stay unique
 
 
 def resnet18in_forward(x, convs, fc_w=None, fc_b=None, bn_norms=None, precision="fp32"):
