@@ -616,7 +616,9 @@ inline size_t pack_off(const Arch& A, int ci) {   // bytes
     for (int i = 1; i < ci; ++i) e += (conv_packed_elems(A.specs[i]) + 127) & ~(size_t)127;
     return e * 2;
 }
-inline int pack_all(const Arch& A, const float* const* conv_w, unsigned short* dst, hipStream_t st, bool f16) {
+// kind: the trunk's 16-bit element type (Form::trunk of resnet_fwd.hip): 1 = bf16, 2 = fp16
+inline int pack_all(const Arch& A, const float* const* conv_w, unsigned short* dst, hipStream_t st, int kind) {
+    const bool f16 = kind == 2;
     for (int i = 1; i < A.nconv; ++i) {
         const ConvSpec& s = A.specs[i];
         if (!v2_conv(s) && !g2_conv(s)) return DSMIL_E_UNSUPPORTED;
@@ -759,8 +761,8 @@ inline int trunk_t(hipStream_t st, const Arch& A, const float* x0, const unsigne
     return DSMIL_OK;
 }
 
-inline int trunk(hipStream_t st, const Arch& A, const float* x0, const unsigned short* wpk, void* scratch, int B, int Hp, int Wp, float* feats, bool f16) {
-    return f16 ? trunk_t<true>(st, A, x0, wpk, scratch, B, Hp, Wp, feats) : trunk_t<false>(st, A, x0, wpk, scratch, B, Hp, Wp, feats);
+inline int trunk(hipStream_t st, const Arch& A, const float* x0, const unsigned short* wpk, void* scratch, int B, int Hp, int Wp, float* feats, int kind) {
+    return kind == 2 ? trunk_t<true>(st, A, x0, wpk, scratch, B, Hp, Wp, feats) : trunk_t<false>(st, A, x0, wpk, scratch, B, Hp, Wp, feats);
 }
 
 }  // namespace b16

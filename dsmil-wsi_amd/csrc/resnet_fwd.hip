@@ -1,8 +1,10 @@
 // ResNet-18 (InstanceNorm2d, fc = Identity) patch embedder, forward — hand-written HIP for gfx950.
 //
 // Replaces the torchvision backbone behind dsmil.IClassifier (reference call sites:
-// compute_feats.py:146-170,211; dsmil.py:21-25).  fp32 end to end on exact-f32 MFMA
-// (v_mfma_f32_32x32x2_f32), activations NHWC in HBM.
+// compute_feats.py:146-170,211; dsmil.py:21-25).  fp32 activations (NHWC in HBM), norms and accumulation; every conv operand is
+// cut into two fp16 planes and multiplied as three plane products on fp16 MFMA (v_mfma_f32_32x32x16_f16; "operand forms" below).
+// The exact-f32 MFMA form (v_mfma_f32_32x32x2_f32: k_conv, k_stem, k_conv_wino) exists in experiment builds only; the opt-in
+// reduced precisions are the one-plane form and the 16-bit-activation trunk of resnet_b16.h.
 //
 // InstanceNorm cannot be folded into the conv weights (per-image, per-channel statistics over
 // H x W, eps = 1e-5, biased variance, no affine).  Each convolution therefore writes its RAW output
@@ -38,12 +40,8 @@
 
 namespace {
 
-// Experiment builds (-DDSMIL_EXPERIMENTS) read ablation knobs from the environment, once per process.
+// Experiment builds (-DDSMIL_EXPERIMENTS) read ablation knobs from the environment, once per process (struct Expt, host part).
 #ifdef DSMIL_EXPERIMENTS
-inline int expt_env(const char* name) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : 0;
-}
 #define DSMIL_WEXPT_ON(a, bit) (((a).expt & (bit)) != 0)
 #else
 #define DSMIL_WEXPT_ON(a, bit) false
@@ -1998,6 +1996,8 @@ __global__ void k_pack_conv(const float* __restrict__ w, float* __restrict__ out
 }
 
 // ---- host ----------------------------------------------------------------------------------
+// One decision in one place ("Embedder host code"): Expt = the experiment knobs of the process, Form = the operand
+// forms of a call, plan_conv / plan_stem = everything the pack, the size queries and the launches need to know about a conv.
 struct ConvSpec { int cout, cin, ks, stride, pad; };
 // torchvision state_dict order of the bias-free convolutions of a BasicBlock ResNet:
 // stem, then per block conv1, conv2 and — first block of layers 2..4 — downsample.0.
@@ -2005,7 +2005,11 @@ struct ConvSpec { int cout, cin, ks, stride, pad; };
 // depth 50 = Bottleneck blocks [3,4,6,3] (53 convs), depth 101 = [3,4,23,3] (104 convs): per block conv1 1x1,
 // conv2 3x3 (stride on conv2: torchvision's ResNet v1.5), conv3 1x1 to 4x the width, and — first block of every
 // layer — downsample.0 1x1; feature width 2048 (compute_feats.py:161-167).
-struct Arch { int depth, nblk[4], nconv, bottleneck, feat; ConvSpec specs[112]; };
+// lvl[i] / normed[i]: conv i reads a map of layer lvl[i]'s resolution (1..4; the stem: 0), raw with its producer's statistics
+// (normed: the conv applies norm + ReLU while staging) or materialised.  noff[i]: offset of conv i's norm in the concatenated
+// per-channel arrays of the frozen-statistics variant.
+constexpr int MAX_CONVS = 112;
+struct Arch { int depth, nblk[4], nconv, bottleneck, feat; ConvSpec specs[MAX_CONVS]; int lvl[MAX_CONVS]; bool normed[MAX_CONVS]; int noff[MAX_CONVS + 1]; };
 Arch make_arch(int depth) {
     Arch a;
     a.depth = depth;
@@ -2013,29 +2017,33 @@ Arch make_arch(int depth) {
     a.bottleneck = depth >= 50;
     for (int l = 0; l < 4; ++l) a.nblk[l] = depth == 18 ? n18[l] : depth == 101 ? n101[l] : n34[l];
     int n = 0;
-    a.specs[n++] = ConvSpec{64, 3, 7, 2, 3};
+    auto add = [&](ConvSpec s, int lvl, bool normed) { a.specs[n] = s; a.lvl[n] = lvl; a.normed[n] = normed; ++n; };
+    add(ConvSpec{64, 3, 7, 2, 3}, 0, false);
     int cin = 64;
     for (int l = 0; l < 4; ++l) {
         const int c = 64 << l;
         for (int b = 0; b < a.nblk[l]; ++b) {
+            const int in = (l > 0 && b == 0) ? l : l + 1;   // the first block of layers 2..4 reads the previous layer's map
             if (a.bottleneck) {
                 const int stride = (l > 0 && b == 0) ? 2 : 1;
-                a.specs[n++] = ConvSpec{c, cin, 1, 1, 0};
-                a.specs[n++] = ConvSpec{c, c, 3, stride, 1};
-                a.specs[n++] = ConvSpec{4 * c, c, 1, 1, 0};
-                if (b == 0) a.specs[n++] = ConvSpec{4 * c, cin, 1, stride, 0};
+                add(ConvSpec{c, cin, 1, 1, 0}, in, false);
+                add(ConvSpec{c, c, 3, stride, 1}, in, true);
+                add(ConvSpec{4 * c, c, 1, 1, 0}, l + 1, true);
+                if (b == 0) add(ConvSpec{4 * c, cin, 1, stride, 0}, in, false);
                 cin = 4 * c;
             } else {
                 const bool down = l > 0 && b == 0;
-                a.specs[n++] = ConvSpec{c, cin, 3, down ? 2 : 1, 1};
-                a.specs[n++] = ConvSpec{c, c, 3, 1, 1};
-                if (down) a.specs[n++] = ConvSpec{c, cin, 1, 2, 0};
+                add(ConvSpec{c, cin, 3, down ? 2 : 1, 1}, in, false);
+                add(ConvSpec{c, c, 3, 1, 1}, l + 1, true);
+                if (down) add(ConvSpec{c, cin, 1, 2, 0}, in, false);
                 cin = c;
             }
         }
     }
     a.nconv = n;
     a.feat = cin;
+    a.noff[0] = 0;
+    for (int i = 0; i < n; ++i) a.noff[i + 1] = a.noff[i] + a.specs[i].cout;
     return a;
 }
 const Arch* arch_of(int depth) {
@@ -2053,89 +2061,61 @@ inline void allow_lds(const void* kern, size_t bytes) { (void)dsmil_lds::allow(k
 // Needs Arch / ConvSpec / allow_lds, lives in namespace b16.
 #include "resnet_b16.h"
 namespace {
-thread_local int g_b16_trunk = 0;    // precision 2 / 3 on THIS host thread: one-plane stem, then b16::trunk on bf16 (1) / fp16 (2) activations
-inline bool stem_fuse() {   // expt builds: DSMIL_STEM_FUSE=0 keeps the stem + k_norm_relu_maxpool pair (A/B, bit-identity test)
+
+// ---- Expt: the ablation knobs of experiment builds (-DDSMIL_EXPERIMENTS), read from the environment once per process.  The
+// product library has none: all zero, no environment read.
+//   DSMIL_STEM_FUSE=0     keep the stem + k_norm_relu_maxpool pair (A/B, bit-identity test)
+//   DSMIL_NO_WINO=1       every conv direct
+//   DSMIL_WINO            h3 (default) | s6 | s9 | f32: MFMA form of the Winograd convs: h3 = fp16 MFMA over two-plane cuts,
+//                         three products (PlaneProducts, round 5); s6 / s9 = bf16 MFMA over exact three-plane cuts with the 6
+//                         largest / all 9 plane products; f32 = v_mfma_f32_32x32x2_f32
+//   DSMIL_CONV            h3 (default) | s6 | f32: the same for the DIRECT convs (strided 3x3, 1x1) and the stem (k_conv_s6 /
+//                         k_stem_s6, weights cut at pack time; f32 = k_conv / k_stem)
+//   DSMIL_WINO_NARROW=1   keep the 64-cout workgroups everywhere (A/B)
+//   DSMIL_WINO_KERNEL     unit (k_conv_wino_s3 everywhere) | w1 (default: k_conv_wino_w1 on the 128-cout layers) | pp (persistent
+//                         role-split k_conv_wino_pp) | alt (k_conv_wino_alt, 128-cout layers)
+//   DSMIL_WINO_EXPT       ablation bits of the Winograd kernels (timing only)
+//   DSMIL_S6_TILE         44 | 42 | 24 | 22 forces a direct-conv tile wherever the channel count allows it (A/B)
+//   DSMIL_WINO_TRACE=k    trace builds: the k-th Winograd launch of the process records stamps (tools_stamp_wino.py)
+enum { WK_DEFAULT = 0, WK_PP = 1, WK_ALT = 2, WK_W1 = 3, WK_UNIT = 4 };
+struct Expt { int stem_unfused, no_wino, wino_form, conv_form, wino_narrow, wino_kernel, wino_expt, s6_tile, wino_trace; };
+const Expt& expt() {
+    static const Expt knobs = [] {
+        Expt x{};
 #ifdef DSMIL_EXPERIMENTS
-    static const int off = [] { const char* e = getenv("DSMIL_STEM_FUSE"); return (e && !strcmp(e, "0")) ? 1 : 0; }();
-    return !off;
-#else
-    return true;
+        auto is = [](const char* name, const char* v) { const char* e = getenv(name); return e && !strcmp(e, v); };
+        auto num = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; };
+        x.stem_unfused = is("DSMIL_STEM_FUSE", "0");
+        x.no_wino = num("DSMIL_NO_WINO");
+        x.wino_form = is("DSMIL_WINO", "f32") ? -1 : is("DSMIL_WINO", "s9") ? 9 : is("DSMIL_WINO", "s6") ? 6 : 0;   // 0: the product form
+        x.conv_form = is("DSMIL_CONV", "f32") ? -1 : is("DSMIL_CONV", "s6") ? 6 : 0;
+        x.wino_narrow = num("DSMIL_WINO_NARROW");
+        x.wino_kernel = is("DSMIL_WINO_KERNEL", "pp") ? WK_PP : is("DSMIL_WINO_KERNEL", "alt") ? WK_ALT
+                      : is("DSMIL_WINO_KERNEL", "w1") ? WK_W1 : is("DSMIL_WINO_KERNEL", "unit") ? WK_UNIT : WK_DEFAULT;
+        x.wino_expt = num("DSMIL_WINO_EXPT");
+        x.s6_tile = num("DSMIL_S6_TILE");
+        x.wino_trace = num("DSMIL_WINO_TRACE");
 #endif
-}
-inline bool use_wino(const ConvSpec& s) {  // 3x3 stride-1 convs run as Winograd F(2x2,3x3)
-#ifdef DSMIL_EXPERIMENTS
-    static const int off = expt_env("DSMIL_NO_WINO");
-#else
-    constexpr int off = 0;
-#endif
-    return !off && s.ks == 3 && s.stride == 1 && s.pad == 1 && s.cin % WK == 0 && s.cout % 64 == 0;
-}
-// Experiment builds: DSMIL_WINO = h3 (default) | s6 | s9 | f32: which MFMA form the Winograd convs use (read once per process;
-// the packed weights and the kernels must agree): h3 = fp16 MFMA over two-plane cuts, three products (PlaneProducts, round 5);
-// s6 / s9 = bf16 MFMA over exact three-plane cuts with the 6 largest / all 9 plane products; f32 = v_mfma_f32_32x32x2_f32
-// dsmil_resnet_pack_ex / dsmil_resnet_forward_ex with precision = 1 (the opt-in reduced-precision path): the form of THIS call on
-// THIS host thread; 0 = the process form below
-thread_local int g_form_override = 0;
-struct FormOverride {
-    int saved;
-    explicit FormOverride(int np) : saved(g_form_override) { g_form_override = np; }
-    ~FormOverride() { g_form_override = saved; }
-};
-inline int wino_form() {
-    if (g_form_override) return g_form_override;
-#ifdef DSMIL_EXPERIMENTS
-    static const int form = [] {
-        const char* e = getenv("DSMIL_WINO");
-        if (e && !strcmp(e, "f32")) return 0;
-        if (e && !strcmp(e, "s9")) return 9;
-        if (e && !strcmp(e, "s6")) return 6;
-        return NPD;
+        return x;
     }();
-    return form;
-#else
-    return NPD;   // the product library has one form; the alternatives are selectable in experiment builds only
-#endif
+    return knobs;
 }
-inline bool wino_s3() { return wino_form() != 0; }
+
+// ---- Form: the operand forms of ONE call, passed down explicitly: plane products per MAC of the Winograd and of the direct
+// convs (PlaneProducts; 0 = the f32-MFMA form of experiment builds) and the trunk behind the stem (0 = this file's fp32
+// activations, 1 / 2 = b16::trunk on bf16 / fp16 activations).  precision as in dsmil_resnet_pack_ex / _forward_ex: 0 = the
+// process form (NPD unless an experiment knob says otherwise), 1 = one fp16 plane, 2 / 3 = one-plane stem + the b16 trunk.  A
+// pack and a forward of the same precision get the same Form, hence the same weight layout.
+struct Form { int wino_np, conv_np, trunk; };
+Form make_form(int precision, const Expt& e) {
+    if (precision >= 1) return Form{1, 1, precision >= 2 ? precision - 1 : 0};
+    return Form{e.wino_form < 0 ? 0 : e.wino_form ? e.wino_form : NPD, e.conv_form < 0 ? 0 : e.conv_form ? e.conv_form : NPD, 0};
+}
+
 #ifndef WIDE_UC
 #define WIDE_UC false
 #endif
 #define WIDE_UD (WIDE_UC ? 3 : 2)
-inline bool wino_wide() {   // expt builds: DSMIL_WINO_NARROW=1 keeps the 64-cout workgroups everywhere (A/B)
-#ifdef DSMIL_EXPERIMENTS
-    static const int narrow = expt_env("DSMIL_WINO_NARROW");
-    return !narrow;
-#else
-    return true;
-#endif
-}
-#ifdef DSMIL_EXPERIMENTS
-// experiment builds: DSMIL_WINO_KERNEL = unit (k_conv_wino_s3 everywhere) | w1 (default: k_conv_wino_w1 on the 128-cout layers) |
-// pp (persistent role-split k_conv_wino_pp) | alt (k_conv_wino_alt, 128-cout layers)
-inline int wino_expt_kernel() {
-    static const int k = [] {
-        const char* e = getenv("DSMIL_WINO_KERNEL");
-        return (e && !strcmp(e, "pp")) ? 1 : (e && !strcmp(e, "alt")) ? 2 : (e && !strcmp(e, "w1")) ? 3 : (e && !strcmp(e, "unit")) ? 4 : 0;
-    }();
-    return k;
-}
-#endif
-// the packed Winograd weights are tiled ([Cout/32][C/16][16][3][32][16]) for k_conv_wino_w1 and k_conv_wino_s3; the two
-// experiment kernels (wino_variants.h) keep the position-major layout
-inline bool wino_tiled() {
-#ifdef DSMIL_EXPERIMENTS
-    return wino_expt_kernel() != 1 && wino_expt_kernel() != 2;
-#else
-    return true;
-#endif
-}
-// which Winograd convs run on k_conv_wino_w1 (one wave per SIMD, tiled weights): the packing and the launch must agree
-inline bool use_w1(const ConvSpec& s) {
-#ifdef DSMIL_EXPERIMENTS
-    if (wino_expt_kernel() != 0 && wino_expt_kernel() != 3) return false;   // DSMIL_WINO_KERNEL = unit | pp | alt: the older kernels
-#endif
-    return wino_s3() && s.cout % 128 == 0;
-}
 #ifdef DSMIL_TRACE
 constexpr size_t WINO_TRACE_WORDS = 4 * 2 * 256 * 8;
 inline unsigned long long* wino_trace_buffer() {
@@ -2148,44 +2128,6 @@ inline unsigned long long* wino_trace_buffer() {
     return buf;
 }
 #endif
-// Experiment builds: DSMIL_CONV = h3 (default) | s6 | f32: MFMA form of the DIRECT convs (strided 3x3, 1x1) and the stem: h3 =
-// fp16 MFMA over two-plane cuts, three products; s6 = bf16 MFMA over exact three-plane cuts, 6 plane products (both k_conv_s6 /
-// k_stem_s6; weights cut at pack time); f32 = v_mfma_f32_32x32x2_f32 (k_conv / k_stem).  Read once per process; the packed
-// weights and the kernels must agree.
-inline int conv_np() {   // plane products of the direct convs (0 = the f32 form)
-    if (g_form_override) return g_form_override;
-#ifdef DSMIL_EXPERIMENTS
-    static const int np = [] {
-        const char* e = getenv("DSMIL_CONV");
-        if (e && !strcmp(e, "f32")) return 0;
-        if (e && !strcmp(e, "s6")) return 6;
-        return NPD;
-    }();
-    return np;
-#else
-    return NPD;
-#endif
-}
-inline bool conv_s6() { return conv_np() != 0; }
-// floats of conv i in the packed buffer: 16 transform positions for Winograd convs (x 3 bf16 planes = 1.5
-// floats per weight in the s3 form), ks*ks taps otherwise
-inline long long wsize(const Arch& A, int i) {
-    const ConvSpec& s = A.specs[i];
-    if (use_wino(s)) return (long long)s.cout * s.cin * (wino_s3() ? 24 : 16);
-    const long long n = (long long)s.cout * s.cin * s.ks * s.ks;
-    return conv_s6() ? n * 3 / 2 : n;   // three bf16 planes = 1.5 floats per weight
-}
-inline size_t pack_offset(const Arch& A, int i) {  // floats; conv 0 (stem) is used unpacked
-    size_t o = 0;
-    for (int j = 1; j < i; ++j) o += (size_t)wsize(A, j);
-    return o;
-}
-// offset of conv i's norm in the concatenated per-channel arrays of the frozen-statistics variant
-inline int norm_offset(const Arch& A, int i) {
-    int o = 0;
-    for (int j = 0; j < i; ++j) o += A.specs[j].cout;
-    return o;
-}
 inline int outdim(int x, int ks, int s, int p) { return (x + 2 * p - ks) / s + 1; }
 
 struct Dims { int H1, W1, Hp, Wp, h[5], w[5]; };
@@ -2232,6 +2174,146 @@ void wino_shape(int B, int TY, int TX, int& IB, int& TYB, int& TXB, int cb = 0, 
             }
     }
 }
+// the units of a Winograd conv over B maps of H x W; rounds = true: chosen for k_conv_wino_w1's rounds of workgroups
+struct WinoUnit { int TY, TX, IB, TYB, TXB, nby, nbx, PB; };
+WinoUnit wino_unit(int B, int H, int W, bool rounds, int cout, int cin) {
+    WinoUnit u;
+    u.TY = (H + 1) / 2; u.TX = (W + 1) / 2;
+    if (rounds) wino_shape(B, u.TY, u.TX, u.IB, u.TYB, u.TXB, cout >= 128 ? cout / 128 : 1, cin / 16);
+    else wino_shape(B, u.TY, u.TX, u.IB, u.TYB, u.TXB);
+    u.nby = (u.TY + u.TYB - 1) / u.TYB; u.nbx = (u.TX + u.TXB - 1) / u.TXB; u.PB = u.nby * u.nbx;
+    return u;
+}
+// elements of the statistics partials: Winograd (cnt, mean, M2) per (image, unit, output-row half, channel); direct convs
+// (mean, M2) per (32-pixel tile, slot, channel) with a slot per image a tile can touch
+inline long long wino_part_elems(int B, const WinoUnit& u, int cout) { return (long long)B * u.PB * 2 * cout * 3; }
+inline int flat_nslots(int HW) { return 31 / HW + 2; }
+inline long long flat_part_elems(int B, int HW, int cout) { return (((long long)B * HW + 31) / 32) * flat_nslots(HW) * cout * 2; }
+
+// ---- ConvPlan: what one conv runs on.  The fields up to `wfloats` depend on (spec, form, expt) alone — they are all the pack
+// and the packed-size queries need, and plan_conv fills only them when B = 0; the rest describes the launch on B maps of H x W.
+enum ConvKern { CK_W1, CK_UNIT, CK_WIDE, CK_PP, CK_ALT, CK_WINO_F32, CK_S6, CK_F32 };
+struct ConvPlan {
+    ConvKern kern;
+    bool wino;             // Winograd F(2x2,3x3) (CK_W1 .. CK_WINO_F32) or direct (CK_S6, CK_F32)
+    int np;                // plane products per MAC (PlaneProducts), 0 = the f32 forms
+    bool tiled;            // Winograd weights [Cout/32][C/16][16][3][32][16] (k_conv_wino_w1 / _s3) or position-major (the others)
+    long long wfloats;     // floats of the packed weights: 16 transform positions (x 3 bf16 planes = 1.5 floats per weight in the
+                           // plane forms) for Winograd convs, ks*ks taps otherwise
+    bool norm;             // the input is raw: apply its producer's statistics + ReLU while staging
+    int tile;              // direct convs, pixels x channels per workgroup: 44 = 128 x 128, 42 = 128 x 64, 24 = 64 x 256, 22 = 64 x 128,
+                           // 21 = 64 x 64 (the kernels' <MW, NT> template digits)
+    int abl, wexpt;        // experiment builds: compile-time ablation of k_conv_wino_w1, ablation bits for the kernel (WinoArgs.expt)
+    WinoUnit u;            // Winograd unit shape
+    int Ho, Wo, nslots;    // direct convs: output map, partial slots per 32-pixel tile
+    long long Mtot;
+    dim3 grid;
+    unsigned block;
+    size_t lds;
+    long long part_elems;  // statistics partials this conv writes
+};
+ConvPlan plan_conv(const ConvSpec& s, int B, int H, int W, bool norm, const Form& f, const Expt& e) {
+    ConvPlan p{};
+    p.wino = !e.no_wino && s.ks == 3 && s.stride == 1 && s.pad == 1 && s.cin % WK == 0 && s.cout % 64 == 0;
+    p.np = p.wino ? f.wino_np : f.conv_np;
+    p.norm = norm;
+    if (p.wino) {
+        // k_conv_wino_w1 (one wave per SIMD, 128 couts per workgroup) wherever the channel count allows it; the older kernels by
+        // DSMIL_WINO_KERNEL.  pp / alt exist in the bf16 forms only (and keep their position-major weights in every form)
+        const bool older = e.wino_kernel != WK_DEFAULT && e.wino_kernel != WK_W1, bf16_form = p.np == 6 || p.np == 9;
+        p.tiled = e.wino_kernel != WK_PP && e.wino_kernel != WK_ALT;
+        p.kern = p.np == 0 ? CK_WINO_F32
+               : e.wino_kernel == WK_PP && bf16_form ? CK_PP
+               : e.wino_kernel == WK_ALT && bf16_form && s.cout % 128 == 0 ? CK_ALT
+               : !older && s.cout % 128 == 0 ? CK_W1
+               : p.np != 1 && older && s.cout % 128 == 0 && !e.wino_narrow ? CK_WIDE : CK_UNIT;
+        p.wfloats = (long long)s.cout * s.cin * (p.np ? 24 : 16);
+    } else {
+        p.kern = p.np ? CK_S6 : CK_F32;
+        const long long n = (long long)s.cout * s.cin * s.ks * s.ks;
+        p.wfloats = p.np ? n * 3 / 2 : n;   // three bf16 planes = 1.5 floats per weight
+    }
+    if (B <= 0) return p;
+    if (p.wino) {
+        // the unit shape is keyed on the layer, not on the kernel: DSMIL_WINO_KERNEL=unit of experiment builds runs the same units
+        // through k_conv_wino_s3, which is what the bit-identity test of the two kernels compares
+        p.u = wino_unit(B, H, W, p.np && s.cout % 128 == 0 && s.cin >= 64, s.cout, s.cin);
+        p.part_elems = wino_part_elems(B, p.u, s.cout);
+        const unsigned units = (unsigned)(((B + p.u.IB - 1) / p.u.IB) * p.u.PB);
+        // k_conv_wino_s3: weights two positions ahead (UD = 2); with NORM the producer statistics are staged through LDS (LS,
+        // +4 KiB: 80 KiB per workgroup, still two per CU)
+        const size_t lds_unit = (size_t)(SV_DW + WRAW_MAX * SRLD) * sizeof(float) + (norm ? 4096 : 0);
+        const size_t lds_two = (size_t)(2 * SV_DW + 2 * WRAW_MAX * SRLD + 1024) * sizeof(float);
+        p.wexpt = p.np && e.wino_kernel == WK_W1 ? 0 : e.wino_expt;   // with w1 named explicitly the ablation bits address that kernel only
+        switch (p.kern) {
+            case CK_W1:    // 1-D grid: the kernel maps it to (unit, cout block) per XCD
+                p.grid = dim3(units * (unsigned)(s.cout / 128)); p.block = 256; p.lds = lds_two + 256 * sizeof(float);
+                p.abl = p.np != 1 ? e.wino_expt : 0;   // (the ablations are instantiated in the product form)
+                break;
+            case CK_UNIT: p.grid = dim3(units, (unsigned)(s.cout / 64)); p.block = 256; p.lds = lds_unit; break;
+            case CK_WIDE: p.grid = dim3(units, (unsigned)(s.cout / 128)); p.block = 512; p.lds = lds_unit; break;
+            case CK_ALT:  p.grid = dim3(units, (unsigned)(s.cout / 128)); p.block = 512; p.lds = lds_two; break;
+            case CK_PP:   // persistent: the launch caps the grid at one workgroup per CU, which walk the (unit, cout tile) items
+                p.grid = dim3(units, (unsigned)(s.cout / 64)); p.block = 512; p.lds = lds_two; break;
+            default:      p.grid = dim3(units, (unsigned)(s.cout / 64)); p.block = 256; p.lds = (size_t)(2 * WTILE + 2 * WRAW_MAX * WLD) * sizeof(float);
+        }
+        return p;
+    }
+    p.Ho = outdim(H, s.ks, s.stride, s.pad); p.Wo = outdim(W, s.ks, s.stride, s.pad);
+    const int HW = p.Ho * p.Wo;
+    p.nslots = flat_nslots(HW);
+    p.Mtot = (long long)B * HW;
+    p.part_elems = flat_part_elems(B, HW, s.cout);
+    p.block = 256;
+    if (p.kern == CK_S6) {
+        // tile = BM pixels x TN output channels per 256-thread workgroup: 128 x 128, 128 x 64, 64 x 256 or 64 x 128.
+        // Measured per layer (tools/s6_shapes.sh, bs 256): the activation rows are the expensive operand to stage (im2col
+        // gather, producer's IN + ReLU, plane cut; the weights are a plain copy), so the tile is as short in pixels and as wide
+        // in channels as the layer allows — 64 x 256, else 64 x 128 — which also quantises better (l4.0.conv1: 392 workgroups
+        // in ONE round instead of 784 on 768 slots; 195 us against 288).  Six direct convs of ResNet-18: 850 -> 726 us.
+        p.tile = s.cout % 256 == 0 ? 24 : s.cout % 128 == 0 ? 22 : 42;
+        if (e.s6_tile == 44 && s.cout % 128 == 0 && p.np != 1) p.tile = 44;   // (the one-plane form has no 128 x 128 tile: 128 x 64)
+        if (e.s6_tile == 42 || (e.s6_tile == 44 && s.cout % 128 == 0 && p.np == 1)) p.tile = 42;
+        if (e.s6_tile == 24 && s.cout % 256 == 0) p.tile = 24;
+        if (e.s6_tile == 22 && s.cout % 128 == 0) p.tile = 22;
+    } else {
+        // DSMIL_CONV=f32: 128x64 for Cout = 64; 128x128 while that yields >= 4 workgroups per CU; 64x64 (finer units, less tail
+        // quantisation) for the small late-layer maps
+        const long long blocks128 = ((p.Mtot + 127) / 128) * (s.cout / 128 > 0 ? s.cout / 128 : 1);
+        p.tile = s.cout == 64 ? 42 : blocks128 >= 1024 ? 44 : 21;
+    }
+    const int BM = p.tile >= 40 ? 128 : 64, TN = p.tile == 24 ? 256 : p.tile == 44 || p.tile == 22 ? 128 : 64;
+    p.grid = dim3((unsigned)((p.Mtot + BM - 1) / BM), (unsigned)(s.cout / TN));
+    p.lds = p.kern == CK_S6 ? (size_t)2 * (BM + TN) * S6LD * 4 : (size_t)(2 * BM * LDK + 2 * TN * LDK) * 4;
+    return p;
+}
+
+// ---- StemPlan: the 7x7 stem follows the direct convs' form.  InstanceNorm trunks: the max-pool is fused into the stem (a frozen
+// BatchNorm may have a negative scale, for which the pool needs the window MINIMUM too: that path keeps the raw map +
+// k_norm_relu_maxpool)
+struct StemPlan { int np; bool fuse; int tx, ty, nparts; dim3 grid; unsigned block; size_t lds; };
+StemPlan plan_stem(const Dims& d, int B, bool frozen_norm, const Form& f, const Expt& e) {
+    StemPlan p{};
+    p.np = f.conv_np;
+    p.fuse = p.np && !frozen_norm && !e.stem_unfused;
+    p.tx = (d.W1 + 15) / 16; p.ty = p.np ? (d.H1 + SS_TR - 1) / SS_TR : (d.H1 + 7) / 8;
+    p.nparts = p.tx * p.ty * (p.np ? 8 : 4);
+    p.grid = dim3((unsigned)p.ty, (unsigned)B);
+    p.block = p.np ? 512 : 256;
+    p.lds = !p.np ? 0 : p.fuse ? SS_LDS + SS_POOL_LDS : SS_LDS;
+    return p;
+}
+
+// floats of conv i's packed weights in front of it (conv 0, the stem, is packed behind the others: off[nconv])
+struct PackOffsets { size_t off[MAX_CONVS + 1]; };
+PackOffsets pack_offsets(const Arch& A, const Form& f, const Expt& e) {
+    PackOffsets o;
+    o.off[0] = o.off[1] = 0;
+    for (int i = 1; i < A.nconv; ++i) o.off[i + 1] = o.off[i] + (size_t)plan_conv(A.specs[i], 0, 0, 0, false, f, e).wfloats;
+    return o;
+}
+// the packed image ends with the stem's three bf16 planes (k_stem_s6; conv 0 keeps its raw OIHW argument for the f32 form)
+size_t packed_bytes(const Arch& A, const Form& f, const Expt& e) { return (pack_offsets(A, f, e).off[A.nconv] + SS_WIMG / 2) * sizeof(float); }
 
 struct RWs {
     size_t y0, buf[5], stat[4][2], part, total;  // stat[k] = {mean, rstd}
@@ -2249,31 +2331,20 @@ RWs rws_layout(int B, int H, int W, int depth = 18) {
     for (int i = 0; i < 5; ++i) { r.buf[i] = o; o = al256(o + (size_t)r.act_elems * 4); }
     for (int k = 0; k < 4; ++k)
         for (int j = 0; j < 2; ++j) { r.stat[k][j] = o; o = al256(o + (size_t)B * 512 * exp * 4); }
-    // partials: stem (n, tiles*4, 64, 3) or flat (tiles32, nslots, C, 2); take the max over layers
-    // per (image, tile, wave): 8 x 16-pixel tiles x 4 waves (k_stem) or 16 x 16 x 8 waves (k_stem_s6), whichever is more
+    // Partials: the largest any conv of any form can need.  The workspace size is part of the ABI's observable behaviour (callers
+    // cache it) and must not depend on the form or the experiment knobs of a call, so this sizes per LAYER for every kind of
+    // conv a form could run there — both Winograd unit shapes, a direct conv at the layer's full width — rather than asking the
+    // plans of one form; the forward checks each plan against it.
+    // stem: per (image, tile, wave): 8 x 16-pixel tiles x 4 waves (k_stem) or 16 x 16 x 8 waves (k_stem_s6), whichever is more
     const long long stem_rows = std::max<long long>(((d.H1 + 7) / 8) * 4, ((d.H1 + SS_TR - 1) / SS_TR) * 8);
-    const long long stem_parts = (long long)B * stem_rows * ((d.W1 + 15) / 16) * 64 * 3;
-    long long mx = stem_parts;
+    long long mx = (long long)B * stem_rows * ((d.W1 + 15) / 16) * 64 * 3;
     for (int l = 1; l <= 4; ++l) {
         const int Cw = 64 << (l - 1);
         // direct convs of layer l: outputs at this layer's resolution (up to Cw*exp channels) and, for a Bottleneck's
         // conv1 in a strided block, at the previous layer's resolution (Cw channels)
-        for (int prev = 0; prev < (A.bottleneck && l > 1 ? 2 : 1); ++prev) {
-            const int HW = d.h[l - prev] * d.w[l - prev];
-            const int C = prev ? Cw : Cw * exp;
-            const long long M = (long long)B * HW;
-            const int nslots = 31 / HW + 2;
-            const long long e = ((M + 31) / 32) * nslots * C * 2;
-            if (e > mx) mx = e;
-        }
-        const int TYl = (d.h[l] + 1) / 2, TXl = (d.w[l] + 1) / 2;
-        for (int v = 0; v < 2; ++v) {   // the unit shape of both Winograd kernels (wino_shape: utilisation / rounds of workgroups)
-            int ib, tyb, txb;
-            wino_shape(B, TYl, TXl, ib, tyb, txb, v ? (Cw >= 128 ? Cw / 128 : 1) : 0, v ? Cw / 16 : 0);
-            const long long PBl = (long long)((TYl + tyb - 1) / tyb) * ((TXl + txb - 1) / txb);
-            const long long ew = (long long)B * PBl * 2 * Cw * 3;  // Winograd (cnt, mean, M2) partials
-            if (ew > mx) mx = ew;
-        }
+        for (int prev = 0; prev < (A.bottleneck && l > 1 ? 2 : 1); ++prev)
+            mx = std::max(mx, flat_part_elems(B, d.h[l - prev] * d.w[l - prev], prev ? Cw : Cw * exp));
+        for (int v = 0; v < 2; ++v) mx = std::max(mx, wino_part_elems(B, wino_unit(B, d.h[l], d.w[l], v != 0, Cw, Cw), Cw));
     }
     r.part_elems = mx;
     r.part = o; o = al256(o + (size_t)mx * 4);
@@ -2295,351 +2366,167 @@ int fill_stats(hipStream_t st, const float* m_c, const float* r_c, float* mean, 
     return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 
-int run_conv(hipStream_t st, const float* x, const float* wpk, const float* in_mean, const float* in_rstd,
-             float* y, float* part, float* mean, float* rstd, int B, int H, int W, const ConvSpec& s,
-             const float* bn_m = nullptr, const float* bn_r = nullptr) {
-    if (use_wino(s)) {
-        WinoArgs wa;
-        wa.x = x; wa.u = wpk; wa.in_mean = in_mean; wa.in_rstd = in_rstd; wa.y = y; wa.part = part;
-        wa.B = B; wa.H = H; wa.W = W; wa.C = s.cin; wa.Cout = s.cout;
-        wa.TY = (H + 1) / 2; wa.TX = (W + 1) / 2;
-        // (keyed on the layer, not on the kernel: DSMIL_WINO_KERNEL=unit of experiment builds runs the same units through
-        // k_conv_wino_s3, which is what the bit-identity test of the two kernels compares)
-        if (wino_s3() && s.cout % 128 == 0 && s.cin >= 64) wino_shape(B, wa.TY, wa.TX, wa.IB, wa.TYB, wa.TXB, s.cout / 128, s.cin / 16);
-        else wino_shape(B, wa.TY, wa.TX, wa.IB, wa.TYB, wa.TXB);
+// ---- launches: a plan -> its template instantiation.  The forms a build HAS are these lists (the product library: the fp16
+// three-product form and the opt-in one-plane form); a plan that names anything else is DSMIL_E_UNSUPPORTED, never another kernel.
+template <int... V> struct Ints {};
 #ifdef DSMIL_EXPERIMENTS
-        static const int wexpt = expt_env("DSMIL_WINO_EXPT");
-        wa.expt = wexpt;
+using WinoNPs = Ints<NPD, 1, 6, 9>;     // k_conv_wino_s3 (two-wave unit), k_conv_wino_w1
+using DirectNPs = Ints<NPD, 1, 6>;      // k_conv_s6 (tiles 42 / 24 / 22), k_stem_s6
+using W1Abls = Ints<3, 4, 15, 16, 32, 64, 96, 128, 143>;   // DSMIL_WINO_EXPT values that are compile-time ablations of k_conv_wino_w1<.., NPD, ABL>
 #else
-        wa.expt = 0;
+using WinoNPs = Ints<NPD, 1>;
+using DirectNPs = Ints<NPD, 1>;
+using W1Abls = Ints<>;
 #endif
-        wa.nby = (wa.TY + wa.TYB - 1) / wa.TYB; wa.nbx = (wa.TX + wa.TXB - 1) / wa.TXB; wa.PB = wa.nby * wa.nbx;
+template <int... V> constexpr bool has(Ints<V...>, int want) { return ((V == want) || ...); }
+// f(std::integral_constant<int, v>) for the v of the list that equals `want`; false when the build does not have it
+template <int... V, class F> bool pick(Ints<V...>, int want, F&& f) { return ((V == want ? (f(std::integral_constant<int, V>{}), true) : false) || ...); }
+template <class F> bool pick(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <class K, class P, class... A> void launch(K kern, const P& p, hipStream_t st, A... args) {
+    allow_lds((const void*)kern, p.lds);
+    hipLaunchKernelGGL(kern, p.grid, dim3(p.block), p.lds, st, args...);
+}
+
+#ifdef DSMIL_EXPERIMENTS   // the launch tables of what only experiment builds instantiate
+template <bool NORM> bool launch_wino_expt(const ConvPlan& p, const WinoArgs& wa, hipStream_t st) {
+    auto bf16 = [&](auto f) { return pick(Ints<6, 9>{}, p.np, f); };
+    if (p.kern == CK_PP) {   // one workgroup per CU walks the (unit, cout tile) items
+        static const int ncu = [] {
+            int dev = 0, n = 0;
+            (void)hipGetDevice(&dev);
+            (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+            return n > 0 ? n : 256;
+        }();
+        ConvPlan q = p;
+        const int nunits = (int)p.grid.x, nitems = (int)(p.grid.x * p.grid.y);
+        q.grid = dim3((unsigned)(nitems < ncu ? nitems : ncu));
+        return bf16([&](auto NP) { launch(k_conv_wino_pp<NORM, decltype(NP)::value, PP_UD>, q, st, wa, nunits, nitems); });
+    }
+    if (p.kern == CK_ALT) return bf16([&](auto NP) { launch(k_conv_wino_alt<NORM, decltype(NP)::value>, p, st, wa); });
+    // (DSMIL_WINO_KERNEL=unit) 128 couts per workgroup (512 threads, one workgroup per CU): round 2's form of layers 2-4
+    if (p.kern == CK_WIDE) return pick(Ints<NPD, 6, 9>{}, p.np, [&](auto NP) { launch(k_conv_wino_s3<NORM, WIDE_UD, NORM, decltype(NP)::value, 4, WIDE_UC>, p, st, wa); });
+    if (p.kern == CK_WINO_F32) { launch(k_conv_wino<NORM>, p, st, wa); return true; }
+    return false;
+}
+template <bool NORM> bool launch_direct_expt(const ConvPlan& p, const ConvArgs& a, hipStream_t st) {
+    if (p.kern == CK_S6 && p.tile == 44) return pick(Ints<NPD, 6>{}, p.np, [&](auto NP) { launch(k_conv_s6<4, 4, NORM, decltype(NP)::value>, p, st, a); });
+    if (p.kern != CK_F32) return false;
+    if (p.tile == 42) launch(k_conv<4, 2, NORM>, p, st, a);
+    else if (p.tile == 44) launch(k_conv<4, 4, NORM>, p, st, a);
+    else launch(k_conv<2, 1, NORM>, p, st, a);
+    return true;
+}
+template <bool U8, class... A> bool launch_stem_f32(const StemPlan& p, hipStream_t st, A... args) { launch(k_stem<U8>, p, st, args...); return true; }
+bool pack_f32(const ConvPlan& p, const ConvSpec& s, unsigned blocks, hipStream_t st, const float* w, float* out) {
+    if (p.wino) hipLaunchKernelGGL(k_pack_wino, dim3(blocks), dim3(256), 0, st, w, out, s.cout, s.cin);
+    else hipLaunchKernelGGL(k_pack_conv, dim3(blocks), dim3(256), 0, st, w, out, s.cout, s.cin, s.ks * s.ks);
+    return true;
+}
+#else
+template <bool NORM> bool launch_wino_expt(const ConvPlan&, const WinoArgs&, hipStream_t) { return false; }
+template <bool NORM> bool launch_direct_expt(const ConvPlan&, const ConvArgs&, hipStream_t) { return false; }
+template <bool U8, class... A> bool launch_stem_f32(const StemPlan&, hipStream_t, A...) { return false; }
+bool pack_f32(const ConvPlan&, const ConvSpec&, unsigned, hipStream_t, const float*, float*) { return false; }
+#endif
+
+struct ConvIO { const float* x; const float* w; const float* in_mean; const float* in_rstd; float* y; float* part; float* mean; float* rstd; const float* bn_m; const float* bn_r; };
+
+bool launch_wino(const ConvPlan& p, const ConvSpec& s, const ConvIO& io, int B, int H, int W, hipStream_t st) {
+    WinoArgs wa;
+    wa.x = io.x; wa.u = io.w; wa.in_mean = io.in_mean; wa.in_rstd = io.in_rstd; wa.y = io.y; wa.part = io.part;
+    wa.B = B; wa.H = H; wa.W = W; wa.C = s.cin; wa.Cout = s.cout;
+    wa.TY = p.u.TY; wa.TX = p.u.TX; wa.IB = p.u.IB; wa.TYB = p.u.TYB; wa.TXB = p.u.TXB;
+    wa.nby = p.u.nby; wa.nbx = p.u.nbx; wa.PB = p.u.PB;
+    wa.expt = p.wexpt;
 #ifdef DSMIL_TRACE
-        {   // DSMIL_WINO_TRACE = k: the k-th Winograd launch of the process records stamps (tools_stamp_wino.py)
-            static const int want = expt_env("DSMIL_WINO_TRACE");
-            static int launch = 0;
-            wa.trace = (++launch == want) ? wino_trace_buffer() : nullptr;
-        }
+    static int nth = 0;
+    wa.trace = (++nth == expt().wino_trace) ? wino_trace_buffer() : nullptr;
 #endif
-        const size_t lds = wino_s3() ? (size_t)(SV_DW + WRAW_MAX * SRLD) * sizeof(float)
-                                     : (size_t)(2 * WTILE + 2 * WRAW_MAX * WLD) * sizeof(float);
-        dim3 grid((unsigned)(((B + wa.IB - 1) / wa.IB) * wa.PB), (unsigned)(s.cout / 64));
-        const int slot = dsmil_prof::begin(dsmil_prof::CH_CONV, st);
-        if (wino_s3()) {
-            // product configuration: weights two positions ahead (UD = 2), producer statistics staged through LDS (LS,
-            // +4 KiB: 80 KiB per workgroup, still two per CU), NP = 6 | 9 by DSMIL_WINO
-            const size_t lds_ls = lds + 4096;
-#ifdef DSMIL_EXPERIMENTS
-            const bool np9 = wino_form() == 9, np6 = wino_form() == 6;
-#define DSMIL_IF_NP9 if (np9)
-#define DSMIL_IF_NP6 if (np6)
-#else
-#define DSMIL_IF_NP9 if constexpr (false)   // the product library has the fp16 three-product form only: the bf16 forms are
-#define DSMIL_IF_NP6 if constexpr (false)   // not instantiated
-#endif
-            auto go = [&](auto kern, size_t l) {
-                allow_lds((const void*)kern, l);
-                hipLaunchKernelGGL(kern, grid, dim3(256), l, st, wa);
-            };
-            const bool half1 = wino_form() == 1;   // the opt-in one-plane path (dsmil_resnet_forward_ex)
-#ifdef DSMIL_EXPERIMENTS
-            static const int ncu = [] {
-                int dev = 0, n = 0;
-                (void)hipGetDevice(&dev);
-                (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-                return n > 0 ? n : 256;
-            }();
-            const int nunits = (int)grid.x, nitems = (int)(grid.x * grid.y);
-            const size_t lds_pp = (size_t)(2 * SV_DW + 2 * WRAW_MAX * SRLD + 1024) * sizeof(float);
-            auto go_pp = [&](auto kern) {   // persistent: one workgroup per CU walks the (unit, cout tile) items
-                allow_lds((const void*)kern, lds_pp);
-                hipLaunchKernelGGL(kern, dim3((unsigned)(nitems < ncu ? nitems : ncu)), dim3(512), lds_pp, st, wa, nunits, nitems);
-            };
-            const dim3 grida(grid.x, (unsigned)(s.cout / 128));
-            auto goa = [&](auto kern) {
-                allow_lds((const void*)kern, lds_pp);
-                hipLaunchKernelGGL(kern, grida, dim3(512), lds_pp, st, wa);
-            };
-            int which = wino_expt_kernel();         // DSMIL_WINO_KERNEL = pp | alt | w1
-            if ((which == 1 || which == 2) && !(np9 || np6)) which = 0;   // the two rejected restructurings exist in the bf16 forms only
-            const int w1_abl = wa.expt;
-            if (which == 3) wa.expt = 0;            // with w1 named explicitly the ablation bits address that kernel only
-#else
-            constexpr int which = 0;
-#endif
-            if (half1) {
-                if (use_w1(s)) {
-                    const dim3 gridw(grid.x * (unsigned)(s.cout / 128));
-                    const size_t lds_w1 = (size_t)(2 * SV_DW + 2 * WRAW_MAX * SRLD + 256 + 1024) * sizeof(float);
-                    auto gow1 = [&](auto kern) {
-                        allow_lds((const void*)kern, lds_w1);
-                        hipLaunchKernelGGL(kern, gridw, dim3(256), lds_w1, st, wa);
-                    };
-                    if (in_mean) gow1(k_conv_wino_w1<true, 1>); else gow1(k_conv_wino_w1<false, 1>);
-                } else if (in_mean) go(k_conv_wino_s3<true, 2, true, 1>, lds_ls);
-                else go(k_conv_wino_s3<false, 2, false, 1>, lds);
-            } else if (which == 1) {
-#ifdef DSMIL_EXPERIMENTS
-                if (in_mean) { if (np9) go_pp(k_conv_wino_pp<true, 9, PP_UD>); else go_pp(k_conv_wino_pp<true, 6, PP_UD>); }
-                else { if (np9) go_pp(k_conv_wino_pp<false, 9, PP_UD>); else go_pp(k_conv_wino_pp<false, 6, PP_UD>); }
-#endif
-            } else if (which == 2 && s.cout % 128 == 0) {
-#ifdef DSMIL_EXPERIMENTS
-                if (in_mean) { if (np9) goa(k_conv_wino_alt<true, 9>); else goa(k_conv_wino_alt<true, 6>); }
-                else { if (np9) goa(k_conv_wino_alt<false, 9>); else goa(k_conv_wino_alt<false, 6>); }
-#endif
-            } else if (use_w1(s)) {
-                // one wave per SIMD: 256 threads, 128 couts, all 16 positions per wave (wino_w1.h)
-                const dim3 gridw(grid.x * (unsigned)(s.cout / 128));   // 1-D: the kernel maps it to (unit, cout block) per XCD
-                const size_t lds_w1 = (size_t)(2 * SV_DW + 2 * WRAW_MAX * SRLD + 256 + 1024) * sizeof(float);
-                auto gow1 = [&](auto kern) {
-                    allow_lds((const void*)kern, lds_w1);
-                    hipLaunchKernelGGL(kern, gridw, dim3(256), lds_w1, st, wa);
-                };
-#ifdef DSMIL_EXPERIMENTS
-                switch (w1_abl) {   // DSMIL_WINO_EXPT: compile-time ablations of the w1 kernel (timing only)
-#define W1_ABL(n) case n: if (in_mean) gow1(k_conv_wino_w1<true, NPD, n>); else gow1(k_conv_wino_w1<false, NPD, n>); break;
-                    W1_ABL(3) W1_ABL(4) W1_ABL(15) W1_ABL(16) W1_ABL(32) W1_ABL(64) W1_ABL(96) W1_ABL(128) W1_ABL(143)
-#undef W1_ABL
-                    default:
-                        if (in_mean) { if (np9) gow1(k_conv_wino_w1<true, 9>); else if (np6) gow1(k_conv_wino_w1<true, 6>); else gow1(k_conv_wino_w1<true, NPD>); }
-                        else { if (np9) gow1(k_conv_wino_w1<false, 9>); else if (np6) gow1(k_conv_wino_w1<false, 6>); else gow1(k_conv_wino_w1<false, NPD>); }
-                }
-#else
-                if (in_mean) gow1(k_conv_wino_w1<true, NPD>); else gow1(k_conv_wino_w1<false, NPD>);
-#endif
-#ifdef DSMIL_EXPERIMENTS
-            } else if (s.cout % 128 == 0 && wino_wide()) {
-                // (DSMIL_WINO_KERNEL=unit) 128 couts per workgroup (512 threads, one workgroup per CU): round 2's form of layers 2-4
-                const dim3 gridw(grid.x, (unsigned)(s.cout / 128));
-                auto gow = [&](auto kern, size_t l) {
-                    allow_lds((const void*)kern, l);
-                    hipLaunchKernelGGL(kern, gridw, dim3(512), l, st, wa);
-                };
-                if (in_mean) {
-                    if (np9) gow(k_conv_wino_s3<true, WIDE_UD, true, 9, 4, WIDE_UC>, lds_ls);
-                    else if (np6) gow(k_conv_wino_s3<true, WIDE_UD, true, 6, 4, WIDE_UC>, lds_ls);
-                    else gow(k_conv_wino_s3<true, WIDE_UD, true, NPD, 4, WIDE_UC>, lds_ls);
-                } else {
-                    if (np9) gow(k_conv_wino_s3<false, WIDE_UD, false, 9, 4, WIDE_UC>, lds);
-                    else if (np6) gow(k_conv_wino_s3<false, WIDE_UD, false, 6, 4, WIDE_UC>, lds);
-                    else gow(k_conv_wino_s3<false, WIDE_UD, false, NPD, 4, WIDE_UC>, lds);
-                }
-#endif
-            } else if (in_mean) {
-                DSMIL_IF_NP9 go(k_conv_wino_s3<true, 2, true, 9>, lds_ls);
-                else DSMIL_IF_NP6 go(k_conv_wino_s3<true, 2, true, 6>, lds_ls);
-                else go(k_conv_wino_s3<true, 2, true, NPD>, lds_ls);
-            } else {
-                DSMIL_IF_NP9 go(k_conv_wino_s3<false, 2, false, 9>, lds);
-                else DSMIL_IF_NP6 go(k_conv_wino_s3<false, 2, false, 6>, lds);
-                else go(k_conv_wino_s3<false, 2, false, NPD>, lds);
-            }
-        }
-#ifdef DSMIL_EXPERIMENTS   // DSMIL_WINO=f32: the f32-MFMA Winograd unit
-        else if (in_mean) hipLaunchKernelGGL((k_conv_wino<true>), grid, dim3(256), lds, st, wa);
-        else hipLaunchKernelGGL((k_conv_wino<false>), grid, dim3(256), lds, st, wa);
-#endif
-        dsmil_prof::end(dsmil_prof::CH_CONV, slot, st);
-        if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
-        if (bn_m) return fill_stats(st, bn_m, bn_r, mean, rstd, B, s.cout);
-        hipLaunchKernelGGL(k_in_finalize_cnt, dim3((unsigned)B, (unsigned)((s.cout + 63) / 64)), dim3(256), 0, st, part, mean, rstd, wa.PB * 2, s.cout);
-        return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
-    }
+    return pick(p.norm, [&](auto N) {
+        constexpr bool NORM = decltype(N)::value;
+        if (p.kern == CK_UNIT) return pick(WinoNPs{}, p.np, [&](auto NP) { launch(k_conv_wino_s3<NORM, 2, NORM, decltype(NP)::value>, p, st, wa); });
+        if (p.kern == CK_W1)   // one wave per SIMD: 256 threads, 128 couts, all 16 positions per wave (wino_w1.h)
+            return has(W1Abls{}, p.abl) ? pick(W1Abls{}, p.abl, [&](auto ABL) { launch(k_conv_wino_w1<NORM, NPD, decltype(ABL)::value>, p, st, wa); })
+                                        : pick(WinoNPs{}, p.np, [&](auto NP) { launch(k_conv_wino_w1<NORM, decltype(NP)::value>, p, st, wa); });
+        return launch_wino_expt<NORM>(p, wa, st);
+    });
+}
+
+bool launch_direct(const ConvPlan& p, const ConvSpec& s, const ConvIO& io, int B, int H, int W, hipStream_t st) {
     ConvArgs a;
-    a.x = x; a.w = wpk; a.in_mean = in_mean; a.in_rstd = in_rstd; a.y = y; a.part = part;
-    a.B = B; a.H = H; a.W = W; a.Cin = s.cin;
-    a.Ho = outdim(H, s.ks, s.stride, s.pad); a.Wo = outdim(W, s.ks, s.stride, s.pad);
+    a.x = io.x; a.w = io.w; a.in_mean = io.in_mean; a.in_rstd = io.in_rstd; a.y = io.y; a.part = io.part;
+    a.B = B; a.H = H; a.W = W; a.Cin = s.cin; a.Ho = p.Ho; a.Wo = p.Wo;
     a.Cout = s.cout; a.ks = s.ks; a.stride = s.stride; a.pad = s.pad;
-    const int HW = a.Ho * a.Wo;
-    a.nslots = 31 / HW + 2;
-    a.Mtot = (long long)B * HW;
-    const bool norm = in_mean != nullptr;
+    a.nslots = p.nslots; a.Mtot = p.Mtot;
+    return pick(p.norm, [&](auto N) {
+        constexpr bool NORM = decltype(N)::value;
+        if (p.kern != CK_S6 || p.tile == 44) return launch_direct_expt<NORM>(p, a, st);
+        return pick(DirectNPs{}, p.np, [&](auto NP) {
+            if (p.tile == 24) launch(k_conv_s6<2, 4, NORM, decltype(NP)::value>, p, st, a);
+            else if (p.tile == 22) launch(k_conv_s6<2, 2, NORM, decltype(NP)::value>, p, st, a);
+            else launch(k_conv_s6<4, 2, NORM, decltype(NP)::value>, p, st, a);
+        });
+    });
+}
+
+// one conv: the planned launch, then its statistics: the frozen ones, or the finalize kernel of its partials
+int run_conv(hipStream_t st, const ConvPlan& p, const ConvSpec& s, const ConvIO& io, int B, int H, int W) {
     const int slot = dsmil_prof::begin(dsmil_prof::CH_CONV, st);
-    const long long blocks128 = ((a.Mtot + 127) / 128) * (s.cout / 128 > 0 ? s.cout / 128 : 1);
-    if (conv_s6()) {
-        // tile = BM pixels x TN output channels per 256-thread workgroup: 128 x 128, 128 x 64, 64 x 256 or 64 x 128
-        auto go = [&](auto kern, int BM, int TN) {
-            const size_t lds = (size_t)2 * (BM + TN) * S6LD * 4;
-            allow_lds((const void*)kern, lds);
-            dim3 grid((unsigned)((a.Mtot + BM - 1) / BM), (unsigned)(s.cout / TN));
-            hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
-        };
-        // Measured per layer (tools/s6_shapes.sh, bs 256): the activation rows are the expensive operand to stage (im2col
-        // gather, producer's IN + ReLU, plane cut; the weights are a plain copy), so the tile is as short in pixels and as wide
-        // in channels as the layer allows — 64 x 256, else 64 x 128 — which also quantises better (l4.0.conv1: 392 workgroups
-        // in ONE round instead of 784 on 768 slots; 195 us against 288).  Six direct convs of ResNet-18: 850 -> 726 us.
-        (void)blocks128;
-        int shape = s.cout % 256 == 0 ? 24 : s.cout % 128 == 0 ? 22 : 42;
-#ifdef DSMIL_EXPERIMENTS
-        {   // DSMIL_S6_TILE = 44 | 42 | 24 | 22 forces a tile shape wherever the channel count allows it (A/B)
-            static const int force = expt_env("DSMIL_S6_TILE");
-            if (force == 44 && s.cout % 128 == 0) shape = 44;
-            if (force == 42) shape = 42;
-            if (force == 24 && s.cout % 256 == 0) shape = 24;
-            if (force == 22 && s.cout % 128 == 0) shape = 22;
-        }
-#endif
-        if (conv_np() == 1) {   // the opt-in one-plane path
-            switch (shape) {
-                case 24: if (norm) go(k_conv_s6<2, 4, true, 1>, 64, 256); else go(k_conv_s6<2, 4, false, 1>, 64, 256); break;
-                case 22: if (norm) go(k_conv_s6<2, 2, true, 1>, 64, 128); else go(k_conv_s6<2, 2, false, 1>, 64, 128); break;
-                default: if (norm) go(k_conv_s6<4, 2, true, 1>, 128, 64); else go(k_conv_s6<4, 2, false, 1>, 128, 64); break;
-            }
-        } else
-#ifdef DSMIL_EXPERIMENTS
-        if (conv_np() == 6) {   // DSMIL_CONV=s6: the bf16 three-plane form
-            switch (shape) {
-                case 44: if (norm) go(k_conv_s6<4, 4, true, 6>, 128, 128); else go(k_conv_s6<4, 4, false, 6>, 128, 128); break;
-                case 24: if (norm) go(k_conv_s6<2, 4, true, 6>, 64, 256); else go(k_conv_s6<2, 4, false, 6>, 64, 256); break;
-                case 22: if (norm) go(k_conv_s6<2, 2, true, 6>, 64, 128); else go(k_conv_s6<2, 2, false, 6>, 64, 128); break;
-                default: if (norm) go(k_conv_s6<4, 2, true, 6>, 128, 64); else go(k_conv_s6<4, 2, false, 6>, 128, 64); break;
-            }
-        } else
-#endif
-        switch (shape) {
-#ifdef DSMIL_EXPERIMENTS
-            case 44: if (norm) go(k_conv_s6<4, 4, true, NPD>, 128, 128); else go(k_conv_s6<4, 4, false, NPD>, 128, 128); break;
-#endif
-            case 24: if (norm) go(k_conv_s6<2, 4, true, NPD>, 64, 256); else go(k_conv_s6<2, 4, false, NPD>, 64, 256); break;
-            case 22: if (norm) go(k_conv_s6<2, 2, true, NPD>, 64, 128); else go(k_conv_s6<2, 2, false, NPD>, 64, 128); break;
-            default: if (norm) go(k_conv_s6<4, 2, true, NPD>, 128, 64); else go(k_conv_s6<4, 2, false, NPD>, 128, 64); break;
-        }
-        dsmil_prof::end(dsmil_prof::CH_CONV, slot, st);
-        if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
-        if (bn_m) return fill_stats(st, bn_m, bn_r, mean, rstd, B, s.cout);
-        hipLaunchKernelGGL(k_in_finalize_flat, dim3((unsigned)B, (unsigned)((s.cout + 63) / 64)), dim3(256), 0, st, part, mean, rstd,
-                           B, HW, s.cout, a.nslots, a.Mtot);
-        return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
-    }
-#ifndef DSMIL_EXPERIMENTS
-    (void)blocks128;
-    return DSMIL_E_UNSUPPORTED;   // (unreachable: the product library has the bf16-MFMA form only)
-#else
-    // DSMIL_CONV=f32.  Tile choice: 128x64 for Cout = 64; 128x128 while that yields >= 4 workgroups per CU;
-    // 64x64 (finer units, less tail quantisation) for the small late-layer maps
-    if (s.cout == 64) {
-        const size_t lds = (size_t)(2 * 128 * LDK + 2 * 64 * LDK) * 4;
-        dim3 grid((unsigned)((a.Mtot + 127) / 128), 1);
-        if (norm) hipLaunchKernelGGL((k_conv<4, 2, true>), grid, dim3(256), lds, st, a);
-        else hipLaunchKernelGGL((k_conv<4, 2, false>), grid, dim3(256), lds, st, a);
-    } else if (blocks128 >= 1024) {
-        const size_t lds = (size_t)(2 * 128 * LDK + 2 * 128 * LDK) * 4;
-        dim3 grid((unsigned)((a.Mtot + 127) / 128), (unsigned)(s.cout / 128));
-        if (norm) hipLaunchKernelGGL((k_conv<4, 4, true>), grid, dim3(256), lds, st, a);
-        else hipLaunchKernelGGL((k_conv<4, 4, false>), grid, dim3(256), lds, st, a);
-    } else {
-        const size_t lds = (size_t)(2 * 64 * LDK + 2 * 64 * LDK) * 4;
-        dim3 grid((unsigned)((a.Mtot + 63) / 64), (unsigned)(s.cout / 64));
-        if (norm) hipLaunchKernelGGL((k_conv<2, 1, true>), grid, dim3(256), lds, st, a);
-        else hipLaunchKernelGGL((k_conv<2, 1, false>), grid, dim3(256), lds, st, a);
-    }
+    const bool have = p.wino ? launch_wino(p, s, io, B, H, W, st) : launch_direct(p, s, io, B, H, W, st);
     dsmil_prof::end(dsmil_prof::CH_CONV, slot, st);
+    if (!have) return DSMIL_E_UNSUPPORTED;   // (the build does not instantiate this form)
     if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
-    if (bn_m) return fill_stats(st, bn_m, bn_r, mean, rstd, B, s.cout);
-    hipLaunchKernelGGL(k_in_finalize_flat, dim3((unsigned)B, (unsigned)((s.cout + 63) / 64)), dim3(256), 0, st, part, mean, rstd,
-                       B, HW, s.cout, a.nslots, a.Mtot);
+    if (io.bn_m) return fill_stats(st, io.bn_m, io.bn_r, io.mean, io.rstd, B, s.cout);
+    const dim3 grid((unsigned)B, (unsigned)((s.cout + 63) / 64));
+    if (p.wino) hipLaunchKernelGGL(k_in_finalize_cnt, grid, dim3(256), 0, st, io.part, io.mean, io.rstd, p.u.PB * 2, s.cout);
+    else hipLaunchKernelGGL(k_in_finalize_flat, grid, dim3(256), 0, st, io.part, io.mean, io.rstd, B, p.Ho * p.Wo, s.cout, p.nslots, p.Mtot);
     return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
-#endif
 }
 
-void set_conv_attrs() {   // per (device, kernel): lds_attr.h.  Only the f32 forms of experiment builds: the others set theirs at launch
-#ifdef DSMIL_EXPERIMENTS
-    const int l4 = (2 * 128 * LDK + 2 * 128 * LDK) * 4, l2 = (2 * 128 * LDK + 2 * 64 * LDK) * 4;
-    allow_lds((const void*)k_conv<4, 4, true>, l4);
-    allow_lds((const void*)k_conv<4, 4, false>, l4);
-    allow_lds((const void*)k_conv<4, 2, true>, l2);
-    allow_lds((const void*)k_conv<4, 2, false>, l2);
-    allow_lds((const void*)k_conv_wino<true>, (2 * WTILE + 2 * WRAW_MAX * WLD) * 4);
-    allow_lds((const void*)k_conv_wino<false>, (2 * WTILE + 2 * WRAW_MAX * WLD) * 4);
-#endif
+bool launch_stem(const StemPlan& p, bool u8, hipStream_t st, const void* x, const float* conv1_w, const unsigned short* wimg, float* y0,
+                 float* pooled, float* part, int B, int H, int W, const Dims& d) {
+    return pick(u8, [&](auto U) {
+        constexpr bool U8 = decltype(U)::value;
+        if (!p.np) return launch_stem_f32<U8>(p, st, x, conv1_w, y0, part, B, H, W, d.H1, d.W1, p.tx, p.ty);
+        // fused: the pooled raw map goes straight to the max-pool's destination; the raw-map region holds the halo rows
+        return pick(p.fuse, [&](auto F) {
+            constexpr bool POOL = decltype(F)::value;
+            return pick(DirectNPs{}, p.np, [&](auto NP) {
+                launch(k_stem_s6<U8, POOL, decltype(NP)::value>, p, st, x, wimg, POOL ? pooled : y0, part, B, H, W, d.H1, d.W1, p.tx, p.ty,
+                       POOL ? y0 : (float*)nullptr, POOL ? d.Hp : 0, POOL ? d.Wp : 0);
+            });
+        });
+    });
 }
 
-}  // namespace
-
-extern "C" {
-
-int dsmil_resnet_mfma_forms(int32_t* wino_products, int32_t* direct_products) {
-    if (wino_products) *wino_products = wino_form();
-    if (direct_products) *direct_products = conv_np();
-    return DSMIL_OK;
-}
-
-int32_t dsmil_resnet_num_convs(int32_t depth) { const Arch* A = arch_of(depth); return A ? A->nconv : 0; }
-int32_t dsmil_resnet_norm_channels(int32_t depth) { const Arch* A = arch_of(depth); return A ? norm_offset(*A, A->nconv) : 0; }
-// the packed image ends with the stem's three bf16 planes (k_stem_s6; conv 0 keeps its raw OIHW argument for the f32 form)
-size_t dsmil_resnet_packed_bytes(int32_t depth) {
-    const Arch* A = arch_of(depth);
-    return A ? (pack_offset(*A, A->nconv) + SS_WIMG / 2) * sizeof(float) : 0;
-}
-
-int dsmil_resnet_pack(int32_t depth, const float* const* conv_w, float* packed, void* stream) {
-    const Arch* A = arch_of(depth);
-    if (!A) return DSMIL_E_UNSUPPORTED;
-    if (!conv_w || !packed) return DSMIL_E_INVALID;
-    hipStream_t st = (hipStream_t)stream;
+int pack_impl(const Arch& A, const float* const* conv_w, float* packed, const Form& f, hipStream_t st) {
+    const Expt& e = expt();
+    const PackOffsets po = pack_offsets(A, f, e);
     if (!conv_w[0]) return DSMIL_E_INVALID;
-    hipLaunchKernelGGL(k_pack_stem_s6, dim3(46), dim3(256), 0, st, conv_w[0],
-                       (unsigned short*)(packed + pack_offset(*A, A->nconv)), conv_np());
+    hipLaunchKernelGGL(k_pack_stem_s6, dim3(46), dim3(256), 0, st, conv_w[0], (unsigned short*)(packed + po.off[A.nconv]), f.conv_np);
     if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
-    for (int i = 1; i < A->nconv; ++i) {
+    for (int i = 1; i < A.nconv; ++i) {
         if (!conv_w[i]) return DSMIL_E_INVALID;
-        const ConvSpec& s = A->specs[i];
-        if (use_wino(s)) {
-            long long blocks = ((long long)s.cout * s.cin + 255) / 256;
-            if (blocks > 4096) blocks = 4096;
-            if (wino_s3())
-                hipLaunchKernelGGL(k_pack_wino_s3, dim3((unsigned)blocks), dim3(256), 0, st, conv_w[i],
-                                   (unsigned short*)(packed + pack_offset(*A, i)), s.cout, s.cin, wino_tiled() ? 1 : 0, wino_form());
-#ifdef DSMIL_EXPERIMENTS
-            else
-                hipLaunchKernelGGL(k_pack_wino, dim3((unsigned)blocks), dim3(256), 0, st, conv_w[i],
-                                   packed + pack_offset(*A, i), s.cout, s.cin);
-#endif
-        } else {
-            const long long total = (long long)s.cout * s.cin * s.ks * s.ks;
-            long long blocks = (total + 255) / 256;
-            if (blocks > 4096) blocks = 4096;
-            if (conv_s6())
-                hipLaunchKernelGGL(k_pack_conv_s6, dim3((unsigned)blocks), dim3(256), 0, st, conv_w[i],
-                                   (unsigned short*)(packed + pack_offset(*A, i)), s.cout, s.cin, s.ks * s.ks, conv_np());
-#ifdef DSMIL_EXPERIMENTS
-            else
-                hipLaunchKernelGGL(k_pack_conv, dim3((unsigned)blocks), dim3(256), 0, st, conv_w[i],
-                                   packed + pack_offset(*A, i), s.cout, s.cin, s.ks * s.ks);
-#endif
-        }
+        const ConvSpec& s = A.specs[i];
+        const ConvPlan p = plan_conv(s, 0, 0, 0, false, f, e);
+        const long long total = (long long)s.cout * s.cin * (p.wino ? 1 : s.ks * s.ks);
+        const unsigned blocks = (unsigned)std::min<long long>((total + 255) / 256, 4096);
+        float* out = packed + po.off[i];
+        if (!p.np) { if (!pack_f32(p, s, blocks, st, conv_w[i], out)) return DSMIL_E_UNSUPPORTED; }
+        else if (p.wino) hipLaunchKernelGGL(k_pack_wino_s3, dim3(blocks), dim3(256), 0, st, conv_w[i], (unsigned short*)out, s.cout, s.cin, p.tiled ? 1 : 0, p.np);
+        else hipLaunchKernelGGL(k_pack_conv_s6, dim3(blocks), dim3(256), 0, st, conv_w[i], (unsigned short*)out, s.cout, s.cin, s.ks * s.ks, p.np);
         if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
     }
     return DSMIL_OK;
 }
 
-size_t dsmil_resnet18_packed_bytes(void) { return dsmil_resnet_packed_bytes(18); }
-int dsmil_resnet18_pack(const float* const* conv_w, float* packed, void* stream) {
-    return dsmil_resnet_pack(18, conv_w, packed, stream);
-}
-
-size_t dsmil_resnet18_workspace_bytes(int32_t B, int32_t H, int32_t W) {
-    if (B <= 0 || H < 32 || W < 32) return 0;
-    return rws_layout(B, H, W).total;
-}
-
-size_t dsmil_resnet_workspace_bytes(int32_t depth, int32_t B, int32_t H, int32_t W) {
-    if (!arch_of(depth) || B <= 0 || H < 32 || W < 32) return 0;
-    return rws_layout(B, H, W, depth).total;
-}
-
-int32_t dsmil_resnet_feature_dim(int32_t depth) { const Arch* A = arch_of(depth); return A ? A->feat : 0; }
-
-static int resnet18in_forward_impl(const void* x_nchw, bool u8, int32_t B, int32_t H, int32_t W, const float* conv1_w,
-                                   const float* packed, const float* fc_w, const float* fc_b, int32_t C,
-                                   float* feats, float* classes, void* ws, size_t ws_bytes, void* stream,
-                                   const float* bn_m = nullptr, const float* bn_r = nullptr, int depth = 18) {
+// One forward of a ResNet-18 / 34 / 50 / 101 trunk (InstanceNorm, or frozen BatchNorm when bn_m / bn_r are given) in `form`
+int resnet_forward_impl(int depth, const Form& form, const void* x_nchw, bool u8, int32_t B, int32_t H, int32_t W, const float* conv1_w,
+                        const float* packed, const float* bn_m, const float* bn_r, const float* fc_w, const float* fc_b, int32_t C,
+                        float* feats, float* classes, void* ws, size_t ws_bytes, void* stream) {
     const Arch* Ap = arch_of(depth);
     if (!Ap) return DSMIL_E_UNSUPPORTED;
     const Arch& A = *Ap;
-    auto bm = [&](int i) { return bn_m ? bn_m + norm_offset(A, i) : nullptr; };
-    auto br = [&](int i) { return bn_r ? bn_r + norm_offset(A, i) : nullptr; };
     if (!x_nchw || !conv1_w || !packed || !feats || !ws) return DSMIL_E_INVALID;
     if (B <= 0 || H < 32 || W < 32) return DSMIL_E_INVALID;
     if (classes && (!fc_w || !fc_b || C <= 0)) return DSMIL_E_INVALID;
@@ -2649,7 +2536,15 @@ static int resnet18in_forward_impl(const void* x_nchw, bool u8, int32_t B, int32
     const Dims d = dims_for(H, W);
     if (d.h[4] < 1 || d.w[4] < 1) return DSMIL_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    set_conv_attrs();
+    const Expt& e = expt();
+    // the plans of this call, once: the stem, and — unless the b16 trunk takes over behind it — every conv
+    const StemPlan sp = plan_stem(d, B, bn_m != nullptr, form, e);
+    const PackOffsets po = pack_offsets(A, form, e);
+    ConvPlan plans[MAX_CONVS];
+    for (int i = 1; i < A.nconv && !form.trunk; ++i) {
+        plans[i] = plan_conv(A.specs[i], B, d.h[A.lvl[i]], d.w[A.lvl[i]], A.normed[i], form, e);
+        if (plans[i].part_elems > L.part_elems) return DSMIL_E_WORKSPACE;
+    }
     char* w8 = (char*)ws;
     float* y0 = (float*)(w8 + L.y0);
     float* buf[5];
@@ -2660,130 +2555,71 @@ static int resnet18in_forward_impl(const void* x_nchw, bool u8, int32_t B, int32
     float* part = (float*)(w8 + L.part);
 
     // ---- stem: conv1 -> IN -> ReLU -> maxpool
-    size_t b16_halo_bytes = 0;
-    bool b16_direct = false;
-    {
-        const bool s6 = conv_s6();   // DSMIL_CONV: the stem follows the direct convs' MFMA form
-        const int tx = (d.W1 + 15) / 16, ty = s6 ? (d.H1 + SS_TR - 1) / SS_TR : (d.H1 + 7) / 8;
-        // InstanceNorm trunks: the max-pool is fused into the stem (a frozen BatchNorm may have a negative scale, for which
-        // the pool needs the window MINIMUM too: that path keeps the raw map + k_norm_relu_maxpool)
-        const bool fuse = s6 && !bn_m && stem_fuse();
-        auto stem_go = [&](auto kern, size_t lds_, float* out, float* halo, int Hp_, int Wp_) {
-            allow_lds((const void*)kern, lds_);
-            hipLaunchKernelGGL(kern, dim3((unsigned)ty, (unsigned)B), dim3(512), lds_, st, x_nchw,
-                               (const unsigned short*)(packed + pack_offset(A, A.nconv)), out, part, B, H, W, d.H1, d.W1, tx, ty, halo, Hp_, Wp_);
-        };
-#ifdef DSMIL_EXPERIMENTS
-        const bool stem6 = conv_np() == 6;   // DSMIL_CONV=s6: the bf16 three-plane form
-#else
-        constexpr bool stem6 = false;
-#endif
-        const bool stem1 = conv_np() == 1;   // the opt-in one-plane path
-        if (fuse) {
-            // the pooled raw map goes straight to the max-pool's destination; the raw-map region holds the halo rows
-            const size_t ldsp = SS_LDS + SS_POOL_LDS;
-            if (stem1) {
-                if (u8) stem_go(k_stem_s6<true, true, 1>, ldsp, buf[0], y0, d.Hp, d.Wp); else stem_go(k_stem_s6<false, true, 1>, ldsp, buf[0], y0, d.Hp, d.Wp);
-            } else if (stem6) {
-#ifdef DSMIL_EXPERIMENTS
-                if (u8) stem_go(k_stem_s6<true, true, 6>, ldsp, buf[0], y0, d.Hp, d.Wp); else stem_go(k_stem_s6<false, true, 6>, ldsp, buf[0], y0, d.Hp, d.Wp);
-#endif
-            } else if (u8) stem_go(k_stem_s6<true, true, NPD>, ldsp, buf[0], y0, d.Hp, d.Wp);
-            else stem_go(k_stem_s6<false, true, NPD>, ldsp, buf[0], y0, d.Hp, d.Wp);
-        } else if (s6) {
-            if (stem1) {
-                if (u8) stem_go(k_stem_s6<true, false, 1>, SS_LDS, y0, nullptr, 0, 0); else stem_go(k_stem_s6<false, false, 1>, SS_LDS, y0, nullptr, 0, 0);
-            } else if (stem6) {
-#ifdef DSMIL_EXPERIMENTS
-                if (u8) stem_go(k_stem_s6<true, false, 6>, SS_LDS, y0, nullptr, 0, 0); else stem_go(k_stem_s6<false, false, 6>, SS_LDS, y0, nullptr, 0, 0);
-#endif
-            } else if (u8) stem_go(k_stem_s6<true, false, NPD>, SS_LDS, y0, nullptr, 0, 0);
-            else stem_go(k_stem_s6<false, false, NPD>, SS_LDS, y0, nullptr, 0, 0);
-        }
-#ifdef DSMIL_EXPERIMENTS   // DSMIL_CONV=f32
-        else if (u8) hipLaunchKernelGGL(k_stem<true>, dim3((unsigned)ty, (unsigned)B), dim3(256), 0, st, x_nchw, conv1_w, y0,
-                                        part, B, H, W, d.H1, d.W1, tx, ty);
-        else hipLaunchKernelGGL(k_stem<false>, dim3((unsigned)ty, (unsigned)B), dim3(256), 0, st, x_nchw, conv1_w, y0,
-                                part, B, H, W, d.H1, d.W1, tx, ty);
-#endif
-        if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
-        if (bn_m) { const int rcf = fill_stats(st, bm(0), br(0), mean[0], rstd[0], B, 64); if (rcf) return rcf; }
-        else hipLaunchKernelGGL(k_in_finalize_stem, dim3((unsigned)B), dim3(64 * FS_G), 0, st, part,
-                                mean[0], rstd[0], B, tx * ty * (s6 ? 8 : 4));
-        const long long total = (long long)B * d.Hp * d.Wp * 16;
-        long long blocks = (total + 255) / 256;
-        if (blocks > 8192) blocks = 8192;
-        // the bf16-activation trunk takes the stem's output as bf16 in its own layout, behind the halo rows of the raw-map region
-        b16_halo_bytes = al256((size_t)B * ty * d.W1 * 64 * sizeof(float));
-        b16_direct = g_b16_trunk && fuse && b16_halo_bytes + b16::scratch_bytes(B, d.Hp, d.Wp) <= L.buf[0] - L.y0;
-        if (fuse) hipLaunchKernelGGL(k_pool_fix_norm, dim3((unsigned)blocks), dim3(256), 0, st, buf[0], y0, mean[0], rstd[0],
-                                     B, d.Hp, d.Wp, d.W1, ty, b16_direct ? (unsigned short*)(w8 + L.y0 + b16_halo_bytes) : (unsigned short*)nullptr, g_b16_trunk == 2 ? 1 : 0);
-        else hipLaunchKernelGGL(k_norm_relu_maxpool, dim3((unsigned)blocks), dim3(256), 0, st, y0, mean[0], rstd[0],
-                                buf[0], B, d.H1, d.W1, d.Hp, d.Wp, 64);
-        if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
-    }
-    if (g_b16_trunk) {
+    if (!launch_stem(sp, u8, st, x_nchw, conv1_w, (const unsigned short*)(packed + po.off[A.nconv]), y0, buf[0], part, B, H, W, d))
+        return DSMIL_E_UNSUPPORTED;
+    if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    if (bn_m) { const int rcf = fill_stats(st, bn_m, bn_r, mean[0], rstd[0], B, 64); if (rcf) return rcf; }
+    else hipLaunchKernelGGL(k_in_finalize_stem, dim3((unsigned)B), dim3(64 * FS_G), 0, st, part, mean[0], rstd[0], B, sp.nparts);
+    const long long total = (long long)B * d.Hp * d.Wp * 16;
+    long long blocks = (total + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    // the bf16-activation trunk takes the stem's output as bf16 in its own layout, behind the halo rows of the raw-map region
+    const size_t b16_halo_bytes = al256((size_t)B * sp.ty * d.W1 * 64 * sizeof(float));
+    const bool b16_direct = form.trunk && sp.fuse && b16_halo_bytes + b16::scratch_bytes(B, d.Hp, d.Wp) <= L.buf[0] - L.y0;
+    if (sp.fuse) hipLaunchKernelGGL(k_pool_fix_norm, dim3((unsigned)blocks), dim3(256), 0, st, buf[0], y0, mean[0], rstd[0],
+                                    B, d.Hp, d.Wp, d.W1, sp.ty, b16_direct ? (unsigned short*)(w8 + L.y0 + b16_halo_bytes) : (unsigned short*)nullptr, form.trunk == 2 ? 1 : 0);
+    else hipLaunchKernelGGL(k_norm_relu_maxpool, dim3((unsigned)blocks), dim3(256), 0, st, y0, mean[0], rstd[0],
+                            buf[0], B, d.H1, d.W1, d.Hp, d.Wp, 64);
+    if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    if (form.trunk) {
         // the bf16-activation trunk: its four activation buffers and statistics partials take the raw-map region (the
         // stem's pooled output sits in buf[0]; the halo rows in y0 are dead behind k_pool_fix_norm); its weight image sits
         // behind the regular packed image
         if (!b16::arch_ok(A) || bn_m) return DSMIL_E_UNSUPPORTED;
         if (b16::scratch_bytes(B, d.Hp, d.Wp) > L.buf[0] - L.y0) return DSMIL_E_UNSUPPORTED;
-        const unsigned short* wpk16 = (const unsigned short*)((const char*)packed + dsmil_resnet_packed_bytes(depth));
+        const unsigned short* wpk16 = (const unsigned short*)((const char*)packed + (po.off[A.nconv] + SS_WIMG / 2) * sizeof(float));
         // (b16_direct: k_pool_fix_norm has already written the trunk's input, bf16, behind the halo rows)
-        const int rc = b16::trunk(st, A, b16_direct ? nullptr : buf[0], wpk16, w8 + L.y0 + (b16_direct ? b16_halo_bytes : 0), B, d.Hp, d.Wp, feats, g_b16_trunk == 2);
+        const int rc = b16::trunk(st, A, b16_direct ? nullptr : buf[0], wpk16, w8 + L.y0 + (b16_direct ? b16_halo_bytes : 0), B, d.Hp, d.Wp, feats, form.trunk);
         if (rc != DSMIL_OK) return rc;
         if (classes) return dsmil_fc_forward(feats, B, A.feat, C, fc_w, fc_b, classes, stream);
         return DSMIL_OK;
     }
-    // ---- layers 1..4, nblk[l] BasicBlocks each.  cur = block input (materialised, normalised)
+    // ---- layers 1..4, nblk[l] blocks each.  cur = block input (materialised, normalised)
     float* cur = buf[0];
     float* y1 = buf[1];
     float* y2 = buf[2];
     float* yd = buf[3];
     float* nxt = buf[4];
-    int ci = 1;  // index into A.specs / packed weights
-    int Hc = d.Hp, Wc = d.Wp;
+    // conv i: in (raw with the statistics of slot `sin` when the plan says normed) -> out, statistics into slot `sout`
+    auto conv = [&](int i, const float* in, int sin, float* out, int sout) {
+        const ConvIO io{in, packed + po.off[i], A.normed[i] ? mean[sin] : nullptr, A.normed[i] ? rstd[sin] : nullptr, out, part, mean[sout], rstd[sout],
+                        bn_m ? bn_m + A.noff[i] : nullptr, bn_r ? bn_r + A.noff[i] : nullptr};
+        return run_conv(st, plans[i], A.specs[i], io, B, d.h[A.lvl[i]], d.w[A.lvl[i]]);
+    };
+    int ci = 1;  // index into A.specs / plans
     for (int l = 1; l <= 4; ++l) {
         for (int b = 0; b < A.nblk[l - 1]; ++b) {
             const bool last = (l == 4 && b == A.nblk[3] - 1);
-            int rc, Ho, Wo, Cc;
+            const int Ho = d.h[l], Wo = d.w[l];
+            int rc, Cc;
             bool down;
             float* yout;   // raw output of the block's last conv
             int sout;      // its statistics slot
             if (A.bottleneck) {
                 // conv1 1x1 -> IN -> ReLU -> conv2 3x3 (stride) -> IN -> ReLU -> conv3 1x1 -> IN, + identity | downsample
                 down = b == 0;
-                const ConvSpec& s1 = A.specs[ci];
-                const ConvSpec& s2 = A.specs[ci + 1];
-                const ConvSpec& s3 = A.specs[ci + 2];
-                Ho = outdim(Hc, 3, s2.stride, 1); Wo = outdim(Wc, 3, s2.stride, 1);
-                rc = run_conv(st, cur, packed + pack_offset(A, ci), nullptr, nullptr, y1, part, mean[1], rstd[1], B, Hc, Wc, s1, bm(ci), br(ci));
-                if (rc) return rc;
-                rc = run_conv(st, y1, packed + pack_offset(A, ci + 1), mean[1], rstd[1], y2, part, mean[2], rstd[2], B, Hc, Wc, s2, bm(ci + 1), br(ci + 1));
-                if (rc) return rc;
-                // y1 and statistics slot 1 are free again: conv3 writes there
-                rc = run_conv(st, y2, packed + pack_offset(A, ci + 2), mean[2], rstd[2], y1, part, mean[1], rstd[1], B, Ho, Wo, s3, bm(ci + 2), br(ci + 2));
-                if (rc) return rc;
-                if (down) {
-                    rc = run_conv(st, cur, packed + pack_offset(A, ci + 3), nullptr, nullptr, yd, part, mean[3], rstd[3], B, Hc, Wc, A.specs[ci + 3], bm(ci + 3), br(ci + 3));
-                    if (rc) return rc;
-                }
-                yout = y1; sout = 1; Cc = s3.cout;
+                if ((rc = conv(ci, cur, 0, y1, 1))) return rc;
+                if ((rc = conv(ci + 1, y1, 1, y2, 2))) return rc;
+                if ((rc = conv(ci + 2, y2, 2, y1, 1))) return rc;   // y1 and statistics slot 1 are free again: conv3 writes there
+                if (down && (rc = conv(ci + 3, cur, 0, yd, 3))) return rc;
+                yout = y1; sout = 1; Cc = A.specs[ci + 2].cout;
                 ci += down ? 4 : 3;
             } else {
                 down = (l > 1 && b == 0);
-                const ConvSpec& sa = A.specs[ci];
-                const ConvSpec& sb = A.specs[ci + 1];
-                Ho = outdim(Hc, sa.ks, sa.stride, sa.pad); Wo = outdim(Wc, sa.ks, sa.stride, sa.pad);
-                rc = run_conv(st, cur, packed + pack_offset(A, ci), nullptr, nullptr, y1, part, mean[1], rstd[1], B, Hc, Wc, sa, bm(ci), br(ci));
-                if (rc) return rc;
-                rc = run_conv(st, y1, packed + pack_offset(A, ci + 1), mean[1], rstd[1], y2, part, mean[2], rstd[2], B, Ho, Wo, sb, bm(ci + 1), br(ci + 1));
-                if (rc) return rc;
-                if (down) {
-                    rc = run_conv(st, cur, packed + pack_offset(A, ci + 2), nullptr, nullptr, yd, part, mean[3], rstd[3], B, Hc, Wc, A.specs[ci + 2], bm(ci + 2), br(ci + 2));
-                    if (rc) return rc;
-                }
-                yout = y2; sout = 2; Cc = sa.cout;
+                if ((rc = conv(ci, cur, 0, y1, 1))) return rc;
+                if ((rc = conv(ci + 1, y1, 1, y2, 2))) return rc;
+                if (down && (rc = conv(ci + 2, cur, 0, yd, 3))) return rc;
+                yout = y2; sout = 2; Cc = A.specs[ci].cout;
                 ci += down ? 3 : 2;
             }
             const long long npix = (long long)B * Ho * Wo;
@@ -2792,62 +2628,69 @@ static int resnet18in_forward_impl(const void* x_nchw, bool u8, int32_t B, int32
                                    mean[sout], rstd[sout], cur, feats, B, Ho * Wo, Cc);
             } else {
                 const int c4n = Cc / 4, tpb = 256 / (c4n < 256 ? c4n : 256);
-                long long blocks = (npix + tpb - 1) / tpb;
-                if (blocks > 8192) blocks = 8192;
-                if (down) hipLaunchKernelGGL(k_norm_add_relu<true>, dim3((unsigned)blocks), dim3(256), 0, st, yout, mean[sout], rstd[sout], yd, mean[3], rstd[3], nxt, npix, Ho * Wo, Cc);
-                else hipLaunchKernelGGL(k_norm_add_relu<false>, dim3((unsigned)blocks), dim3(256), 0, st, yout, mean[sout], rstd[sout], cur, nullptr, nullptr, nxt, npix, Ho * Wo, Cc);
+                long long nb = (npix + tpb - 1) / tpb;
+                if (nb > 8192) nb = 8192;
+                if (down) hipLaunchKernelGGL(k_norm_add_relu<true>, dim3((unsigned)nb), dim3(256), 0, st, yout, mean[sout], rstd[sout], yd, mean[3], rstd[3], nxt, npix, Ho * Wo, Cc);
+                else hipLaunchKernelGGL(k_norm_add_relu<false>, dim3((unsigned)nb), dim3(256), 0, st, yout, mean[sout], rstd[sout], cur, nullptr, nullptr, nxt, npix, Ho * Wo, Cc);
             }
             if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
             float* t = cur; cur = nxt; nxt = t;
-            Hc = Ho; Wc = Wo;
         }
     }
     if (classes) return dsmil_fc_forward(feats, B, A.feat, C, fc_w, fc_b, classes, stream);
     return DSMIL_OK;
 }
 
-int dsmil_resnet18in_forward(const float* x_nchw, int32_t B, int32_t H, int32_t W, const float* conv1_w,
-                             const float* packed, const float* fc_w, const float* fc_b, int32_t C,
-                             float* feats, float* classes, void* ws, size_t ws_bytes, void* stream) {
-    return resnet18in_forward_impl(x_nchw, false, B, H, W, conv1_w, packed, fc_w, fc_b, C, feats, classes, ws,
-                                   ws_bytes, stream);
+}  // namespace
+
+extern "C" {
+
+int dsmil_resnet_mfma_forms(int32_t* wino_products, int32_t* direct_products) {
+    const Form f = make_form(0, expt());
+    if (wino_products) *wino_products = f.wino_np;
+    if (direct_products) *direct_products = f.conv_np;
+    return DSMIL_OK;
 }
 
-int dsmil_resnet18in_forward_u8(const uint8_t* x_nhwc, int32_t B, int32_t H, int32_t W, const float* conv1_w,
-                                const float* packed, const float* fc_w, const float* fc_b, int32_t C,
-                                float* feats, float* classes, void* ws, size_t ws_bytes, void* stream) {
-    return resnet18in_forward_impl(x_nhwc, true, B, H, W, conv1_w, packed, fc_w, fc_b, C, feats, classes, ws,
-                                   ws_bytes, stream);
-}
+int32_t dsmil_resnet_num_convs(int32_t depth) { const Arch* A = arch_of(depth); return A ? A->nconv : 0; }
+int32_t dsmil_resnet_norm_channels(int32_t depth) { const Arch* A = arch_of(depth); return A ? A->noff[A->nconv] : 0; }
+int32_t dsmil_resnet_feature_dim(int32_t depth) { const Arch* A = arch_of(depth); return A ? A->feat : 0; }
 
-int32_t dsmil_resnet18_norm_channels(void) { return dsmil_resnet_norm_channels(18); }
-
-int dsmil_resnet_forward(int32_t depth, const void* x, int32_t x_is_u8_nhwc, int32_t B, int32_t H, int32_t W,
-                         const float* conv1_w, const float* packed, const float* bn_mean, const float* bn_rstd,
-                         const float* fc_w, const float* fc_b, int32_t C, float* feats, float* classes, void* ws,
-                         size_t ws_bytes, void* stream) {
-    if ((bn_mean == nullptr) != (bn_rstd == nullptr)) return DSMIL_E_INVALID;
-    return resnet18in_forward_impl(x, x_is_u8_nhwc != 0, B, H, W, conv1_w, packed, fc_w, fc_b, C, feats, classes, ws,
-                                   ws_bytes, stream, bn_mean, bn_rstd, depth);
-}
-
-// precision 2 = the bf16-activation trunk (its packed image is larger)
+// precision 2 / 3 = the bf16 / fp16-activation trunk (its packed image is larger)
 size_t dsmil_resnet_packed_bytes_ex(int32_t depth, int32_t precision) {
     const Arch* A = arch_of(depth);
     if (!A || precision < 0 || precision > 3) return 0;
-    if (precision >= 2) return b16::arch_ok(*A) ? dsmil_resnet_packed_bytes(depth) + b16::packed_bytes(*A) : 0;
-    return dsmil_resnet_packed_bytes(depth);
+    const size_t n = packed_bytes(*A, make_form(precision, expt()), expt());
+    if (precision >= 2) return b16::arch_ok(*A) ? n + b16::packed_bytes(*A) : 0;
+    return n;
 }
+size_t dsmil_resnet_packed_bytes(int32_t depth) { return dsmil_resnet_packed_bytes_ex(depth, 0); }
 
 int dsmil_resnet_pack_ex(int32_t depth, const float* const* conv_w, float* packed, int32_t precision, void* stream) {
     if (precision < 0 || precision > 3) return DSMIL_E_INVALID;
-    FormOverride fo(precision >= 1 ? 1 : 0);
-    const int rc = dsmil_resnet_pack(depth, conv_w, packed, stream);
-    if (rc != DSMIL_OK || precision < 2) return rc;
     const Arch* A = arch_of(depth);
+    if (!A) return DSMIL_E_UNSUPPORTED;
+    if (!conv_w || !packed) return DSMIL_E_INVALID;
+    const Form f = make_form(precision, expt());
+    const int rc = pack_impl(*A, conv_w, packed, f, (hipStream_t)stream);
+    if (rc != DSMIL_OK || !f.trunk) return rc;
     if (!b16::arch_ok(*A)) return DSMIL_E_UNSUPPORTED;
-    return b16::pack_all(*A, conv_w, (unsigned short*)((char*)packed + dsmil_resnet_packed_bytes(depth)), (hipStream_t)stream, precision == 3);
+    return b16::pack_all(*A, conv_w, (unsigned short*)((char*)packed + packed_bytes(*A, f, expt())), (hipStream_t)stream, f.trunk);
 }
+int dsmil_resnet_pack(int32_t depth, const float* const* conv_w, float* packed, void* stream) {
+    return dsmil_resnet_pack_ex(depth, conv_w, packed, 0, stream);
+}
+
+size_t dsmil_resnet18_packed_bytes(void) { return dsmil_resnet_packed_bytes(18); }
+int dsmil_resnet18_pack(const float* const* conv_w, float* packed, void* stream) {
+    return dsmil_resnet_pack(18, conv_w, packed, stream);
+}
+
+size_t dsmil_resnet_workspace_bytes(int32_t depth, int32_t B, int32_t H, int32_t W) {
+    if (!arch_of(depth) || B <= 0 || H < 32 || W < 32) return 0;
+    return rws_layout(B, H, W, depth).total;
+}
+size_t dsmil_resnet18_workspace_bytes(int32_t B, int32_t H, int32_t W) { return dsmil_resnet_workspace_bytes(18, B, H, W); }
 
 int dsmil_resnet_forward_ex(int32_t depth, const void* x, int32_t x_is_u8_nhwc, int32_t B, int32_t H, int32_t W,
                             const float* conv1_w, const float* packed, const float* bn_mean, const float* bn_rstd,
@@ -2855,19 +2698,39 @@ int dsmil_resnet_forward_ex(int32_t depth, const void* x, int32_t x_is_u8_nhwc, 
                             size_t ws_bytes, int32_t precision, void* stream) {
     if (precision < 0 || precision > 3) return DSMIL_E_INVALID;
     if (precision >= 2 && (bn_mean || bn_rstd)) return DSMIL_E_UNSUPPORTED;
-    FormOverride fo(precision >= 1 ? 1 : 0);
-    struct B16Flag { int saved; explicit B16Flag(int v) : saved(g_b16_trunk) { g_b16_trunk = v; } ~B16Flag() { g_b16_trunk = saved; } } bf(precision >= 2 ? precision - 1 : 0);
-    return dsmil_resnet_forward(depth, x, x_is_u8_nhwc, B, H, W, conv1_w, packed, bn_mean, bn_rstd, fc_w, fc_b, C, feats, classes,
-                                ws, ws_bytes, stream);
+    if ((bn_mean == nullptr) != (bn_rstd == nullptr)) return DSMIL_E_INVALID;
+    return resnet_forward_impl(depth, make_form(precision, expt()), x, x_is_u8_nhwc != 0, B, H, W, conv1_w, packed, bn_mean, bn_rstd,
+                               fc_w, fc_b, C, feats, classes, ws, ws_bytes, stream);
 }
+
+int dsmil_resnet_forward(int32_t depth, const void* x, int32_t x_is_u8_nhwc, int32_t B, int32_t H, int32_t W,
+                         const float* conv1_w, const float* packed, const float* bn_mean, const float* bn_rstd,
+                         const float* fc_w, const float* fc_b, int32_t C, float* feats, float* classes, void* ws,
+                         size_t ws_bytes, void* stream) {
+    return dsmil_resnet_forward_ex(depth, x, x_is_u8_nhwc, B, H, W, conv1_w, packed, bn_mean, bn_rstd, fc_w, fc_b, C, feats, classes,
+                                   ws, ws_bytes, 0, stream);
+}
+
+int dsmil_resnet18in_forward(const float* x_nchw, int32_t B, int32_t H, int32_t W, const float* conv1_w,
+                             const float* packed, const float* fc_w, const float* fc_b, int32_t C,
+                             float* feats, float* classes, void* ws, size_t ws_bytes, void* stream) {
+    return dsmil_resnet_forward(18, x_nchw, 0, B, H, W, conv1_w, packed, nullptr, nullptr, fc_w, fc_b, C, feats, classes, ws, ws_bytes, stream);
+}
+
+int dsmil_resnet18in_forward_u8(const uint8_t* x_nhwc, int32_t B, int32_t H, int32_t W, const float* conv1_w,
+                                const float* packed, const float* fc_w, const float* fc_b, int32_t C,
+                                float* feats, float* classes, void* ws, size_t ws_bytes, void* stream) {
+    return dsmil_resnet_forward(18, x_nhwc, 1, B, H, W, conv1_w, packed, nullptr, nullptr, fc_w, fc_b, C, feats, classes, ws, ws_bytes, stream);
+}
+
+int32_t dsmil_resnet18_norm_channels(void) { return dsmil_resnet_norm_channels(18); }
 
 int dsmil_resnet18bn_forward(const void* x, int32_t x_is_u8_nhwc, int32_t B, int32_t H, int32_t W,
                              const float* conv1_w, const float* packed, const float* bn_mean,
                              const float* bn_rstd, const float* fc_w, const float* fc_b, int32_t C,
                              float* feats, float* classes, void* ws, size_t ws_bytes, void* stream) {
     if (!bn_mean || !bn_rstd) return DSMIL_E_INVALID;
-    return resnet18in_forward_impl(x, x_is_u8_nhwc != 0, B, H, W, conv1_w, packed, fc_w, fc_b, C, feats, classes, ws,
-                                   ws_bytes, stream, bn_mean, bn_rstd);
+    return dsmil_resnet_forward(18, x, x_is_u8_nhwc, B, H, W, conv1_w, packed, bn_mean, bn_rstd, fc_w, fc_b, C, feats, classes, ws, ws_bytes, stream);
 }
 
 }  // extern "C"
