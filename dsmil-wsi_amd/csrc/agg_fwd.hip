@@ -2076,6 +2076,60 @@ int dsmil_value_forward(const float* feats, int64_t rows, int32_t K, int32_t Kv,
     return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 
+// ---- the same layer on bf16-stored rows (k_pack_value_b16, k_value_proj_b16, k_value_proj_b16_valu: agg_value.h) ----
+size_t dsmil_value_packed_bf16_bytes(int32_t K, int32_t Kv) { return (K <= 0 || Kv <= 0) ? 0 : vb_image_bytes(K, Kv); }
+
+int dsmil_value_pack_bf16(const float* v_w, int32_t K, int32_t Kv, void* packed, void* stream) {
+    if (!v_w || !packed || K <= 0 || Kv <= 0) return DSMIL_E_INVALID;
+    if ((uintptr_t)packed % 16) return DSMIL_E_ALIGN;
+    hipLaunchKernelGGL(k_pack_value_b16, dim3(256), dim3(256), 0, (hipStream_t)stream, v_w, (bf16_t*)packed, K, Kv, vp_nks(K),
+                       vp_ntp(Kv));
+    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
+}
+
+size_t dsmil_value_workspace_bf16_bytes(int64_t rows, int32_t K, int32_t Kv) {
+    if (rows <= 0 || K <= 0 || Kv <= 0 || K > VB_MAX_K) return 0;   // (the plain kernel of wider rows reads v_w itself)
+    return vp_al(vb_image_bytes(K, Kv));
+}
+
+int dsmil_value_forward_bf16(const void* feats_bf16, int64_t rows, int32_t K, int32_t Kv, const float* v_w, const float* v_b,
+                             const void* packed, void* V_out_bf16, void* ws, size_t ws_bytes, void* stream) {
+    if (!feats_bf16 || !v_w || !v_b || !V_out_bf16 || rows <= 0 || K <= 0 || Kv <= 0) return DSMIL_E_INVALID;
+    if ((K % 8) || (Kv % 4)) return DSMIL_E_UNSUPPORTED;
+    if (((uintptr_t)feats_bf16 % 16) || ((uintptr_t)V_out_bf16 % 4)) return DSMIL_E_ALIGN;
+    if (rows * (int64_t)Kv / 256 + 1 > 0x7fffffffLL) return DSMIL_E_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    const bf16_t* x = (const bf16_t*)feats_bf16;
+    bf16_t* V = (bf16_t*)V_out_bf16;
+    if (K > VB_MAX_K) {
+        hipLaunchKernelGGL(k_value_proj_b16_valu, dim3((unsigned)((rows * Kv + 255) / 256)), dim3(256), 0, st, x, v_w, v_b, V,
+                           (long long)rows, K, Kv);
+        return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
+    }
+    const bool cut = !packed;   // round Wv into the workspace first (a caller with fixed weights packs once: dsmil_value_pack_bf16)
+    if (cut) {
+        if (!ws) return DSMIL_E_INVALID;
+        if ((uintptr_t)ws % 256) return DSMIL_E_ALIGN;
+        if (ws_bytes < vb_image_bytes(K, Kv)) return DSMIL_E_WORKSPACE;
+        packed = ws;
+    }
+    if ((uintptr_t)packed % 16) return DSMIL_E_ALIGN;
+    if (cut) {
+        const int rc = dsmil_value_pack_bf16(v_w, K, Kv, ws, stream);
+        if (rc) return rc;
+    }
+    const int nks = vp_nks(K);
+    const int lds = 2 * nks * VB_BM * 16;
+    const bool full = K % 64 == 0;
+    void (*fn)(const bf16_t*, const f32x4*, const float*, bf16_t*, long long, int, int) =
+        full ? (nks == 32 ? k_value_proj_b16<32, true> : k_value_proj_b16<0, true>) : k_value_proj_b16<0, false>;
+    if (!dsmil_lds::allow((const void*)fn, lds)) return DSMIL_E_LAUNCH;
+    const long long tiles = (rows + VB_BM - 1) / VB_BM;
+    hipLaunchKernelGGL(fn, dim3((unsigned)tiles), dim3(VP_THREADS), lds, st, x, (const f32x4*)packed, v_b, V, (long long)rows, K,
+                       Kv);
+    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
+}
+
 int dsmil_agg_forward_ex(const float* feats, const float* vals, const int64_t* offsets,
                          int32_t n_bags, int64_t total_rows, int64_t max_rows,
                          const dsmil_agg_params* p, const dsmil_agg_opts* opts, const float* classes_in,

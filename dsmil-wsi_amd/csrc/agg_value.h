@@ -1,6 +1,7 @@
 // agg_value.h — the value stream of BClassifier(passing_v=True), dsmil.py:35-39,48:  V = ReLU(x Wv^T + bv)  and its
-// parameter gradients.  Included from agg_fwd.hip (DSMIL_VALUE_FWD: k_pack_value, k_value_proj, k_value_proj_valu) and
-// from agg_bwd.hip (DSMIL_VALUE_BWD: k_value_tn, k_value_reduce).
+// parameter gradients.  Included from agg_fwd.hip (DSMIL_VALUE_FWD: k_pack_value, k_value_proj, k_value_proj_valu and, for
+// bf16-stored rows, k_pack_value_b16, k_value_proj_b16, k_value_proj_b16_valu: described above them) and from agg_bwd.hip
+// (DSMIL_VALUE_BWD: k_value_tn, k_value_reduce).
 //
 // Forward, k_value_proj.  A GEMM with Kv output columns per row on v_mfma_f32_32x32x16_f16 in the arithmetic of agg_f2.h:
 // x' = x * 2^e per ROW, Wv' = Wv * 2^f per TENSOR (f2_scale), both cut into two fp16 planes (split2h_scaled / the pack
@@ -271,6 +272,175 @@ __global__ __launch_bounds__(256) void k_value_proj_valu(const float* __restrict
     for (int k = 0; k < K; ++k) s = fmaf(xr[k], wr[k], s);
     s += bias[j];
     V[i] = s < 0.f ? 0.f : s;
+}
+// ---- bf16-stored rows: k_pack_value_b16, k_value_proj_b16, k_value_proj_b16_valu ------------------------------------------
+// V = bf16_rne(max(0, x w_b^T + v_b)) for bf16 rows x and w_b = bf16_rne(Wv): both are exact MFMA operands, so ONE
+// v_mfma_f32_32x32x16_bf16 product per MAC replaces the three plane products above — no cut, no scale, fp32 accumulation.
+//   * a workgroup (four waves) owns a tile of 64 rows and produces ALL Kv columns of it: x is read once;
+//   * the tile lives in LDS as the bf16 it is stored as, [k-octet][row] x 16 B (octet o = k / 8: step o >> 1, half o & 1):
+//     2 K bytes per row, half the fp32 kernel's plane image.  K <= 512: 64 KiB, so TWO workgroups share a compute unit and
+//     one stages its tile while the other multiplies (the fp32 kernel has one); K <= 1024: 128 KiB, 64 rows where the fp32
+//     kernel holds 32;
+//   * staging: a wave-wide load takes 8 rows x 128 B (lane = (row & 7, octet & 7): whole 128-B lines), the 8 lanes of a
+//     ds_write_b128 group write 8 consecutive cells (conflict-free); no transform, no second pass;
+//   * A-fragment read: one ds_read_b128 over 32 consecutive cells per lane half (conflict-free), 2 reads per 8 MFMAs;
+//   * wave w owns column groups w, w + 4, ... of 128 columns (four 32 x 32 accumulator tiles per 32 rows: 128 accumulator
+//     registers).  The weights come from the packed image (L2; 512 KiB at K = Kv = 512) as B fragments, two register sets,
+//     each refilled for step s + 2 behind the MFMAs of step s;
+//   * epilogue: bias and ReLU on the accumulators; the lane halves exchange the tiles of a pair (v_permlane32_swap: lanes
+//     0..31 then hold tile 2u, lanes 32..63 tile 2u + 1, each for all 32 rows), neighbouring lanes exchange one value (DPP)
+//     so that a lane holds two adjacent columns of one row: a 4-byte store instruction writes two rows in 128-B runs.
+// Every output's sum runs over the k steps 0, 1, ... in turn whatever its row's place in the call: its bits depend on K alone.
+// K is zero-padded to a multiple of 32 in the staged tile and in the pack, Kv to a multiple of 128 columns in the pack.
+// K % 8 == 0 and Kv % 4 == 0 (16-B cells, 4-B stores: dsmil_agg_forward_bf16's own condition); K > 1024 takes
+// k_value_proj_b16_valu.
+constexpr int VB_BM = 64;                             // rows per tile
+constexpr int VB_MAX_K = 1024;                        // widest K of the MFMA kernel (128 KiB tile)
+inline size_t vb_image_bytes(int K, int Kv) { return (size_t)vp_nks(K) * vp_ntp(Kv) * 64 * 16; }
+
+// fp32 Wv [Kv, K] -> bf16 (round to nearest even), B-fragment order:
+//   [step s][tile t][lane (l31, hi)][e] = bf16(Wv[32 t + l31][16 s + 8 hi + e])   (0 past Kv / K)
+__global__ __launch_bounds__(256) void k_pack_value_b16(const float* __restrict__ v_w, bf16_t* __restrict__ out, int K, int Kv,
+                                                        int nks, int ntp) {
+    const long long total = (long long)nks * ntp * 512;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int e = (int)(i & 7), ln = (int)((i >> 3) & 63);
+        const long long st = i >> 9;
+        const int t = (int)(st % ntp), s = (int)(st / ntp);
+        const int j = 32 * t + (ln & 31), k = 16 * s + 8 * (ln >> 5) + e;
+        out[i] = (j < Kv && k < K) ? f2bf(v_w[(long long)j * K + k]) : (bf16_t)0;
+    }
+}
+
+__device__ __forceinline__ float vb_xor1(float v) {   // the value of lane ^ 1 (DPP quad_perm [1, 0, 3, 2])
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
+}
+
+// grid = tiles of 64 rows; FULL: K % 64 == 0 (every staging load is a real cell); NKS = the number of 16-k steps when it is a
+// compile-time constant (straight-line MFMA loop), 0 = the run-time value
+template <int NKS, bool FULL>
+__global__ __launch_bounds__(VP_THREADS, 2) void k_value_proj_b16(const bf16_t* __restrict__ x, const f32x4* __restrict__ wimg,
+                                                                  const float* __restrict__ bias, bf16_t* __restrict__ V,
+                                                                  long long rows, int K, int Kv) {
+    constexpr int BM = VB_BM;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    f32x4* sX = reinterpret_cast<f32x4*>(smem);          // [k-octet][BM] x 16 B
+    const int nks = NKS ? NKS : vp_nks(K);
+    const int ntp = vp_ntp(Kv);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, hi = lane >> 5;
+    const long long row0 = (long long)blockIdx.x * BM;
+    // ---- stage: wave w brings rows 16 w .. 16 w + 15, eight rows x eight octets per load instruction
+    {
+        const int rr = lane & 7, o = lane >> 3;
+        const int noct = 2 * nks, kreal = K >> 3;
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb) {
+            const int row = 16 * wave + 8 * rb + rr;
+            long long gr = row0 + row;
+            if (gr >= rows) gr = rows - 1;               // rows past the end repeat the last row and are never stored
+            const bf16_t* src = x + gr * (long long)K;
+            if constexpr (FULL) {
+#pragma unroll 8
+                for (int ko = o; ko < noct; ko += 8) sX[ko * BM + row] = *(const DSMIL_GLOBAL f32x4*)(src + 8 * ko);
+            } else {
+                for (int ko = o; ko < noct; ko += 8) {
+                    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+                    if (ko < kreal) v = *(const DSMIL_GLOBAL f32x4*)(src + 8 * ko);
+                    sX[ko * BM + row] = v;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // ---- all Kv columns of the tile: wave w takes the 128-column groups w, w + 4, ...
+    union Frag { f32x4 f; bf16x8 v; };
+    const long long sstride = (long long)ntp * 64;       // 16-B units per step of the image
+    for (int g = wave; g < ntp / 4; g += 4) {
+        f32x16 acc[2][4];
+#pragma unroll
+        for (int rg = 0; rg < 2; ++rg)
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[rg][t][r] = 0.f;
+        const f32x4* wp = wimg + (long long)g * 256 + lane;
+        Frag wr[2][4];
+        auto load_w = [&](auto slot_, int s) {
+            constexpr int SL = decltype(slot_)::value;
+            const int sw = s < nks ? s : nks - 1;        // (past the last step: a harmless re-read, no branch)
+            const f32x4* p = wp + (long long)sw * sstride;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) wr[SL][t].f = *(const DSMIL_GLOBAL f32x4*)(p + t * 64);
+        };
+        auto step = [&](auto slot_, int s) {
+            constexpr int SL = decltype(slot_)::value;
+            Frag xa[2];
+            const f32x4* p = sX + (s * 2 + hi) * BM + l31;
+            xa[0].f = p[0];
+            xa[1].f = p[32];
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int rg = 0; rg < 2; ++rg)
+                    acc[rg][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[rg].v, wr[SL][t].v, acc[rg][t], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            load_w(slot_, s + 2);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        constexpr int UNR = NKS ? NKS / 2 : 1;
+        load_w(std::integral_constant<int, 0>{}, 0);
+        load_w(std::integral_constant<int, 1>{}, 1);
+#pragma unroll UNR
+        for (int s = 0; s < nks; s += 2) {               // (nks is even)
+            step(std::integral_constant<int, 0>{}, s);
+            step(std::integral_constant<int, 1>{}, s + 1);
+        }
+        // ---- bias, ReLU, round, store.  reg 4q + e of tile t <-> row 32 rg + 8q + 4 hi + e, column 32 (4g + t) + l31
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int j0 = 32 * (4 * g + 2 * u) + l31, j1 = j0 + 32;
+            const float b0 = j0 < Kv ? bias[j0] : 0.f, b1 = j1 < Kv ? bias[j1] : 0.f;
+            const int j = hi ? j1 : j0;                  // this lane's column after the half exchange
+            const bool jok = (j & ~1) < Kv;              // (Kv % 4 == 0: the pair j & ~1, (j & ~1) + 1 is inside or outside together)
+#pragma unroll
+            for (int rg = 0; rg < 2; ++rg)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    float a = acc[rg][2 * u][r] + b0, b = acc[rg][2 * u + 1][r] + b1;
+                    a = a < 0.f ? 0.f : a;               // (a NaN stays a NaN, as torch's ReLU)
+                    b = b < 0.f ? 0.f : b;
+                    // lanes 0..31 keep a (tile 2u, rows 8q + e) and take the upper half's a (tile 2u, rows 8q + 4 + e); lanes
+                    // 32..63 take the lower half's b (tile 2u + 1, rows 8q + e) and keep b (tile 2u + 1, rows 8q + 4 + e)
+                    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+                    const float lo = __uint_as_float(sw[0]), up = __uint_as_float(sw[1]);   // rows 8q + e / 8q + 4 + e of column j
+                    // an even lane keeps row 8q + e and takes its neighbour's, an odd lane keeps row 8q + 4 + e
+                    const bool odd = lane & 1;
+                    const float got = vb_xor1(odd ? lo : up);
+                    const unsigned w2 = odd ? pack_bf16x2_hw(got, up) : pack_bf16x2_hw(lo, got);
+                    const int row = 32 * rg + 8 * (r >> 2) + (odd ? 4 : 0) + (r & 3);
+                    const long long gr = row0 + row;
+                    if (jok && gr < rows) *reinterpret_cast<unsigned*>(V + gr * (long long)Kv + (j & ~1)) = w2;
+                }
+        }
+    }
+}
+
+// any other width (K > VB_MAX_K): one thread per output, fp32 FMAs of the exact bf16 products in k order
+__global__ __launch_bounds__(256) void k_value_proj_b16_valu(const bf16_t* __restrict__ x, const float* __restrict__ v_w,
+                                                             const float* __restrict__ bias, bf16_t* __restrict__ V,
+                                                             long long rows, int K, int Kv) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows * Kv) return;
+    const long long n = i / Kv;
+    const int j = (int)(i - n * Kv);
+    const bf16_t* xr = x + n * (long long)K;
+    const float* wr = v_w + (long long)j * K;
+    float s = 0.f;
+    for (int k = 0; k < K; ++k) s = fmaf(bf2f(xr[k]), bf2f(f2bf(wr[k])), s);
+    s += bias[j];
+    V[i] = f2bf(s < 0.f ? 0.f : s);
 }
 #endif  // DSMIL_VALUE_FWD
 

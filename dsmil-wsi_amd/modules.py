@@ -149,13 +149,18 @@ class BClassifier(nn.Module):
         whether or not they require a gradient (ops.value_proj: Linear + ReLU in one HIP launch; its parameter gradients in
         ops.value_proj_backward, the gradient of the rows in ops.value_proj_backward_rows).  An ACTIVE dropout (training
         mode, p > 0) is torch's own, applied to the rows first — the native projection then runs on the dropped rows; torch's
-        random stream is not reproduced inside a kernel.  bf16-stored rows keep the torch route (nn.Linear + ReLU)."""
+        random stream is not reproduced inside a kernel.  bf16-stored rows (inference only) take the native projection of
+        the bf16 path (dsmil_value_forward_bf16: fp32 master weights are rounded inside, as ops.agg_forward does with the
+        aggregator's); with an ACTIVE dropout they keep the torch route (nn.Linear + ReLU)."""
         if not self.passing_v:
             return None
         drop, lin = self.v[0], self.v[1]
+        active = drop.training and drop.p > 0
+        if feats.dtype == torch.bfloat16 and not active:
+            return ops.value_proj(feats.detach(), lin.weight.detach(), lin.bias.detach())
         if feats.dtype != torch.float32:
             return self.v(feats)
-        x = drop(feats) if (drop.training and drop.p > 0) else feats
+        x = drop(feats) if active else feats
         return _ValueProjFunction.apply(x, lin.weight, lin.bias)
 
     def forward(self, feats, c):
@@ -177,11 +182,11 @@ class MILNet(nn.Module):
     def _fused(self, x=None):
         """Whether the fused native calls (FCLayer's logits + the aggregator in one call sequence) apply: the two modules
         are FCLayer + BClassifier and — given rows — ``x`` is a 2-D CUDA tensor whose dtype the value stream takes natively
-        (with passing_v: fp32 only).  Every caller adds its own further conditions."""
+        (with passing_v: fp32 or bf16).  Every caller adds its own further conditions."""
         ic, bc = self.i_classifier, self.b_classifier
         if not (isinstance(ic, FCLayer) and isinstance(bc, BClassifier)):
             return False
-        return x is None or (x.is_cuda and x.dim() == 2 and (x.dtype == torch.float32 or not bc.passing_v))
+        return x is None or (x.is_cuda and x.dim() == 2 and (x.dtype in (torch.float32, torch.bfloat16) or not bc.passing_v))
 
     def _lin_weights(self, detach=False):
         """(FCLayer's nn.Linear, the eight-key weight dict of the fused native calls)."""
@@ -192,7 +197,7 @@ class MILNet(nn.Module):
         ic, bc = self.i_classifier, self.b_classifier
         if self._fused(x):
             # one fused native call: instance logits + aggregator (dsmil.py:70-74); with passing_v the native value
-            # projection runs in front of it and its result goes in as `vals` (bf16 rows keep the two-module route below);
+            # projection runs in front of it and its result goes in as `vals` (bf16 rows: the bf16 forms of both calls);
             # rows that require a gradient get it from the native backward (k_bwd_gx, k_value_gx)
             _, w = self._lin_weights()
             return _AggFunction.apply(x, None, bc._values(x), None, *w.values(), bc.nonlinear)[0:4]
@@ -200,16 +205,20 @@ class MILNet(nn.Module):
         prediction_bag, A, B = bc(feats, classes)
         return classes, prediction_bag, A, B
 
-    def graphed(self, n_rows):
+    def graphed(self, n_rows, dtype=None):
         """A hipGraph-replayed forward for bags of exactly ``n_rows`` rows (inference; weights frozen): returns a
-        callable feats -> (classes, pred [1,C], A, B [1,C,K]).  Single-bag latency is launch-bound otherwise."""
+        callable feats -> (classes, pred [1,C], A, B [1,C,K]).  Single-bag latency is launch-bound otherwise.
+        ``dtype``: the bags' storage type, torch.float32 or torch.bfloat16 (the bf16-storage path, fp32 outputs); None = the
+        parameters' own (bf16 after ``.bfloat16()``, else fp32)."""
         if not self._fused():
             raise NotImplementedError("graphed forward: FCLayer + BClassifier")
         bc = self.b_classifier
         lin, w = self._lin_weights(detach=True)
         # passing_v: the value projection is captured with the rest (inference: the dropout of bc.v is the identity)
         v_w, v_b = (bc.v[1].weight.detach(), bc.v[1].bias.detach()) if bc.passing_v else (None, None)
-        g = ops.GraphedAggForward(w, n_rows, lin.in_features, nonlinear=bc.nonlinear, device=lin.weight.device,
+        if dtype is None:
+            dtype = torch.bfloat16 if lin.weight.dtype == torch.bfloat16 else torch.float32
+        g = ops.GraphedAggForward(w, n_rows, lin.in_features, nonlinear=bc.nonlinear, device=lin.weight.device, dtype=dtype,
                                   v_w=v_w, v_b=v_b)
 
         def run(feats):
@@ -257,14 +266,12 @@ class MILNet(nn.Module):
         bc = self.b_classifier
         if not self._fused():
             return [self.forward(b) for b in bags]
-        if bc.passing_v and bags[0].dtype != torch.float32:
-            return [self.forward(b) for b in bags]   # (the value layer on bf16-stored rows: the torch route, bag by bag)
         if isinstance(bags, tuple):
             feats, lengths = bags
         else:
             lengths = [int(b.shape[0]) for b in bags]
             feats = torch.cat(list(bags), dim=0)
-        # passing_v: ONE projection over the concatenated rows, then one aggregator call over the batch
+        # passing_v: ONE projection over the concatenated rows, then one aggregator call over the batch (fp32 and bf16 rows)
         vals = bc._values(feats)
         classes, pred, A, B, _ = ops.agg_forward(feats, lengths, self._lin_weights(detach=True)[1], vals=vals,
                                                  nonlinear=bc.nonlinear)

@@ -367,10 +367,51 @@ def _value_params(v_w, dev):
     return _cached(_split_cache, ("value", str(dev), _tkey(v_w)), dev, [v_w], make)[0]
 
 
+def _value_params_b16(v_w, v_b, dev):
+    """bf16 rows: BClassifier.v's weight rounded to bf16 in MFMA-fragment order (dsmil_value_pack_bf16, csrc/agg_value.h), the
+    fp32 weight the entry also takes and the bias rounded to bf16 and kept as fp32 (what module.bfloat16() would hold, as
+    _bf16_params does for the aggregator's), prepared once per weight set.  v_w / v_b: fp32 masters or bf16 parameters."""
+    Kv, K = v_w.shape
+
+    def make():
+        w32 = v_w.detach().to(torch.float32).contiguous()
+        b32 = v_b.detach().to(torch.bfloat16).to(torch.float32).contiguous()
+        nbytes = _native.lib().dsmil_value_packed_bf16_bytes(K, Kv)
+        return (_pack_image(dev, nbytes, "dsmil_value_pack_bf16", _ptr(w32), K, Kv), w32, b32)
+    return _cached(_split_cache, ("value_b16", str(dev), _tkey(v_w), _tkey(v_b)), dev, [v_w, v_b], make)
+
+
+def _value_proj_b16(feats, v_w, v_b):
+    """dsmil_value_forward_bf16: bf16 rows [rows, K] -> bf16 V [rows, Kv] in one native launch."""
+    if not (feats.is_cuda and v_w.is_cuda and v_b.is_cuda):
+        raise RuntimeError("feats, v_w and v_b must be CUDA(HIP) tensors for the native path")
+    feats = feats if feats.is_contiguous() else feats.contiguous()
+    dev = feats.device
+    rows, K = feats.shape
+    Kv = v_w.shape[0]
+    if v_w.shape[1] != K or v_b.numel() != Kv:
+        raise ValueError(f"v_w must be [Kv,{K}] and v_b [Kv], got {tuple(v_w.shape)} / {tuple(v_b.shape)}")
+    V = torch.empty((rows, Kv), dtype=torch.bfloat16, device=dev)
+    if rows == 0:
+        return V
+    packed, w32, b32 = _value_params_b16(v_w, v_b, dev)
+    with torch.cuda.device(dev):
+        rc = _native.lib().dsmil_value_forward_bf16(_ptr(feats), rows, K, Kv, _ptr(w32), _ptr(b32), _ptr(packed), _ptr(V), None, 0,
+                                                    _stream(dev))
+    _native.check(rc, "dsmil_value_forward_bf16")
+    return V
+
+
 def value_proj(feats, v_w, v_b, row_map=None):
     """dsmil_value_forward: V = ReLU(feats @ v_w^T + v_b), the Linear + ReLU of BClassifier.v (dsmil.py:35-39,48), in ONE
     native launch (fp32 in, fp32 out; the weight planes are cut once per weight set).  feats [rows, K] fp32 CUDA, v_w [Kv, K],
-    v_b [Kv]; ``row_map`` (int64 [n]): logical row i is physical row row_map[i] of feats.  Returns V [n, Kv] in logical order."""
+    v_b [Kv]; ``row_map`` (int64 [n]): logical row i is physical row row_map[i] of feats.  Returns V [n, Kv] in logical order.
+    bf16 ``feats`` select dsmil_value_forward_bf16 (the bf16-storage path: v_w and v_b — fp32 masters or bf16 parameters —
+    are rounded to bf16, fp32 accumulation, one bf16 MFMA product per MAC): bf16 V [rows, Kv], inference only, no row map."""
+    if feats.dtype == torch.bfloat16:
+        if row_map is not None:
+            raise ValueError("row_map is implemented for the fp32 path")
+        return _value_proj_b16(feats, v_w, v_b)
     feats = _f32c(feats, "feats"); v_w = _f32c(v_w, "v_w"); v_b = _f32c(v_b, "v_b")
     dev = feats.device
     rows, K = feats.shape
@@ -449,16 +490,15 @@ class GraphedAggForward:
         g = GraphedAggForward(w, n_rows, K)          # captures once (weights are read from `w`'s tensors in place)
         classes, pred, A, B, idx = g(feats)          # copies feats into the static input, replays, returns the
                                                      # static output tensors (valid until the next call)
-    Inference only: the capture holds the addresses of the weights and of their packed plane cuts, so the weights
+    ``dtype=torch.bfloat16`` captures the bf16-storage path; with ``v_w`` / ``v_b`` the value projection of either dtype is
+    one more launch of the same capture.  Inference only: the capture holds the addresses of the weights and of their packed plane cuts, so the weights
     must stay as they are — build a new object after an optimizer step or a load_state_dict."""
 
     def __init__(self, w, n_rows, K, nonlinear=True, device=None, dtype=torch.float32, v_w=None, v_b=None):
         dev = torch.device(device) if device is not None else w["q0_w"].device
         self.w, self.n, self.nonlinear, self.dev = w, int(n_rows), nonlinear, dev
-        if v_w is not None and dtype != torch.float32:
-            raise ValueError("the value layer (v_w / v_b) is implemented for fp32 bags")
 
-        def fwd():   # with v_w / v_b (BClassifier(passing_v=True)): the projection launch is captured with the rest
+        def fwd():   # with v_w / v_b (BClassifier(passing_v=True)): the projection launch is captured with the rest (either dtype)
             vals = self._vals = value_proj(self.x, v_w, v_b) if v_w is not None else None   # (V lives as long as the graph)
             return agg_forward(self.x, [self.n], w, vals=vals, nonlinear=nonlinear, offsets=self.offsets)
         self.x = torch.zeros((self.n, K), dtype=dtype, device=dev)
@@ -474,7 +514,8 @@ class GraphedAggForward:
         self._keep = [_split_params(_f32c(w["q0_w"], "q0_w"), _f32c(w.get("q2_w"), "q2_w"), nonlinear, dev)
                       if dtype == torch.float32 else _bf16_params(w, nonlinear, dev)]
         if v_w is not None:
-            self._keep.append(_value_params(_f32c(v_w, "v_w"), dev))
+            self._keep.append(_value_params(_f32c(v_w, "v_w"), dev) if dtype == torch.float32
+                              else _value_params_b16(v_w, v_b, dev))
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.out = fwd()

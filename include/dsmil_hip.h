@@ -349,6 +349,32 @@ int dsmil_value_backward_rows(const float* feats, const float* V, const float* g
                               const float* v_w, const void* packed, int32_t accumulate, float* g_feats, void* ws,
                               size_t ws_bytes, void* stream);
 
+/* ---- the value stream on bf16-stored rows (ABI 6, additive: detected by SYMBOL like dsmil_agg_backward_rows) -----------------
+ * Replaces `V = self.v(feats)` of dsmil.py:48 with self.v = Sequential(Dropout, Linear(K, K), ReLU) (dsmil.py:35-39) for the
+ * bf16-storage aggregator (dsmil_agg_forward_bf16, whose `vals` operand the result is):
+ *     V[n, j] = bf16(max(0, sum_k feats[n, k] w_b[j, k] + v_b[j])),   w_b = bf16(v_w),  round to nearest even both times,
+ * bf16 rows in, bf16 rows out, fp32 accumulation: one bf16 MFMA product per MAC (csrc/agg_value.h, k_value_proj_b16).  Every
+ * output's sum runs in an order that depends on K alone — not on the row's place in the call or the number of rows — so a
+ * row's result has the same bits in any batch.  Inference only (there is no backward for bf16 rows), no row map.
+ *   v_w [Kv, K] fp32 (rounded inside), v_b [Kv] fp32, read as it is (the caller passes bf16-rounded values there if it wants
+ *                        what module.bfloat16() holds, as with every bias of the bf16 path).  K % 8 == 0 and Kv % 4 == 0, else
+ *                        DSMIL_E_UNSUPPORTED (dsmil_agg_forward_bf16's own condition on its operands).
+ *   dsmil_value_pack_bf16     replaces nothing in the reference (dsmil.py:35-39's nn.Linear reads its weights as they are):
+ *                        rounds v_w ONCE per weight set into dsmil_value_packed_bf16_bytes(K, Kv) bytes (16-B aligned) in
+ *                        MFMA-fragment order, zero padded past K and Kv.
+ *   dsmil_value_forward_bf16  dsmil.py:35-39,48.  feats_bf16 [rows, K] (16-B aligned), V_out_bf16 [rows, Kv].  packed: that
+ *                        image, or NULL = round v_w into `ws` first (then ws must hold dsmil_value_workspace_bf16_bytes(rows,
+ *                        K, Kv) bytes, 256-B aligned; with an image ws may be NULL).  One launch (two with packed == NULL).
+ *                        K <= 1024 on the matrix cores, wider rows on a plain kernel (same arithmetic, k order; it reads v_w and
+ *                        needs neither image nor workspace).  NULL operands: DSMIL_E_INVALID; a misaligned image, workspace or
+ *                        row pointer: DSMIL_E_ALIGN; a short workspace: DSMIL_E_WORKSPACE — all before any launch.  Never
+ *                        allocates or synchronises: capturable in a graph. */
+size_t dsmil_value_packed_bf16_bytes(int32_t K, int32_t Kv);
+int dsmil_value_pack_bf16(const float* v_w, int32_t K, int32_t Kv, void* packed, void* stream);
+size_t dsmil_value_workspace_bf16_bytes(int64_t rows, int32_t K, int32_t Kv);
+int dsmil_value_forward_bf16(const void* feats_bf16, int64_t rows, int32_t K, int32_t Kv, const float* v_w, const float* v_b,
+                             const void* packed, void* V_out_bf16, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- one training step per C call (ABI 3) --------------------------------------------------------
  * Replaces the body of the reference's training loop for one bag, train_tcga.py:60-75 (train_mil.py:44-56 likewise):
  *     optimizer.zero_grad()
