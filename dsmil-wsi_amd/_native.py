@@ -182,6 +182,12 @@ SIGNATURES = {
                                                ctypes.POINTER(AggParams), c_f32p, c_f32p, c_i64p, c_f32p, c_f32p, c_f32p,
                                                c_f32p, c_f32p, ctypes.POINTER(AggGrads), c_f32p, c_i64p, ctypes.c_void_p,
                                                ctypes.c_size_t, ctypes.c_void_p, c_f32p]),
+    "dsmil_agg_backward_bags_bf16_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                                                       ctypes.c_int32, ctypes.c_int32]),
+    "dsmil_agg_backward_bags_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i64p, ctypes.c_int32, ctypes.c_int64,
+                                                    ctypes.c_int64, ctypes.POINTER(AggParams), c_f32p, c_f32p, c_i64p, c_f32p,
+                                                    c_f32p, c_f32p, c_f32p, c_f32p, ctypes.POINTER(AggGrads), c_f32p,
+                                                    ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "dsmil_agg_loss_head_bags": (ctypes.c_int, [c_f32p, c_i64p, c_f32p, c_i64p, c_f32p, ctypes.c_int32, ctypes.c_int32,
                                                 c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
     "dsmil_value_backward_rows": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,

@@ -218,8 +218,8 @@ __global__ void k_train_prologue(const float* __restrict__ q0_w, const float* __
 }
 
 // ---- k_bwd_qrow: q_c = q(x[idx_c]) (dsmil.py:53-54), one workgroup per class ------------------
-template <int VEC>
-__device__ __forceinline__ void qrow_body(const float* __restrict__ x, const float* __restrict__ q0_w,
+template <int VEC, typename XT = float>
+__device__ __forceinline__ void qrow_body(const XT* __restrict__ x, const float* __restrict__ q0_w,
                                           const float* __restrict__ q0_b, const float* __restrict__ q2_w,
                                           const float* __restrict__ q2_b, float* __restrict__ out, int K, int nonlinear) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -229,7 +229,7 @@ __device__ __forceinline__ void qrow_body(const float* __restrict__ x, const flo
         const float* wr = q0_w + (long long)(wave * 32 + jb) * K;
         for (int k0 = 0; k0 < K; k0 += 256) {
             const int k = k0 + lane * 4;
-            const f32x4 xv = load4<VEC, float>(x, k, K);
+            const f32x4 xv = load4<VEC, XT>(x, k, K);
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const f32x4 wv = load4<VEC, float>(wr + (long long)u * K, k, K);
@@ -361,7 +361,8 @@ __device__ __forceinline__ void halfwave_colsum64(const float (&v)[64], int l31,
     }
 }
 
-template <int NW, int VEC, bool BAGS = false>
+// XT: storage type of the rows.  bf16_t rows take the register-staged tile at every NW (the LDS-DMA tile stages fp32 bytes).
+template <int NW, int VEC, bool BAGS = false, typename XT = float>
 __global__ __launch_bounds__(NW * 64, (NW == 1 ? 1 : 2)) void k_bwd_rows(BwdRowsArgs b) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const AttendArgs& a = b.at;
@@ -391,10 +392,10 @@ __global__ __launch_bounds__(NW * 64, (NW == 1 ? 1 : 2)) void k_bwd_rows(BwdRows
     const bool valid = row < Nb;
     f32x16 Q[4];
     const StoreH hook{a.nonlinear ? b.Hbuf + off0 * QD : nullptr, row, valid && a.nonlinear, hi};
-    if constexpr (VEC == 4) {
+    if constexpr (VEC == 4 && sizeof(XT) == 4) {
         if (!mlp_tile_split_dma<NW, NP_BWD, false>(a, bag, tile, smem, Q, hook)) return;
     } else {
-        if (!mlp_tile_split<NW, VEC, NP_BWD>(a, bag, tile, smem, Q, hook)) return;
+        if (!mlp_tile_split<NW, VEC, NP_BWD, StoreH, XT>(a, bag, tile, smem, Q, hook)) return;
     }
     const long long rc = valid ? row : Nb - 1;
     const float scale = 0.08838834764831845f;  // 1/sqrt(128)
@@ -507,7 +508,7 @@ __device__ __forceinline__ float halfwave_colsum16(const float (&v)[16], int l31
     return a1 + __shfl_xor(a1, 1, 64);
 }
 
-template <bool BAGS = false>
+template <bool BAGS = false, typename XT = float>
 __global__ __launch_bounds__(HS_THREADS, 2) void k_bwd_rows_hs(BwdRowsArgs b) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const AttendArgs& a = b.at;
@@ -522,7 +523,7 @@ __global__ __launch_bounds__(HS_THREADS, 2) void k_bwd_rows_hs(BwdRowsArgs b) {
     }
     const long long Nb = a.offsets[bag + 1] - a.offsets[bag];
     f32x16 Hw[HS_RG], Qw[HS_RG];
-    if (!mlp_tile_hs<NP_BWD>(a, bag, tile, smem, Hw, Qw)) return;
+    if (!mlp_tile_hs<NP_BWD, XT>(a, bag, tile, smem, Hw, Qw)) return;
     const float* Dv = b.Dv + (long long)bag * a.C;
     const int C = a.C, u0 = 32 * wave + 4 * hi;     // reg 4q+e <-> unit u0 + 8q + e
     const float scale = 0.08838834764831845f;       // 1/sqrt(128)
@@ -673,7 +674,7 @@ constexpr int TN_WGS = 384;     // target workgroups per launch: sets the number
 struct TnArgs {
     const float* A0;
     const float* A1;
-    const float* X;
+    const void* X;        // fp32, or bf16 (k_tn_split's XT)
     const float* Hb;
     const int64_t* rowmap;
     float* part0;
@@ -696,8 +697,11 @@ struct TnArgs {
 // that call's data loads.  Vector memory returns in order: waiting for map entries requested after the previous step's data
 // (as the first form did — and, the wait being emitted behind the `if (map)`, also when there was no map) drained the whole
 // queue at every prefetch, so only one step's loads were ever in flight.
-template <bool WIDE, bool MAP>
+// XT (WIDE only): storage type of X.  bf16_t: the B role of an X slab fetches 8 bytes per row and widens them; the H slabs and
+// the A role read fp32 as before (the choice is uniform per wave).
+template <bool WIDE, bool MAP, typename XT = float>
 __global__ __launch_bounds__(256, 2) void k_tn_split(TnArgs a) {
+    static_assert(WIDE || sizeof(XT) == 4, "bf16 rows are 16-B aligned with K % 8 == 0: the wide form");
     __shared__ __attribute__((aligned(16))) unsigned sA[3 * QD * TN_LDW];
     __shared__ __attribute__((aligned(16))) unsigned sB[3 * 64 * TN_LDW];
     __shared__ float s_cs[512];
@@ -707,7 +711,7 @@ __global__ __launch_bounds__(256, 2) void k_tn_split(TnArgs a) {
     if (split >= a.S) return;
     const bool is_h = slab >= a.nx;
     const float* Am = is_h ? a.A1 : a.A0;
-    const float* Bm = is_h ? a.Hb : a.X;
+    const float* Bm = is_h ? a.Hb : reinterpret_cast<const float*>(a.X);   // (XT = bf16_t: the X slabs read xb16 below instead)
     const int ldb = is_h ? QD : a.K;
     const int col0 = (is_h ? slab - a.nx : slab) * 64;
     const int64_t* bmap = is_h ? nullptr : a.rowmap;
@@ -736,6 +740,17 @@ __global__ __launch_bounds__(256, 2) void k_tn_split(TnArgs a) {
 #pragma unroll
                 for (int p = 0; p < 3; ++p)
                     fa[tt][p].f = *reinterpret_cast<const f32x4*>(&sA[(p * QD + 32 * (2 * up + tt) + l31) * TN_LDW + 4 * j]);
+            if constexpr (sizeof(XT) == 2) {
+                if (!is_h) {   // bf16 rows (uniform per workgroup): the planes 1, 2 of X are identically zero — 3 products, not 6
+#pragma unroll
+                    for (int qq = P0; qq < 9; ++qq)
+#pragma unroll
+                        for (int tt = 0; tt < 2; ++tt)
+                            if (S3_PB(qq) == 0)
+                                acc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tt][S3_PA(qq)].v, fb[0].v, acc[tt], 0, 0, 0);
+                    continue;
+                }
+            }
 #pragma unroll
             for (int qq = P0; qq < 9; ++qq)
 #pragma unroll
@@ -785,6 +800,14 @@ __global__ __launch_bounds__(256, 2) void k_tn_split(TnArgs a) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) pr[e] = nmap[e];
                     map_load(r0 + 32);                     // in front of this call's data loads
+                }
+            }
+            if constexpr (sizeof(XT) == 2) {
+                if (roleB && !is_h) {                      // (uniform per wave)
+                    const XT* xb16 = reinterpret_cast<const XT*>(a.X) + bc;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[SET][e] = load4_nocheck<XT>(xb16 + pr[e] * (long long)ld, 0);
+                    return;
                 }
             }
 #pragma unroll
@@ -1072,8 +1095,8 @@ __global__ void k_reduce_parts(const float* __restrict__ part, float* __restrict
 //      also part_a[s][M] = column sums of a.  grid = (row ranges, 256-wide k-segments); the 4 waves
 //      stride the rows (b row read once for up to 4 classes), then merge through LDS.  Only the DENSE instance-logit
 //      gradient (g_classes: never requested by the reference's training loop) takes it. -------------
-template <int VEC>
-__global__ __launch_bounds__(256) void k_tn_small(const float* __restrict__ a, const float* __restrict__ bm,
+template <int VEC, typename XT = float>
+__global__ __launch_bounds__(256) void k_tn_small(const float* __restrict__ a, const XT* __restrict__ bm,
                                                   float* __restrict__ part, float* __restrict__ part_a,
                                                   long long N, int M, int Kc, int TNR, const int64_t* __restrict__ bmap) {
     __shared__ __attribute__((aligned(16))) float sacc[4][4][256];
@@ -1089,7 +1112,7 @@ __global__ __launch_bounds__(256) void k_tn_small(const float* __restrict__ a, c
         for (int j = 0; j < 4; ++j) { acc[j] = f32x4{0.f, 0.f, 0.f, 0.f}; asum[j] = 0.f; }
 #pragma unroll 4
         for (long long r = rbeg + wave; r < rend; r += 4) {
-            const f32x4 bv = load4<VEC, float>(bm + phys_row(bmap, r) * (long long)Kc, k, Kc);
+            const f32x4 bv = load4<VEC, XT>(bm + phys_row(bmap, r) * (long long)Kc, k, Kc);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float av = (m0 + j < M) ? a[r * M + m0 + j] : 0.f;
@@ -1232,11 +1255,12 @@ int launch_tile_kernel(KernelT kern, const ArgT& arg, int nw, bool dma, long lon
     return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 
-int tn_small(const float* a, const float* bm, long long N, int M, int Kc, float* part, float* part_a, float* out,
+template <typename XT>
+int tn_small(const float* a, const XT* bm, long long N, int M, int Kc, float* part, float* part_a, float* out,
              float* out_a, int splits, bool v4, hipStream_t st, const int64_t* bmap = nullptr) {
     const dim3 grid((unsigned)splits, (unsigned)((Kc + 255) / 256));
-    if (v4) hipLaunchKernelGGL(k_tn_small<4>, grid, dim3(256), 0, st, a, bm, part, part_a, N, M, Kc, tn_rows(N), bmap);
-    else hipLaunchKernelGGL(k_tn_small<1>, grid, dim3(256), 0, st, a, bm, part, part_a, N, M, Kc, tn_rows(N), bmap);
+    if (v4) hipLaunchKernelGGL((k_tn_small<4, XT>), grid, dim3(256), 0, st, a, bm, part, part_a, N, M, Kc, tn_rows(N), bmap);
+    else hipLaunchKernelGGL((k_tn_small<1, XT>), grid, dim3(256), 0, st, a, bm, part, part_a, N, M, Kc, tn_rows(N), bmap);
     if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
     const long long n = (long long)M * Kc;
     hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, out, splits, n);
@@ -1491,6 +1515,20 @@ int dsmil_agg_backward_bags(const float* feats, const float* vals, const int64_t
                             float* g_vals, const int64_t* rowmap, void* ws, size_t ws_bytes, void* stream, float* g_feats) {
     return agg_backward_bags_impl(feats, vals, offsets, n_bags, total_rows, max_rows, p, A, Bm, idx, g_classes, g_max, g_pred,
                                   g_A, g_B, g, g_vals, rowmap, ws, ws_bytes, stream, g_feats);
+}
+
+size_t dsmil_agg_backward_bags_bf16_workspace_bytes(int32_t n_bags, int64_t total_rows, int32_t K, int32_t Kv, int32_t C) {
+    return dsmil_agg_backward_bags_workspace_bytes(n_bags, total_rows, K, Kv, C);   // the fp32 call's layout
+}
+
+int dsmil_agg_backward_bags_bf16(const void* feats_bf16, const void* vals_bf16, const int64_t* offsets, int32_t n_bags,
+                                 int64_t total_rows, int64_t max_rows, const dsmil_agg_params* p, const float* A,
+                                 const float* Bm, const int64_t* idx, const float* g_classes, const float* g_max,
+                                 const float* g_pred, const float* g_A, const float* g_B, const dsmil_agg_grads* g,
+                                 float* g_vals, void* ws, size_t ws_bytes, void* stream) {
+    return agg_backward_bags_impl((const bf16_t*)feats_bf16, (const bf16_t*)vals_bf16, offsets, n_bags, total_rows, max_rows,
+                                  p, A, Bm, idx, g_classes, g_max, g_pred, g_A, g_B, g, g_vals, nullptr, ws, ws_bytes, stream,
+                                  nullptr);
 }
 
 int dsmil_agg_loss_head_bags(const float* classes, const int64_t* offsets, const float* pred, const int64_t* idx,

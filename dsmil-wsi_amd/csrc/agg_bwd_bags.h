@@ -17,6 +17,9 @@
 //   k_bags_head       fixed-order sums over the bags: g_fcc_w, g_fcc_b and the sparse FCLayer term (n_bags * C critical rows)
 //   k_bags_gvals      g_vals[n,:] = A[n,:] gB[bag(n)]
 //   k_bags_gx         (agg_gx.h) gx_tile with the row's own gB / idx / g_max in the tail
+// The kernels that read the rows (k_bags_ga, k_bags_qrow, the tile kernels, k_tn_split, k_tn_small, k_bags_head) take the
+// rows' storage type XT as a template parameter and reach them through ONE fetch (load4 and its forms, agg_common.h):
+// dsmil_agg_backward_bags_bf16 is the same launch sequence with XT = bf16_t, 2 bytes per element in HBM throughout.
 // Launch boundaries order the steps; no atomics, no hand-offs inside a launch, every sum in a fixed order: two runs give the
 // same bits, and a batch of ONE bag gives the bits of dsmil_agg_backward_rows (same arithmetic per element, same tile regime).
 //
@@ -71,21 +74,21 @@ __global__ __launch_bounds__(256) void k_bags_prep(
 }
 
 // gA[n,c] = <V[n,:], gB[bag(n),c,:]>: agg_fwd.hip k_fc with the row's own weights (b := 0)
-template <int VEC>
-__global__ __launch_bounds__(256) void k_bags_ga(const float* __restrict__ vals, const float* __restrict__ gB,
+template <int VEC, typename XT = float>
+__global__ __launch_bounds__(256) void k_bags_ga(const XT* __restrict__ vals, const float* __restrict__ gB,
                                                  const int* __restrict__ rowbag, float* __restrict__ gA, long long N, int Kv,
                                                  int C, const int64_t* __restrict__ rowmap) {
     const int lane = threadIdx.x & 63;
     const long long wid = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const long long nw = (long long)gridDim.x * 4;
     for (long long r = wid; r < N; r += nw) {
-        const float* x = vals + phys_row(rowmap, r) * Kv;
+        const XT* x = vals + phys_row(rowmap, r) * Kv;
         const float* w = gB + (long long)rowbag[r] * C * Kv;
         for (int c = 0; c < C; ++c) {
             float acc = 0.f;
             for (int k0 = 0; k0 < Kv; k0 += 256) {
                 const int k = k0 + lane * 4;
-                const f32x4 xv = load4<VEC>(x, k, Kv);
+                const f32x4 xv = load4<VEC, XT>(x, k, Kv);
                 const f32x4 wv = load4<VEC>(w + (long long)c * Kv, k, Kv);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) acc = fmaf(xv[e], wv[e], acc);
@@ -97,14 +100,14 @@ __global__ __launch_bounds__(256) void k_bags_ga(const float* __restrict__ vals,
 }
 
 // one workgroup per (bag, class)
-template <int VEC>
+template <int VEC, typename XT = float>
 __global__ __launch_bounds__(256) void k_bags_qrow(
-    const float* __restrict__ feats, const int64_t* __restrict__ offsets, const int64_t* __restrict__ idx,
+    const XT* __restrict__ feats, const int64_t* __restrict__ offsets, const int64_t* __restrict__ idx,
     const float* __restrict__ q0_w, const float* __restrict__ q0_b, const float* __restrict__ q2_w,
     const float* __restrict__ q2_b, float* __restrict__ qmax, int K, int C, int nonlinear, const int64_t* __restrict__ rowmap) {
     const long long bc = blockIdx.x;
     const long long row = (long long)offsets[bc / C] + (long long)idx[bc];
-    qrow_body<VEC>(feats + phys_row(rowmap, row) * (long long)K, q0_w, q0_b, q2_w, q2_b, qmax + bc * QD, K, nonlinear);
+    qrow_body<VEC, XT>(feats + phys_row(rowmap, row) * (long long)K, q0_w, q0_b, q2_w, q2_b, qmax + bc * QD, K, nonlinear);
 }
 
 // one workgroup per bag; its slice of gqp starts at the bag's first 32-row tile slot (k_bwd_rows: offsets[b] / 32 + b)
@@ -121,23 +124,25 @@ __global__ __launch_bounds__(1024) void k_bags_critical(const int64_t* __restric
 //   g_fc_w[c,k] (+)= sum_b g_max[b,c] x[offsets[b] + idx[b,c], k],  g_fc_b[c] (+)= sum_b g_max[b,c]      (g_max != null)
 //   g_fcc_w[o,c,k] = sum_b g_pred[b,o] B[b,c,k],                    g_fcc_b[o] = sum_b g_pred[b,o]
 struct BagsHeadArgs {
-    const float* feats; const int64_t* offsets; const int64_t* idx; const float* g_max; const int64_t* rowmap;
+    const void* feats; const int64_t* offsets; const int64_t* idx; const float* g_max; const int64_t* rowmap;   // feats: XT rows
     float* g_fc_w; float* g_fc_b;
     const float* g_pred; const float* Bm; float* g_fcc_w; float* g_fcc_b;
     int n_bags, K, Kv, C, accumulate;
 };
+template <typename XT = float>
 __global__ __launch_bounds__(256) void k_bags_head(BagsHeadArgs a) {
     const int C = a.C;
+    const XT* feats = reinterpret_cast<const XT*>(a.feats);
     const long long nf = a.g_max ? (long long)C * a.K + C : 0, nw = (long long)C * C * a.Kv;
     long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i < nf) {
         if (i < (long long)C * a.K) {
             const int c = (int)(i / a.K), k = (int)(i - (long long)c * a.K);
-            const float v = a.g_max[c] * a.feats[phys_row(a.rowmap, a.idx[c]) * (long long)a.K + k];   // bag 0: offsets[0] == 0
+            const float v = a.g_max[c] * load1<XT>(feats, phys_row(a.rowmap, a.idx[c]) * (long long)a.K + k);   // bag 0: offsets[0] == 0
             float g = a.accumulate ? a.g_fc_w[i] + v : v;
             for (int b = 1; b < a.n_bags; ++b) {
                 const long long row = (long long)a.offsets[b] + (long long)a.idx[(long long)b * C + c];
-                g += a.g_max[(long long)b * C + c] * a.feats[phys_row(a.rowmap, row) * (long long)a.K + k];
+                g += a.g_max[(long long)b * C + c] * load1<XT>(feats, phys_row(a.rowmap, row) * (long long)a.K + k);
             }
             a.g_fc_w[i] = g;
         } else {
@@ -249,7 +254,11 @@ BagsWs bags_layout(int n_bags, long long T, int K, int Kv, int C, int nonlinear)
     return w;
 }
 
-int agg_backward_bags_impl(const float* feats, const float* vals, const int64_t* offsets, int32_t n_bags, int64_t T,
+// XT = float: dsmil_agg_backward_bags.  XT = bf16_t: dsmil_agg_backward_bags_bf16 — the same launches on the same workspace
+// layout with the rows fetched as bf16 (exact MFMA operands: their plane cut is (x, 0, 0)); no row map, no g_feats, and the
+// register-staged / hidden-split tiles only (the LDS-DMA tile stages fp32 bytes as they are).
+template <typename XT>
+int agg_backward_bags_impl(const XT* feats, const XT* vals, const int64_t* offsets, int32_t n_bags, int64_t T,
                            int64_t max_rows, const dsmil_agg_params* p, const float* A, const float* Bm, const int64_t* idx,
                            const float* g_classes, const float* g_max, const float* g_pred, const float* g_A,
                            const float* g_B, const dsmil_agg_grads* g, float* g_vals, const int64_t* rowmap, void* ws,
@@ -265,6 +274,10 @@ int agg_backward_bags_impl(const float* feats, const float* vals, const int64_t*
     if (!vals) vals = feats;
     if (vals == feats && p->Kv != p->K) return DSMIL_E_INVALID;
     if (T > BAGS_MAX_ROWS) return DSMIL_E_UNSUPPORTED;
+    constexpr bool B16 = sizeof(XT) == 2;
+    if (B16 && (rowmap || g_feats)) return DSMIL_E_INVALID;
+    if (B16 && (p->K % 8 || p->Kv % 4)) return DSMIL_E_UNSUPPORTED;          // the bf16 forward's condition
+    if (B16 && (((uintptr_t)feats | (uintptr_t)vals) % 16)) return DSMIL_E_ALIGN;
     if (((uintptr_t)ws % 256) || ((uintptr_t)p->q0_b % 16) || (p->nonlinear && ((uintptr_t)p->q2_b % 16))) return DSMIL_E_ALIGN;
     const int K = p->K, Kv = p->Kv, C = p->C;
     const BagsWs L = bags_layout(n_bags, T, K, Kv, C, p->nonlinear);
@@ -300,12 +313,12 @@ int agg_backward_bags_impl(const float* feats, const float* vals, const int64_t*
     {
         long long blocks = ((long long)T + 3) / 4;
         if (blocks > 4096) blocks = 4096;
-        if (v4v) hipLaunchKernelGGL(k_bags_ga<4>, dim3((unsigned)blocks), dim3(256), 0, st, vals, gB, rowbag, gA, (long long)T, Kv, C, rowmap);
-        else hipLaunchKernelGGL(k_bags_ga<1>, dim3((unsigned)blocks), dim3(256), 0, st, vals, gB, rowbag, gA, (long long)T, Kv, C, rowmap);
+        if (v4v) hipLaunchKernelGGL((k_bags_ga<4, XT>), dim3((unsigned)blocks), dim3(256), 0, st, vals, gB, rowbag, gA, (long long)T, Kv, C, rowmap);
+        else hipLaunchKernelGGL((k_bags_ga<1, XT>), dim3((unsigned)blocks), dim3(256), 0, st, vals, gB, rowbag, gA, (long long)T, Kv, C, rowmap);
     }
     // 3. critical queries
-    if (w4) hipLaunchKernelGGL(k_bags_qrow<4>, dim3((unsigned)(C * n_bags)), dim3(256), 0, st, feats, offsets, idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, K, C, p->nonlinear, rowmap);
-    else hipLaunchKernelGGL(k_bags_qrow<1>, dim3((unsigned)(C * n_bags)), dim3(256), 0, st, feats, offsets, idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, K, C, p->nonlinear, rowmap);
+    if (w4) hipLaunchKernelGGL((k_bags_qrow<4, XT>), dim3((unsigned)(C * n_bags)), dim3(256), 0, st, feats, offsets, idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, K, C, p->nonlinear, rowmap);
+    else hipLaunchKernelGGL((k_bags_qrow<1, XT>), dim3((unsigned)(C * n_bags)), dim3(256), 0, st, feats, offsets, idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, K, C, p->nonlinear, rowmap);
     if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
     // 4. per-row part on MFMA, a 1-D grid of tile slots
     const int nw = (T / 128 >= 512) ? 4 : 1;
@@ -321,10 +334,10 @@ int agg_backward_bags_impl(const float* feats, const float* vals, const int64_t*
     };
     if (nw == 4) {
         const long long slots = T / 128 + n_bags;
-        rc = v4 ? launch_tile_kernel(k_bwd_rows<4, 4, true>, br, 4, true, T, st, slots)
-                : launch_tile_kernel(k_bwd_rows<1, 1, true>, br, 1, false, T, st, T / 32 + n_bags);
-    } else if (v4) rc = launch_hs(k_bwd_rows_hs<true>, br, T / HS_BM + n_bags);
-    else rc = launch_tile_kernel(k_bwd_rows<1, 1, true>, br, 1, false, T, st, T / 32 + n_bags);
+        rc = v4 ? launch_tile_kernel(k_bwd_rows<4, 4, true, XT>, br, 4, !B16, T, st, slots)
+                : launch_tile_kernel(k_bwd_rows<1, 1, true, XT>, br, 1, false, T, st, T / 32 + n_bags);
+    } else if (v4) rc = launch_hs(k_bwd_rows_hs<true, XT>, br, T / HS_BM + n_bags);
+    else rc = launch_tile_kernel(k_bwd_rows<1, 1, true, XT>, br, 1, false, T, st, T / 32 + n_bags);
     if (rc) return rc;
     // 5. gradient of the critical queries joins their rows, bag by bag
     hipLaunchKernelGGL(k_bags_critical, dim3((unsigned)n_bags), dim3(1024), 0, st, offsets, idx, gqp, Qb, gz2, gq, C, p->nonlinear);
@@ -351,7 +364,8 @@ int agg_backward_bags_impl(const float* feats, const float* vals, const int64_t*
 #endif
     {
         const dim3 gtn((unsigned)(tn.nslab * ((L.S + 7) / 8 * 8)));
-        if (v4 && rowmap) hipLaunchKernelGGL((k_tn_split<true, true>), gtn, dim3(256), 0, st, tn);
+        if constexpr (B16) hipLaunchKernelGGL((k_tn_split<true, false, XT>), gtn, dim3(256), 0, st, tn);   // (v4 holds, no map)
+        else if (v4 && rowmap) hipLaunchKernelGGL((k_tn_split<true, true>), gtn, dim3(256), 0, st, tn);
         else if (v4) hipLaunchKernelGGL((k_tn_split<true, false>), gtn, dim3(256), 0, st, tn);
         else if (rowmap) hipLaunchKernelGGL((k_tn_split<false, true>), gtn, dim3(256), 0, st, tn);
         else hipLaunchKernelGGL((k_tn_split<false, false>), gtn, dim3(256), 0, st, tn);
@@ -372,7 +386,7 @@ int agg_backward_bags_impl(const float* feats, const float* vals, const int64_t*
     BagsHeadArgs ha{feats, offsets, idx, g_max, rowmap, g->fc_w, g->fc_b, g_pred, Bm, g->fcc_w, g->fcc_b, n_bags, K, Kv, C,
                     g_classes ? 1 : 0};
     const long long nhead = (g_max ? (long long)C * K + C : 0) + (long long)C * C * Kv + C;
-    hipLaunchKernelGGL(k_bags_head, dim3((unsigned)((nhead + 255) / 256)), dim3(256), 0, st, ha);
+    hipLaunchKernelGGL(k_bags_head<XT>, dim3((unsigned)((nhead + 255) / 256)), dim3(256), 0, st, ha);
     if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
     // 9. gradient of the value rows
     if (g_vals) {

@@ -123,6 +123,8 @@ __device__ __forceinline__ float fast_tanh(float x) {
 #endif
 }
 
+// The row fetch of every aggregator kernel, parameterised on the storage type T of the rows (float, or bf16_t: one 8-byte
+// load of four elements, widened by a shift): load4 (range-checked), load4_nocheck, load4_clamped (staging), load1.
 // 4 consecutive elements at p[k..k+3] as floats, zero beyond klim.  VEC=4 needs rows aligned to
 // 4 elements (16 B for fp32, 8 B for bf16).
 template <int VEC, typename T = float>
@@ -168,14 +170,21 @@ __device__ __forceinline__ f32x4 load4_nocheck(const T* __restrict__ p, int k) {
 // Staging variant: never branches for VEC=4 — the address is clamped into the row (klim % 4 == 0,
 // klim >= 4) and the caller zeroes out-of-range k later (at LDS-write time), so a run of these
 // loads issues back to back and stays in flight under the MFMAs.
-template <int VEC>
-__device__ __forceinline__ f32x4 load4_clamped(const float* __restrict__ p, int k, int klim) {
+template <int VEC, typename T = float>
+__device__ __forceinline__ f32x4 load4_clamped(const T* __restrict__ p, int k, int klim) {
     if constexpr (VEC == 4) {
         const int kc = k < klim ? k : klim - 4;
-        return *(const DSMIL_GLOBAL f32x4*)(p + kc);
+        return load4_nocheck<T>(p, kc);
     } else {
-        return load4<1>(p, k, klim);
+        return load4<1, T>(p, k, klim);
     }
+}
+
+// one element of a stored row as a float
+template <typename T>
+__device__ __forceinline__ float load1(const T* __restrict__ p, long long i) {
+    if constexpr (sizeof(T) == 2) return bf2f(p[i]);
+    else return p[i];
 }
 
 // better (value, index): larger value wins, lowest index wins on exact ties

@@ -59,7 +59,9 @@ static_assert(4 * 1024 <= HS_STAGE, "the value-sum merge buffer aliases the stag
 // tile w (= Hw when !nonlinear); every remaining wave is past the last barrier and no DMA is in flight (the LDS is free).
 // Returns false for the cutter waves (they are done) and when the tile lies past the end of the bag (block-uniform): the
 // caller returns.  Rows 16-B aligned, K % 4 == 0.
-template <int NP>
+// XT: storage type of the feature rows.  bf16_t rows do not take the LDS-DMA ring (it stages fp32 bytes as they are): the
+// cutting lane fetches its own 8 elements of every chunk into a register ring, three chunks ahead.
+template <int NP, typename XT = float>
 __device__ __forceinline__ bool mlp_tile_hs(const AttendArgs& a, int bag, int tile, float* smem, f32x16 (&Hw)[HS_RG],
                                             f32x16 (&Qw)[HS_RG]) {
     static_assert(NP == 6 && HS_RG == 2, "12 MFMAs per step");
@@ -90,6 +92,45 @@ __device__ __forceinline__ bool mlp_tile_hs(const AttendArgs& a, int bag, int ti
         // no barrier between "landed" and "cut"; the one barrier per chunk publishes the planes.  (vmcnt is per wave and
         // vector memory returns in order: the compute waves' weight stream must not queue behind the HBM-sourced features.)
         const int j = wave - 4;
+        if constexpr (sizeof(XT) == 2) {
+            const int rr = lane & 15, o = lane >> 4;  // this lane cuts row 16j + rr, k-octet o: the fp32 form's roles
+            long long gr = row0 + 16 * j + rr;
+            if (gr >= Nb) gr = Nb - 1;                // rows past the bag end are masked by the caller
+            const XT* xr = reinterpret_cast<const XT*>(a.feats) + phys_row(a.rowmap, off0 + gr) * (long long)K + 8 * o;
+            f32x4 ring[4][2];                         // chunk c sits in slot c & 3
+            auto fetch = [&](auto slot, int c) {      // branch-free: past the end the last chunk is re-read
+                constexpr int R = decltype(slot)::value;
+                const int k = (c < nk1 ? c : nk1 - 1) * 32;
+                ring[R][0] = load4_clamped<4, XT>(xr, k, K - 8 * o);
+                ring[R][1] = load4_clamped<4, XT>(xr, k + 4, K - 8 * o);
+            };
+            auto cut = [&](auto slot, int c) {
+                constexpr int R = decltype(slot)::value;
+                const f32x4 x0 = ring[R][0], x1 = ring[R][1];
+                const float xv[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
+                S3Frag f[3];
+                split3(xv, f);
+                f32x4* dst = sPl + (c & 1) * HS_PL_SLOT + o * HS_BM + 16 * j + rr;
+#pragma unroll
+                for (int p = 0; p < 3; ++p) dst[p * 4 * HS_BM] = f[p].f;
+                fetch(std::integral_constant<int, (R + 3) & 3>{}, c + 3);   // into the slot of chunk c - 1
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();         // planes of chunk c are visible to the compute waves
+            };
+            fetch(std::integral_constant<int, 0>{}, 0);
+            fetch(std::integral_constant<int, 1>{}, 1);
+            fetch(std::integral_constant<int, 2>{}, 2);
+            for (int c = 0; c < nk1; c += 4) {
+                cut(std::integral_constant<int, 0>{}, c);
+                if (c + 1 >= nk1) break;
+                cut(std::integral_constant<int, 1>{}, c + 1);
+                if (c + 2 >= nk1) break;
+                cut(std::integral_constant<int, 2>{}, c + 2);
+                if (c + 3 >= nk1) break;
+                cut(std::integral_constant<int, 3>{}, c + 3);
+            }
+            return false;
+        }
         const float* feats = reinterpret_cast<const float*>(a.feats);
         // LDS-DMA writes lane-linear (lane -> row lane >> 3 of the piece, 16-B slot lane & 7): the slot is permuted on the
         // SOURCE side (slot c of row rr holds global slot c ^ (rr >> 1)) so that the cutting lanes — lane -> (row lane & 15,
@@ -209,6 +250,9 @@ __device__ __forceinline__ bool mlp_tile_hs(const AttendArgs& a, int bag, int ti
 #pragma unroll
         for (int k = 0; k < 12; ++k) {
             const int g = k & 1, q = P0 + (k >> 1);
+            if constexpr (!G2 && sizeof(XT) == 2) {
+                if (S3_PB(q) != 0) continue;   // bf16 rows: the row planes 1, 2 are identically zero — 6 MFMAs per step, not 12
+            }
             if constexpr (G2) Qw[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wr[RI][S3_PA(q)].v, xb[g][S3_PB(q)].v, Qw[g], 0, 0, 0);
             else Hw[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wr[RI][S3_PA(q)].v, xb[g][S3_PB(q)].v, Hw[g], 0, 0, 0);
         }

@@ -60,7 +60,9 @@ __device__ __forceinline__ void split3(const float (&x)[8], S3Frag (&o)[3]) {
 struct S3NoHook {
     __device__ __forceinline__ void operator()(const f32x16 (&)[4]) const {}
 };
-template <int NW, int VEC, int NP, typename OnH = S3NoHook>
+// XT: storage type of the feature rows (float, or bf16_t: widened as they are fetched, fp32 in LDS — the cut of a widened
+// bf16 value is (x, 0, 0), so the products are exact as they are for fp32 rows).
+template <int NW, int VEC, int NP, typename OnH = S3NoHook, typename XT = float>
 __device__ __forceinline__ bool mlp_tile_split(const AttendArgs& a, int bag, int tile, float* smem, f32x16 (&Q)[4],
                                                OnH on_h = OnH()) {
     static_assert(NP == 6 || NP == 9, "plane products");
@@ -83,12 +85,12 @@ __device__ __forceinline__ bool mlp_tile_split(const AttendArgs& a, int bag, int
     const int nk1 = (K + 31) / 32;  // feature chunks
     const int nks = 2 * nk1;        // 16-k steps of GEMM 1
     const int nst = nks + (a.nonlinear ? 8 : 0);
-    const float* feats = reinterpret_cast<const float*>(a.feats);
+    const XT* feats = reinterpret_cast<const XT*>(a.feats);
     const f32x4* wpk = reinterpret_cast<const f32x4*>(a.wpk);
     const int c4 = tid & 7;
 
     f32x4 wreg[WPT], xreg[XPT];
-    const float* xrow[XPT];
+    const XT* xrow[XPT];
 #pragma unroll
     for (int i = 0; i < XPT; ++i) {
         long long gr = row0 + ((tid + T * i) >> 3);
@@ -109,7 +111,7 @@ __device__ __forceinline__ bool mlp_tile_split(const AttendArgs& a, int bag, int
     auto load_x = [&](int c) {
         const int cx = c < nk1 ? c : nk1 - 1;
 #pragma unroll
-        for (int i = 0; i < XPT; ++i) xreg[i] = load4_clamped<VEC>(xrow[i], cx * 32 + c4 * 4, K);
+        for (int i = 0; i < XPT; ++i) xreg[i] = load4_clamped<VEC, XT>(xrow[i], cx * 32 + c4 * 4, K);
     };
     auto write_x = [&](int c) {
         float* dst = sX + (c & 1) * X_TILE + c4 * 4;
@@ -145,8 +147,12 @@ __device__ __forceinline__ bool mlp_tile_split(const AttendArgs& a, int bag, int
 #pragma unroll
             for (int p = 0; p < 3; ++p) wa[p].f = w[(t * 3 + p) * 64];
 #pragma unroll
-            for (int q = P0; q < 9; ++q)
+            for (int q = P0; q < 9; ++q) {
+                if constexpr (sizeof(XT) == 2) {
+                    if (S3_PB(q) != 0) continue;   // bf16 rows: the row planes 1, 2 are identically zero — 3 products, not 6
+                }
                 H[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[S3_PA(q)].v, xb[S3_PB(q)].v, H[t], 0, 0, 0);
+            }
         }
         write_w(s + 1);
         load_w(s + 2);

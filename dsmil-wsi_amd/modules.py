@@ -149,14 +149,19 @@ class BClassifier(nn.Module):
         whether or not they require a gradient (ops.value_proj: Linear + ReLU in one HIP launch; its parameter gradients in
         ops.value_proj_backward, the gradient of the rows in ops.value_proj_backward_rows).  An ACTIVE dropout (training
         mode, p > 0) is torch's own, applied to the rows first — the native projection then runs on the dropped rows; torch's
-        random stream is not reproduced inside a kernel.  bf16-stored rows (inference only) take the native projection of
-        the bf16 path (dsmil_value_forward_bf16: fp32 master weights are rounded inside, as ops.agg_forward does with the
-        aggregator's); with an ACTIVE dropout they keep the torch route (nn.Linear + ReLU)."""
+        random stream is not reproduced inside a kernel.  bf16-stored rows take the native projection of the bf16 path
+        (dsmil_value_forward_bf16: fp32 master weights are rounded inside, as ops.agg_forward does with the aggregator's),
+        which has no backward: under autograd a TRAINABLE value layer on bf16 rows raises (the aggregator trains on bf16
+        rows, the value layer does not — detaching it here would train without it and say nothing); a frozen one is a
+        constant.  With an ACTIVE dropout they keep the torch route (nn.Linear + ReLU)."""
         if not self.passing_v:
             return None
         drop, lin = self.v[0], self.v[1]
         active = drop.training and drop.p > 0
         if feats.dtype == torch.bfloat16 and not active:
+            if torch.is_grad_enabled() and (lin.weight.requires_grad or lin.bias.requires_grad):
+                raise NotImplementedError("passing_v with a trainable value layer on bf16-stored rows: the bf16 value "
+                                          "projection has no backward (freeze b_classifier.v or store the rows in fp32)")
             return ops.value_proj(feats.detach(), lin.weight.detach(), lin.bias.detach())
         if feats.dtype != torch.float32:
             return self.v(feats)
@@ -166,6 +171,7 @@ class BClassifier(nn.Module):
     def forward(self, feats, c):
         if not feats.is_cuda:
             return self._forward_cpu(feats, c)
+        MILNet._loss_dtype(feats)   # (bf16 rows that require a gradient are refused here, under grad mode)
         w = _wdict(None, None, **self._weights())
         pred, A, B = _AggFunction.apply(feats, c, self._values(feats), None, *w.values(), self.nonlinear)[1:4]
         return pred, A, B
@@ -194,13 +200,18 @@ class MILNet(nn.Module):
         return lin, _wdict(lin.weight, lin.bias, **self.b_classifier._weights(), detach=detach)
 
     def forward(self, x):
+        return self._forward(x)
+
+    def _forward(self, x, _f32_out=False):
         ic, bc = self.i_classifier, self.b_classifier
         if self._fused(x):
+            self._loss_dtype(x)   # (bf16 rows that require a gradient are refused here, under grad mode)
             # one fused native call: instance logits + aggregator (dsmil.py:70-74); with passing_v the native value
             # projection runs in front of it and its result goes in as `vals` (bf16 rows: the bf16 forms of both calls);
-            # rows that require a gradient get it from the native backward (k_bwd_gx, k_value_gx)
+            # rows that require a gradient get it from the native backward (k_bwd_gx, k_value_gx).
+            # _f32_out (bag_loss / batch_loss): on bf16 rows keep the call's fp32 outputs — the loss is formed from those
             _, w = self._lin_weights()
-            return _AggFunction.apply(x, None, bc._values(x), None, *w.values(), bc.nonlinear)[0:4]
+            return _AggFunction.apply(x, None, bc._values(x), None, *w.values(), bc.nonlinear, _f32_out)[0:4]
         feats, classes = ic(x)
         prediction_bag, A, B = bc(feats, classes)
         return classes, prediction_bag, A, B
@@ -234,13 +245,17 @@ class MILNet(nn.Module):
             ins, bag, _, _ = milnet(bag_feats);  mx = max(ins, 0)
             loss = 0.5 BCEWithLogitsLoss(bag, y) + 0.5 BCEWithLogitsLoss(mx, y)
         Returns (loss [], bag_prediction [1,C], max_prediction [C]).  CUDA fp32 bags with FCLayer + BClassifier
-        (v = Identity) whose rows need no gradient take the fused path (the fused loss call has no row-gradient output);
+        (v = Identity) whose rows need no gradient take the fused path (the fused loss call has no row-gradient output); so do
+        bf16-stored bags with K % 8 == 0 (the bf16 forward and dsmil_agg_backward_bags_bf16; a row map is ONE index_select
+        of the bf16 rows in front of the call; loss and predictions are the fp32 ones of the forward's fp32 logits);
         everything else — a passing_v model and rows that require a gradient included, whose forward and backward are
         native all the same (value projection + aggregator + the row-gradient kernels) — composes the same objective
         around ``self(x)``."""
         bc = self.b_classifier
-        if (self._fused(feats) and feats.dtype == torch.float32 and not bc.passing_v and not feats.requires_grad
+        if (self._fused(feats) and self._loss_dtype(feats) and not bc.passing_v and not feats.requires_grad
                 and self.i_classifier.fc[0].out_features <= 64):   # dsmil_agg_loss_head: one wave of classes; more take the torch expression
+            if feats.dtype == torch.bfloat16 and row_map is not None:
+                feats, row_map = feats.index_select(0, row_map), None
             if row_map is not None and row_map.numel():
                 # an out-of-range index would become an out-of-bounds device read in the row loads: checked once per
                 # bag on the device, surfaced with the step's only host sync (the loss .item() of train_tcga.py:74)
@@ -249,7 +264,7 @@ class MILNet(nn.Module):
             _, w = self._lin_weights()
             return _BagLossFunction.apply(feats, label, row_map, None, *w.values(), bc.nonlinear)
         x = feats if row_map is None else feats.index_select(0, row_map)
-        ins, bag, _, _ = self(x)
+        ins, bag, _, _ = self._forward(x, _f32_out=True)
         mx, _ = torch.max(ins, 0)
         y = label.view(1, -1).to(bag.dtype)
         loss = 0.5 * F.binary_cross_entropy_with_logits(bag.view(1, -1), y) + \
@@ -281,12 +296,21 @@ class MILNet(nn.Module):
             o += n
         return out
 
+    @staticmethod
+    def _loss_dtype(feats):
+        """Row storage the native training calls take: fp32, or bf16 with K % 8 == 0 (the bf16 forward's condition)."""
+        if feats.dtype == torch.bfloat16:
+            if torch.is_grad_enabled() and feats.requires_grad:
+                raise NotImplementedError("bf16-stored rows have no row gradient (store the rows in fp32 to differentiate them)")
+            return feats.shape[1] % 8 == 0
+        return feats.dtype == torch.float32
+
     # -- minibatches: several bags per call, differentiable ----------------------------------------
     def _batch_native(self, feats):
         """Whether a batch of these rows takes the native batched forward + backward (_AggFunction with lengths): fp32 rows
-        under the conditions of ``forward``'s fused call, minus what dsmil_agg_backward_bags would reject (query biases off
-        16-byte alignment)."""
-        if not (self._fused(feats) and feats.dtype == torch.float32):
+        (or bf16 rows with K % 8 == 0) under the conditions of ``forward``'s fused call, minus what dsmil_agg_backward_bags
+        would reject (query biases off 16-byte alignment)."""
+        if not (self._fused(feats) and self._loss_dtype(feats)):
             return False
         w = self.b_classifier._weights()
         return all(t is None or t.data_ptr() % 16 == 0 for t in (w["q0_b"], w["q2_b"]))
@@ -296,20 +320,24 @@ class MILNet(nn.Module):
 
         feats [sum(lengths), K]; bag b owns rows sum(lengths[:b]) .. + lengths[b].  Returns
         (classes [T,C], pred [n,C], A [T,C], B [n,C,Kv]): per bag what ``forward`` returns, laid end to end.  CUDA fp32 rows
+        (bf16-stored rows with K % 8 == 0 likewise: dsmil_agg_backward_bags_bf16, no row gradient, outputs in bf16)
         of MILNet(FCLayer, BClassifier): ONE native batched forward and, under autograd, ONE native batched backward
         (dsmil_agg_backward_bags) whose parameter gradients are summed over the bags; rows that require a gradient get it
         from the same call; with passing_v the value projection and its backward run once over the concatenated rows.
         Everything else (CPU tensors, other modules) runs the same mathematics bag by bag through ``forward``."""
+        return self._forward_batch(feats, lengths)
+
+    def _forward_batch(self, feats, lengths, _f32_out=False):
         lengths = [int(n) for n in lengths]
         if sum(lengths) != feats.shape[0] or any(n <= 0 for n in lengths):
             raise ValueError(f"bag lengths must be positive and sum to {feats.shape[0]} rows")
         if self._batch_native(feats):
             bc = self.b_classifier
             _, w = self._lin_weights()
-            return _AggFunction.apply(feats, None, bc._values(feats), tuple(lengths), *w.values(), bc.nonlinear)[0:4]
+            return _AggFunction.apply(feats, None, bc._values(feats), tuple(lengths), *w.values(), bc.nonlinear, _f32_out)[0:4]
         outs, o = [], 0
         for n in lengths:
-            classes, pred, A, B = self.forward(feats[o:o + n])
+            classes, pred, A, B = self._forward(feats[o:o + n], _f32_out)
             outs.append((classes, pred.view(1, -1), A, B.view(1, B.shape[-2], B.shape[-1])))
             o += n
         return tuple(torch.cat([t[i] for t in outs], dim=0) for i in range(4))
@@ -321,7 +349,8 @@ class MILNet(nn.Module):
         (every bag's dropout_patches index list with the bag's offset added, concatenated).  labels [n,C].
         Returns (loss [], pred [n,C], max_pred [n,C]) and, with per_bag, each bag's own loss [n] (detached) as a fourth value.
         CUDA fp32 rows that need no gradient, v = Identity, C <= 64: one native batched forward + batched loss head, and one
-        native batched backward with the sparse max-stream gradient.  Otherwise the same objective from torch ops around
+        native batched backward with the sparse max-stream gradient.  bf16-stored rows (K % 8 == 0) likewise, through the
+        bf16 forward and dsmil_agg_backward_bags_bf16; a row map is one index_select of the bf16 rows in front of the call.  Otherwise the same objective from torch ops around
         ``forward_batch``."""
         lengths = [int(n) for n in lengths]
         n = len(lengths)
@@ -329,13 +358,15 @@ class MILNet(nn.Module):
         bc = self.b_classifier
         if (self._batch_native(feats) and not bc.passing_v and not feats.requires_grad
                 and self.i_classifier.fc[0].out_features <= 64):
+            if feats.dtype == torch.bfloat16 and row_map is not None:
+                feats, row_map = feats.index_select(0, row_map), None
             if row_map is not None and row_map.numel():
                 torch._assert_async((row_map.min() >= 0) & (row_map.max() < feats.shape[0]), "row_map index out of range")
             _, w = self._lin_weights()
             loss, pred, mx, each = _BagLossFunction.apply(feats, labels, row_map, tuple(lengths), *w.values(), bc.nonlinear)
             return (loss, pred, mx, each) if per_bag else (loss, pred, mx)
         x = feats if row_map is None else feats.index_select(0, row_map)
-        ins, pred, _, _ = self.forward_batch(x, lengths)
+        ins, pred, _, _ = self._forward_batch(x, lengths, _f32_out=True)
         mx = torch.stack([t.max(0)[0] for t in torch.split(ins, lengths, dim=0)])
         y = labels.to(pred.dtype)
         each = 0.5 * F.binary_cross_entropy_with_logits(pred, y, reduction="none").mean(1) + \
@@ -391,12 +422,19 @@ class _ValueProjFunction(torch.autograd.Function):
         return gx, gw, gb
 
 
+def _param_grads(g, w):
+    """The eight parameter gradients of ops.agg_backward's dict in ops.W_KEYS order (None where the call made none), each in
+    its parameter's dtype: fp32 for fp32 masters, bf16 for a module after ``.bfloat16()``."""
+    return tuple(None if g.get(k) is None else g[k].to(w[k].dtype) for k in ops.W_KEYS)
+
+
 class _BagLossFunction(torch.autograd.Function):
     """Forward = dsmil_agg_forward_ex (row map) + dsmil_agg_loss_head; backward = dsmil_agg_backward_ex with the sparse
     max-stream gradient.  Replaces, per training step, the row gather, torch.max, two BCEWithLogitsLoss graphs and the
     dense [N,C] instance-logit gradient of train_tcga.py:64-72.  With ``lengths`` (a tuple) the same over a batch of bags
     stored back to back: the batched forward + dsmil_agg_loss_head_bags, loss = the mean of the bags' losses (each bag's own
-    loss is a fourth output), backward = dsmil_agg_backward_bags."""
+    loss is a fourth output), backward = dsmil_agg_backward_bags.  bf16-stored rows (no row map): the bf16 forward, the same
+    loss head on its fp32 logits, backward = dsmil_agg_backward_bags_bf16; gradients in the parameters' dtype."""
 
     @staticmethod
     def forward(ctx, feats, label, row_map, lengths, fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, nonlinear):
@@ -411,14 +449,16 @@ class _BagLossFunction(torch.autograd.Function):
             each, max_pred, g_pred, g_max = ops.agg_loss_head_bags(classes, lengths, pred, idx, label.detach())
             out = (each.mean(), pred, max_pred, each)
         ctx.nonlinear, ctx.lengths = nonlinear, lengths
-        ctx.save_for_backward(feats, row_map, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx, g_pred, g_max)
+        ctx.save_for_backward(feats, row_map, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx, g_pred, g_max, fc_b, fcc_b)
         ctx.mark_non_differentiable(*out[1:])
         return out
 
     @staticmethod
     def backward(ctx, g_loss, *_):
-        feats, row_map, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx, g_pred, g_max = ctx.saved_tensors
-        w = _wdict(fc_w, None, q0_w, q0_b, q2_w, q2_b, fcc_w, None)
+        feats, row_map, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx, g_pred, g_max, fc_b, fcc_b = ctx.saved_tensors
+        # (the biases are not read by the backward; with them the dict is the forward's: the same cached bf16 weight set)
+        w = _wdict(fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, detach=True)
+        g_loss = g_loss.float()
         # every parameter gradient is linear in (g_pred, g_max): the upstream scalar scales those two vectors (a batch: the
         # mean over the bags is a factor 1 / n on each bag's own)
         if ctx.lengths is None:
@@ -428,8 +468,7 @@ class _BagLossFunction(torch.autograd.Function):
             scale = g_loss / len(ctx.lengths)
             g = ops.agg_backward_bags(feats, ctx.lengths, w, A, B, idx, g_pred * scale, g_max=g_max * scale, row_map=row_map,
                                       nonlinear=ctx.nonlinear)
-        return (None, None, None, None, g["fc_w"], g["fc_b"], g["q0_w"], g["q0_b"], g.get("q2_w"), g.get("q2_b"),
-                g["fcc_w"], g["fcc_b"], None)
+        return (None, None, None, None, *_param_grads(g, w), None)
 
 
 class _AggFunction(torch.autograd.Function):
@@ -439,33 +478,35 @@ class _AggFunction(torch.autograd.Function):
     when asked for, comes from the same native call (dsmil_agg_backward_rows, k_bwd_gx).
     ``lengths`` None: ONE bag.  A tuple of lengths: a batch of bags stored back to back (fp32 rows, no ``c_in``) — the batched
     forward and, for the backward, dsmil_agg_backward_bags: every parameter gradient summed over the bags in one native call,
-    g_vals for a trainable v and the gradient of the input rows from the same call."""
+    g_vals for a trainable v and the gradient of the input rows from the same call.
+    bf16-stored rows: the bf16 forward, outputs cast to the rows' dtype (``f32_out``: left fp32, for the loss); the backward widens the incoming gradients to fp32
+    and is dsmil_agg_backward_bags_bf16 — the gradient of the reference function at the bf16 rows and the bf16-rounded
+    parameters with the forward's A, B, idx, straight-through for the roundings; fp32 masters get fp32 gradients, a module
+    after ``.bfloat16()`` gets them in bf16.  The rows themselves and caller-supplied ``vals`` get no gradient there."""
 
     @staticmethod
-    def forward(ctx, feats, c_in, vals, lengths, fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, nonlinear):
+    def forward(ctx, feats, c_in, vals, lengths, fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, nonlinear, f32_out=False):
         det = lambda t: t.detach() if t is not None else None
         w = _wdict(fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, detach=True)
         classes, pred, A, B, idx = ops.agg_forward(feats.detach(), [feats.shape[0]] if lengths is None else lengths, w,
                                                    classes_in=det(c_in), vals=det(vals), nonlinear=nonlinear)
-        if feats.dtype == torch.bfloat16:
-            # bf16-storage path (BASELINE config 2) is inference only; results keep the input dtype
-            ctx.bf16 = True
-            out = tuple(t.to(torch.bfloat16) for t in (classes, pred, A, B))
-            ctx.mark_non_differentiable(*out, idx)
-            return (*out, idx)
-        ctx.bf16 = False
+        ctx.bf16 = feats.dtype == torch.bfloat16
         ctx.nonlinear, ctx.lengths = nonlinear, lengths
         ctx.has_cin = c_in is not None
         ctx.has_vals = vals is not None
-        ctx.save_for_backward(feats, vals, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx)
+        ctx.save_for_backward(feats, vals, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx, fc_b, fcc_b)
         ctx.mark_non_differentiable(idx)
+        if ctx.bf16 and not f32_out:   # bf16-storage path (BASELINE config 2): results keep the input dtype
+            classes, pred, A, B = (t.to(torch.bfloat16) for t in (classes, pred, A, B))
         return classes, pred, A, B, idx
 
     @staticmethod
     def backward(ctx, g_cls, g_pred, g_A, g_B, _g_idx):
-        if ctx.bf16:
-            raise NotImplementedError("the bf16-storage aggregator path is inference only")
-        if ctx.lengths is not None or not ctx.needs_input_grad[0] or _AggFunction._native_accepts(ctx):
+        if ctx.bf16 and (ctx.needs_input_grad[0] or (ctx.has_vals and ctx.needs_input_grad[2])):
+            # (MILNet / BClassifier refuse these at the forward, under grad mode; a direct caller of the Function gets here)
+            raise NotImplementedError("bf16-stored rows: the parameters have a native backward, the rows and the value "
+                                      "layer do not")
+        if ctx.bf16 or ctx.lengths is not None or not ctx.needs_input_grad[0] or _AggFunction._native_accepts(ctx):
             return _AggFunction._backward_native(ctx, g_cls, g_pred, g_A, g_B)
         return _AggFunction._backward_dense(ctx, g_cls, g_pred, g_A, g_B)
 
@@ -480,11 +521,14 @@ class _AggFunction(torch.autograd.Function):
     def _backward_native(ctx, g_cls, g_pred, g_A, g_B):
         """dsmil_agg_backward (HIP): every parameter gradient, g_vals for a trainable v, and — when the input rows require
         one — their gradient (v = Identity: A gB included; caller's vals: the value function adds its own share)."""
-        feats, vals, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx = ctx.saved_tensors
+        feats, vals, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx, fc_b, fcc_b = ctx.saved_tensors
         C = fcc_w.shape[0]
         if g_pred is None:
             g_pred = torch.zeros((1 if ctx.lengths is None else len(ctx.lengths), C), device=feats.device)
-        w = _wdict(fc_w, None, q0_w, q0_b, q2_w, q2_b, fcc_w, None)
+        if ctx.bf16:   # the saved A, B are the forward's fp32 ones; the incoming gradients arrive in the outputs' dtype
+            g_cls, g_pred, g_A, g_B = (None if t is None else t.float() for t in (g_cls, g_pred, g_A, g_B))
+        # (the biases are not read by the backward; with them the dict is the forward's: the same cached bf16 weight set)
+        w = _wdict(fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, detach=True)
         want_x = ctx.needs_input_grad[0]
         # (vals sharing feats' memory IS v = Identity to the kernels: the rows' gradient then already holds A gB)
         same = ctx.has_vals and vals.data_ptr() == feats.data_ptr()
@@ -495,15 +539,14 @@ class _AggFunction(torch.autograd.Function):
             g = ops.agg_backward(feats, w, A, B, idx, g_pred, g_B=g_B[0] if g_B is not None else None, **kw)
         else:
             g = ops.agg_backward_bags(feats, ctx.lengths, w, A, B, idx, g_pred, g_B=g_B, **kw)
-        return (g.get("feats"), None, g.get("vals"), None, g.get("fc_w"), g.get("fc_b"), g["q0_w"], g["q0_b"],
-                g.get("q2_w"), g.get("q2_b"), g["fcc_w"], g["fcc_b"], None)
+        return (g.get("feats"), None, g.get("vals"), None, *_param_grads(g, w), None, None)
 
     @staticmethod
     def _backward_dense(ctx, g_cls, g_pred, g_A, g_B):
         """The fallback for what the native call rejects when the gradient of the INPUT rows is requested (_native_accepts:
         misaligned query biases): the same analytic gradient composed from dense GPU products.  No fp32 CUDA route of
         FCLayer + BClassifier with ordinary parameters reaches it."""
-        feats, vals, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx = ctx.saved_tensors
+        feats, vals, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx = ctx.saved_tensors[:11]
         x = feats
         V = vals if ctx.has_vals else feats
         idx = idx[0]
@@ -558,4 +601,4 @@ class _AggFunction(torch.autograd.Function):
         if ctx.has_vals and ctx.needs_input_grad[2]:
             g_vals = A.mm(gB)
         return (g_x, g_cin, g_vals, None, g_fc_w, g_fc_b, g_q0_w, g_q0_b, g_q2_w, g_q2_b,
-                g_fcc_w, g_fcc_b, None)
+                g_fcc_w, g_fcc_b, None, None)

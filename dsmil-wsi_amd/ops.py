@@ -594,14 +594,32 @@ def agg_loss_head(classes, pred, idx, label):
 def _agg_backward(lengths, offsets, feats, w, A, B, idx, g_pred, g_classes, g_A, g_B, vals, nonlinear, want_g_vals, g_max,
                   row_map, want_g_feats):
     """The body of agg_backward (``lengths`` None: ONE bag, dsmil_agg_backward_ex, or dsmil_agg_backward_rows for the input
-    rows' gradient) and of agg_backward_bags (a batch: dsmil_agg_backward_bags).  The entries launch different kernels."""
-    feats = _f32c(feats, "feats")
+    rows' gradient) and of agg_backward_bags (a batch: dsmil_agg_backward_bags).  The entries launch different kernels.
+    bf16-stored rows take dsmil_agg_backward_bags_bf16 (a lone bag as a batch of one) with the bf16-rounded weight set of
+    the forward (_bf16_params: the same cache entry): the gradient of what agg_forward computed on those rows, in fp32."""
+    bf16 = feats.dtype == torch.bfloat16
+    if bf16:
+        if row_map is not None:
+            raise ValueError("row_map is implemented for the fp32 path")
+        if want_g_feats:
+            raise ValueError("the gradient of the input rows is implemented for the fp32 path")
+        if not feats.is_cuda:
+            raise RuntimeError("feats must be a CUDA(HIP) tensor for the native path")
+        feats = feats if feats.is_contiguous() else feats.contiguous()
+        w = _bf16_params(w, nonlinear, feats.device)[0]
+        if lengths is None:
+            lengths = [feats.shape[0]]
+    else:
+        feats = _f32c(feats, "feats")
     dev = feats.device
     N, K = feats.shape
     row_map = _i64c(row_map, "row_map")
     if row_map is not None:
         N = int(row_map.numel())
-    vals = feats if vals is None else _f32c(vals, "vals")
+    if vals is None:
+        vals = feats
+    else:
+        vals = vals.to(torch.bfloat16).contiguous() if bf16 else _f32c(vals, "vals")
     Kv = vals.shape[1]
     p, keep, C = _agg_params(w, K, Kv, nonlinear)
     A = _f32c(A, "A"); B = _f32c(B, "B")
@@ -613,14 +631,14 @@ def _agg_backward(lengths, offsets, feats, w, A, B, idx, g_pred, g_classes, g_A,
         idx = idx.contiguous()
         nbytes = L.dsmil_agg_backward_workspace_bytes(N, K, Kv, C)
     else:
-        entry = "dsmil_agg_backward_bags"
+        entry = "dsmil_agg_backward_bags_bf16" if bf16 else "dsmil_agg_backward_bags"
         lengths = [int(n) for n in lengths]
         if sum(lengths) != N or any(n <= 0 for n in lengths):
             raise ValueError(f"bag lengths must be positive and sum to {N}")
         off = offsets if offsets is not None else offsets_tensor(lengths, dev)
         extent, per_bag = (_ptr(off), len(lengths), N, max(lengths)), (len(lengths), C)
         idx = _i64c(idx.reshape(per_bag), "idx")
-        nbytes = L.dsmil_agg_backward_bags_workspace_bytes(len(lengths), N, K, Kv, C)
+        nbytes = getattr(L, entry + "_workspace_bytes")(len(lengths), N, K, Kv, C)
     g_pred = _f32c(g_pred.reshape(per_bag), "g_pred")
     g_max = _f32c(g_max.reshape(per_bag), "g_max") if g_max is not None else None
     new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
@@ -633,10 +651,12 @@ def _agg_backward(lengths, offsets, feats, w, A, B, idx, g_pred, g_classes, g_A,
     g_vals = new(N, Kv) if want_g_vals else None
     g_feats = new(N, K) if want_g_feats else None
     ws = _workspace(dev, nbytes)
-    tail = () if entry == "dsmil_agg_backward_ex" else (_ptr(g_feats),)   # (the entry without the row-gradient argument)
+    # (the bf16 entry has neither a row map nor a row-gradient argument; dsmil_agg_backward_ex no row-gradient argument)
+    rmap = () if bf16 else (_ptr(row_map),)
+    tail = () if bf16 or entry == "dsmil_agg_backward_ex" else (_ptr(g_feats),)
     with torch.cuda.device(dev):
         rc = getattr(L, entry)(_ptr(feats), _ptr(vals), *extent, ctypes.byref(p), _ptr(A), _ptr(B), _ptr(idx), _ptr(g_classes),
-                               _ptr(g_max), _ptr(g_pred), _ptr(g_A), _ptr(g_B), ctypes.byref(g), _ptr(g_vals), _ptr(row_map),
+                               _ptr(g_max), _ptr(g_pred), _ptr(g_A), _ptr(g_B), ctypes.byref(g), _ptr(g_vals), *rmap,
                                _ptr(ws), ws.numel(), _stream(dev), *tail)
     _native.check(rc, entry)
     del keep
@@ -650,7 +670,8 @@ def _agg_backward(lengths, offsets, feats, w, A, B, idx, g_pred, g_classes, g_A,
 def agg_backward(feats, w, A, B, idx, g_pred, g_classes=None, g_A=None, g_B=None, vals=None, nonlinear=True,
                  want_g_vals=False, g_max=None, row_map=None, want_g_feats=False):
     """dsmil_agg_backward: parameter gradients of FCLayer + BClassifier for ONE bag (what autograd
-    derives for train_tcga.py:67-72).  feats [N,K] fp32 CUDA, w as in agg_forward, A [N,C], B [1,C,Kv],
+    derives for train_tcga.py:67-72).  feats [N,K] fp32 CUDA (or bf16: dsmil_agg_backward_bags_bf16 on a batch of one, the
+    gradient at the bf16 rows and the bf16-rounded weights, fp32 results; no row_map, no want_g_feats), w as in agg_forward, A [N,C], B [1,C,Kv],
     idx [1,C] = the forward's outputs; g_* = upstream gradients (None = zero).  Returns a dict with the
     gradient of every key of ``w`` (fc_* only when g_classes or g_max is given, q2_* only when nonlinear) and
     ``vals`` (when want_g_vals).  ``g_max`` [C]: the sparse gradient of max_n classes[n,:] (the training objective's
@@ -688,7 +709,8 @@ def agg_backward_bags(feats, lengths, w, A, B, idx, g_pred, g_classes=None, g_A=
     training: one summed gradient over the bags).  ``lengths``: the bags' LOGICAL row counts; A [total,C], B [n,C,Kv],
     idx [n,C] = the batched forward's outputs; g_pred [n,C], g_max [n,C] or None, g_classes / g_A [total,C], g_B [n,C,Kv]
     (None = zero).  Returns the dict of ``agg_backward``: every parameter gradient summed over the bags, ``vals`` /
-    ``feats`` (on request) laid end to end in logical row order."""
+    ``feats`` (on request) laid end to end in logical row order.  bf16 ``feats``: dsmil_agg_backward_bags_bf16 (see
+    ``agg_backward``)."""
     return _agg_backward(lengths, offsets, feats, w, A, B, idx, g_pred, g_classes, g_A, g_B, vals, nonlinear, want_g_vals,
                          g_max, row_map, want_g_feats)
 

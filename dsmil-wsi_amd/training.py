@@ -61,15 +61,20 @@ def generate_pt_files(args, df, temp_train_dir="temp_train"):
 class BagCache:
     """path -> (feats [N,K] contiguous, label [1,C]) resident on the training device.  The reference re-reads the
     stacked [N, K+C] tensor from disk every iteration and slices it (train_tcga.py:62-64: a strided view that the
-    following gather densifies); here the split happens once per bag, when it is first loaded."""
+    following gather densifies); here the split happens once per bag, when it is first loaded.
+    ``dtype`` (not in the reference): the storage type of the resident rows — torch.float32, or torch.bfloat16 for half the
+    bytes per bag; MILNet.bag_loss / batch_loss train on the bf16 rows as they are (the labels stay fp32)."""
 
-    def __init__(self, device, feats_size=None):
+    def __init__(self, device, feats_size=None, dtype=torch.float32):
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"BagCache stores fp32 or bf16 rows, not {dtype}")
         self.device = device
         self.feats_size = feats_size
+        self.dtype = dtype
         self.store = {}
 
     def _split(self, stacked, feats_size):
-        return (stacked[:, :feats_size].contiguous().float(), stacked[0, feats_size:].unsqueeze(0).float())
+        return (stacked[:, :feats_size].contiguous().to(self.dtype), stacked[0, feats_size:].unsqueeze(0).float())
 
     def get(self, item, feats_size=None):
         feats_size = feats_size or self.feats_size
@@ -193,6 +198,7 @@ class FusedTrainStep:
             return None
 
     def accepts(self, bag_feats):
+        # (fp32 bags only: bf16-stored bags take the generic loop around bag_loss / batch_loss)
         return bag_feats.is_cuda and bag_feats.dtype == torch.float32 and bag_feats.dim() == 2 and bag_feats.is_contiguous()
 
     def __call__(self, bag_feats, bag_label, row_map=None):
@@ -517,7 +523,7 @@ def run_eval_scheme(args, mil, device, bags_path=None):
     save_path = os.path.join("weights", datetime.date.today().strftime("%Y%m%d"))
     os.makedirs(save_path, exist_ok=True)
     run = len(glob.glob(os.path.join(save_path, "*.pth")))
-    cache = BagCache(device)
+    cache = BagCache(device, dtype=torch.bfloat16 if getattr(args, "feats_dtype", "fp32") == "bf16" else torch.float32)
     fold_results = []
     if args.eval_scheme == "5-fold-cv":
         kf = KFold(n_splits=5, shuffle=True, random_state=42)

@@ -311,6 +311,31 @@ int dsmil_agg_loss_head_bags(const float* classes, const int64_t* offsets, const
                              const float* labels, int32_t n_bags, int32_t C, float* loss, float* max_pred,
                              float* g_pred, float* g_max, void* stream);
 
+/* ---- the batched aggregator backward on bf16-STORED rows (training on a bf16 feature cache) -----------------------------
+ * Replaces what autograd derives for `loss.backward()` in train_tcga.py:60-73 when the bag's rows are stored in bfloat16
+ * (the rows dsmil_agg_forward_bf16 reads; the reference has no such storage: it would widen the bag first).  The contract of
+ * dsmil_agg_backward_bags with two omissions — no row_map and no g_feats, like the bf16 forward; a lone bag is a batch of
+ * one (offsets = {0, N}), so there is no one-bag entry:
+ *   feats_bf16 [total_rows, K], vals_bf16 [total_rows, Kv] or NULL (= feats): raw bfloat16, rows 16-B aligned
+ *   *p         fp32 parameters.  The gradient is the analytic gradient of dsmil.py:46-62 (+ the fused FCLayer) at x := the
+ *              bf16 rows and W := *p, with the forward's own A, B, idx as inputs (csrc/agg_bwd.hip, header) — exact for
+ *              whatever is handed in; to differentiate dsmil_agg_forward_bf16 hand in the bf16-ROUNDED weights it used
+ *              (straight-through for its roundings).  A bf16 value is an exact bf16 MFMA operand (plane cut (x, 0, 0)):
+ *              no arithmetic is lost against the fp32 call on a widened copy, and no such copy is ever written.
+ *   g, g_vals  fp32, as in dsmil_agg_backward_bags
+ * Requires K % 8 == 0 and Kv % 4 == 0 (dsmil_agg_forward_bf16's condition; else DSMIL_E_UNSUPPORTED).  Checks run in the
+ * order DSMIL_E_INVALID, total_rows > 2^30 and the shape condition (DSMIL_E_UNSUPPORTED), DSMIL_E_ALIGN (rows, workspace,
+ * biases), DSMIL_E_WORKSPACE — all before any launch.  Same launch sequence, same workspace layout and size as the fp32
+ * call; the rows stay 2 bytes per element for the six kernels that read them (the register-staged and hidden-split tiles:
+ * the LDS-DMA tile stages fp32 bytes).  No allocation, no sync, no atomics, fixed-order sums: two runs give the same bits.
+ * Added without a change of DSMIL_ABI_VERSION (it stays 6): detected by SYMBOL. */
+size_t dsmil_agg_backward_bags_bf16_workspace_bytes(int32_t n_bags, int64_t total_rows, int32_t K, int32_t Kv, int32_t C);
+int dsmil_agg_backward_bags_bf16(const void* feats_bf16, const void* vals_bf16, const int64_t* offsets, int32_t n_bags,
+                                 int64_t total_rows, int64_t max_rows, const dsmil_agg_params* p, const float* A,
+                                 const float* B, const int64_t* idx, const float* g_classes, const float* g_max,
+                                 const float* g_pred, const float* g_A, const float* g_B, const dsmil_agg_grads* g,
+                                 float* g_vals, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- the value stream of BClassifier(passing_v=True) (ABI 6) ---------------------------------------------------------
  * Replaces `V = self.v(feats)` of dsmil.py:48 with self.v = Sequential(Dropout, Linear(K, K), ReLU) (dsmil.py:35-39; the
  * dropout is the caller's: it hands in the rows it wants projected):  V[n, j] = max(0, sum_k feats[n, k] v_w[j, k] + v_b[j]),

@@ -30,6 +30,10 @@ def build_parser():
     p.add_argument("--bags_per_step", default=1, type=int,
                    help="Bags per optimiser step [1]; NOT a flag of the reference's train_tcga.py, which steps once per bag: "
                         "with N > 1 the mean loss of N bags is stepped on at once (minibatch training, a different schedule)")
+    p.add_argument("--feats_dtype", default="fp32", choices=("fp32", "bf16"),
+                   help="Storage type of the bags resident on the device [fp32]; NOT a flag of the reference's train_tcga.py: "
+                        "bf16 keeps every bag at 2 bytes per element and trains on those rows (native bf16 forward and "
+                        "backward, fp32 parameters and gradients; the one-call fused step is fp32-only)")
     return p
 
 
