@@ -151,6 +151,21 @@ SIGNATURES = {
                                                ctypes.c_int32, ctypes.c_int32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
                                                c_f32p, ctypes.c_int32, c_f32p, c_f32p, ctypes.c_void_p,
                                                ctypes.c_size_t, ctypes.c_int32, ctypes.c_void_p]),
+    # the stages of the 16-bit activation trunk alone (for tests)
+    "dsmil_trunk16_positions": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "dsmil_trunk16_layout": (ctypes.c_int, [c_f32p, ctypes.c_void_p] + [ctypes.c_int32] * 6 + [ctypes.c_void_p]),
+    "dsmil_trunk16_conv_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "dsmil_trunk16_conv": (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_void_p] + [ctypes.c_int32] * 9 +
+                           [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "dsmil_trunk16_norm_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32]),
+    "dsmil_trunk16_norm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int32] * 6 +
+                           [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "dsmil_trunk16_pool": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_f32p] + [ctypes.c_int32] * 5 +
+                           [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "dsmil_trunk16_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32] * 4),
+    "dsmil_trunk16_forward": (ctypes.c_int, [ctypes.c_int32, c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                             ctypes.POINTER(ctypes.c_void_p), c_f32p, ctypes.c_int32, ctypes.c_void_p,
+                                             ctypes.c_size_t, ctypes.c_void_p]),
     "dsmil_tile_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
                                         ctypes.c_void_p]),
     "dsmil_jpeg_plan_bytes": (ctypes.c_size_t, [ctypes.c_int32]),

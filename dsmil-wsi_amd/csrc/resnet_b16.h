@@ -600,6 +600,8 @@ __global__ __launch_bounds__(256) void k_pool_b16(const unsigned short* __restri
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
+// (run_conv / run_stats / run_apply / pack_all / trunk are also what the dsmil_trunk16_* entries of resnet_fwd.hip call to run ONE
+// stage for tests/test_trunk16_gpu.py: a change of a launch condition here is a change of the shapes that test must cover)
 inline bool v2_conv(const ConvSpec& s) { return s.ks == 3 && s.stride == 1 && s.pad == 1 && s.cin % 32 == 0 && s.cout % 64 == 0; }
 inline bool g2_conv(const ConvSpec& s) { return !v2_conv(s) && s.cin % 64 == 0 && s.cout % 128 == 0; }
 inline int chunk_for(const ConvSpec& s) { return v2_conv(s) ? 16 : 64; }

@@ -2703,6 +2703,160 @@ int dsmil_resnet_forward_ex(int32_t depth, const void* x, int32_t x_is_u8_nhwc, 
                                fc_w, fc_b, C, feats, classes, ws, ws_bytes, stream);
 }
 
+// ---- the stages of the 16-bit activation trunk (csrc/resnet_b16.h) ALONE, FOR TESTS (tests/test_trunk16_gpu.py compares each
+// with fp64 at a derived bar; include/dsmil_hip.h states the contracts).  Each entry is the trunk's own host call — b16::run_conv,
+// run_stats, run_apply, pack_all, trunk, and the launches of k_b16_pad / k_b16_borders / k_pack_b16 / k_pool_b16 as trunk_t and
+// pack_all make them — behind argument checks that all run before the first launch: no kernel, geometry or plan of its own.
+// kind as Form::trunk: 1 = bf16, 2 = fp16.
+namespace {
+inline bool t16_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline bool t16_al256(const void* p) { return ((uintptr_t)p & 255) == 0; }
+inline bool t16_kind(int kind) { return kind == 1 || kind == 2; }
+inline bool t16_pos(int B, int H, int W, int C) { return B >= 1 && H >= 1 && W >= 1 && C >= 1; }
+// a map every kernel of the trunk can index: eight channels per 16-B piece, images on gridDim.y, element offsets inside an int
+// (k_conv_b16g's staging offsets)
+inline bool t16_map(int B, int H, int W, int C) {
+    return C % 8 == 0 && B <= 65535 && H <= 32767 && W <= 32767 && b16::npos(B, H, W) * C < 0x7fffffffLL;
+}
+// k_stats_b16 / k_apply_b16: 256 threads = (C / 8 pieces) x (256 / (C / 8) pixel lanes), partial sums in 2 x 2048 floats of LDS
+inline bool t16_norm_c(int C) { return C % 8 == 0 && C <= 2048 && 256 % (C / 8) == 0; }
+inline size_t t16_part_bytes(int B, int C) { return al256((size_t)B * 8 * C * 2 * sizeof(float)); }
+// the conv forms of a BasicBlock trunk, and run_conv's own window limits (so that a refusal comes BEFORE the weights are packed)
+inline int t16_conv_check(const ConvSpec& s, int Wo) {
+    const bool form = (s.ks == 3 && s.pad == 1 && (s.stride == 1 || s.stride == 2)) || (s.ks == 1 && s.pad == 0 && s.stride == 2);
+    if (!form) return DSMIL_E_UNSUPPORTED;
+    if (b16::v2_conv(s)) {
+        const int Wp = Wo + 1;
+        if (s.cout % 128 == 0) return (256 + 2 * Wp + 2) * 2 > b16::B16W_NIA * 256 ? DSMIL_E_UNSUPPORTED : DSMIL_OK;
+        if (s.cin == 64 && s.cout == 64 && (256 + 2 * Wp + 2) * 8 <= b16::B16N_NIA * 256) return DSMIL_OK;
+        return (512 + 2 * Wp + 2) * 2 > b16::B16W_NIA * 256 ? DSMIL_E_UNSUPPORTED : DSMIL_OK;
+    }
+    return b16::g2_conv(s) && s.stride == 2 ? DSMIL_OK : DSMIL_E_UNSUPPORTED;
+}
+}  // namespace
+
+size_t dsmil_trunk16_positions(int32_t B, int32_t H, int32_t W) {
+    return B >= 1 && H >= 1 && W >= 1 && B <= 65535 && H <= 32767 && W <= 32767 ? (size_t)b16::npos(B, H, W) : 0;
+}
+
+int dsmil_trunk16_layout(const float* x_nhwc, void* out16, int32_t B, int32_t H, int32_t W, int32_t C, int32_t kind,
+                         int32_t borders_only, void* stream) {
+    if (!out16 || (!borders_only && !x_nhwc) || !t16_pos(B, H, W, C) || !t16_kind(kind)) return DSMIL_E_INVALID;
+    if (!t16_map(B, H, W, C)) return DSMIL_E_UNSUPPORTED;
+    if (!t16_al16(out16) || !t16_al16(x_nhwc)) return DSMIL_E_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned short* out = (unsigned short*)out16;
+    const int oc = C / 8;
+    if (borders_only) {
+        if (hipMemsetAsync(out, 0x3C, (size_t)b16::npos(B, H, W) * C * 2, st) != hipSuccess) return DSMIL_E_LAUNCH;
+        const long long total = ((long long)B * (W + 1 + H) + W + 1) * oc;
+        hipLaunchKernelGGL(b16::k_b16_borders, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out, B, H, W, C);
+    } else {
+        const long long total = b16::npos(B, H, W) * oc;
+        long long blocks = (total + 255) / 256;
+        if (blocks > 16384) blocks = 16384;
+        if (kind == 2) hipLaunchKernelGGL(b16::k_b16_pad<true>, dim3((unsigned)blocks), dim3(256), 0, st, x_nhwc, out, B, H, W, C);
+        else hipLaunchKernelGGL(b16::k_b16_pad<false>, dim3((unsigned)blocks), dim3(256), 0, st, x_nhwc, out, B, H, W, C);
+    }
+    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
+}
+
+size_t dsmil_trunk16_conv_workspace_bytes(int32_t Cin, int32_t Cout, int32_t ks) {
+    if (Cin < 1 || Cout < 1 || (ks != 1 && ks != 3)) return 0;
+    return al256((size_t)Cout * Cin * ks * ks * 2);
+}
+
+int dsmil_trunk16_conv(const void* in16, const float* w_oihw, void* out16, int32_t B, int32_t Hi, int32_t Wi, int32_t Cin,
+                       int32_t Cout, int32_t ks, int32_t stride, int32_t pad, int32_t kind, void* ws, size_t ws_bytes, void* stream) {
+    if (!in16 || !w_oihw || !out16 || !ws || in16 == out16 || !t16_pos(B, Hi, Wi, Cin) || Cout < 1 || ks < 1 || stride < 1 || pad < 0 ||
+        !t16_kind(kind)) return DSMIL_E_INVALID;
+    const ConvSpec s{Cout, Cin, ks, stride, pad};
+    if (Hi > 32767 || Wi > 32767 || Hi + 2 * pad < ks || Wi + 2 * pad < ks) return DSMIL_E_UNSUPPORTED;
+    const int Ho = (Hi + 2 * pad - ks) / stride + 1, Wo = (Wi + 2 * pad - ks) / stride + 1;
+    if (!t16_map(B, Hi, Wi, Cin) || !t16_map(B, Ho, Wo, Cout)) return DSMIL_E_UNSUPPORTED;
+    if (const int rc = t16_conv_check(s, Wo)) return rc;
+    if (!t16_al16(in16) || !t16_al16(out16) || ((uintptr_t)w_oihw & 3) || !t16_al256(ws)) return DSMIL_E_ALIGN;
+    if (ws_bytes < dsmil_trunk16_conv_workspace_bytes(Cin, Cout, ks)) return DSMIL_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned short* wpk = (unsigned short*)ws;
+    if (kind == 2) hipLaunchKernelGGL(b16::k_pack_b16<true>, dim3(512), dim3(256), 0, st, w_oihw, wpk, s.cout, s.cin, s.ks, b16::chunk_for(s));
+    else hipLaunchKernelGGL(b16::k_pack_b16<false>, dim3(512), dim3(256), 0, st, w_oihw, wpk, s.cout, s.cin, s.ks, b16::chunk_for(s));
+    if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    int ho, wo;
+    return kind == 2 ? b16::run_conv<true>(st, (const unsigned short*)in16, wpk, (unsigned short*)out16, B, Hi, Wi, s, &ho, &wo)
+                     : b16::run_conv<false>(st, (const unsigned short*)in16, wpk, (unsigned short*)out16, B, Hi, Wi, s, &ho, &wo);
+}
+
+size_t dsmil_trunk16_norm_workspace_bytes(int32_t B, int32_t C) { return B >= 1 && C >= 1 ? t16_part_bytes(B, C) : 0; }
+
+int dsmil_trunk16_norm(const void* x16, const void* idn16, void* y16, int32_t B, int32_t H, int32_t W, int32_t C, int32_t relu,
+                       int32_t kind, void* ws, size_t ws_bytes, void* stream) {
+    if (!x16 || !y16 || !ws || !t16_pos(B, H, W, C) || !t16_kind(kind) || (relu != 0 && relu != 1)) return DSMIL_E_INVALID;
+    if (!t16_map(B, H, W, C) || !t16_norm_c(C)) return DSMIL_E_UNSUPPORTED;
+    if (idn16 && !relu) return DSMIL_E_UNSUPPORTED;          // (the trunk has no residual form without the ReLU)
+    if (!t16_al16(x16) || !t16_al16(idn16) || !t16_al16(y16) || !t16_al256(ws)) return DSMIL_E_ALIGN;
+    if (ws_bytes < t16_part_bytes(B, C)) return DSMIL_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned short* x = (const unsigned short*)x16;
+    const unsigned short* idn = (const unsigned short*)idn16;
+    unsigned short* y = (unsigned short*)y16;
+    float* part = (float*)ws;
+    if (const int rc = kind == 2 ? b16::run_stats<true>(st, x, part, B, H, W, C) : b16::run_stats<false>(st, x, part, B, H, W, C)) return rc;
+    return kind == 2 ? b16::run_apply<true>(st, x, idn, y, part, B, H, W, C, relu != 0)
+                     : b16::run_apply<false>(st, x, idn, y, part, B, H, W, C, relu != 0);
+}
+
+int dsmil_trunk16_pool(const void* x16, const void* idn16, float* feats, int32_t B, int32_t H, int32_t W, int32_t C, int32_t kind,
+                       void* ws, size_t ws_bytes, void* stream) {
+    if (!x16 || !idn16 || !feats || !ws || !t16_pos(B, H, W, C) || !t16_kind(kind)) return DSMIL_E_INVALID;
+    if (!t16_map(B, H, W, C) || !t16_norm_c(C)) return DSMIL_E_UNSUPPORTED;
+    if (!t16_al16(x16) || !t16_al16(idn16) || ((uintptr_t)feats & 3) || !t16_al256(ws)) return DSMIL_E_ALIGN;
+    if (ws_bytes < t16_part_bytes(B, C)) return DSMIL_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned short* x = (const unsigned short*)x16;
+    const unsigned short* idn = (const unsigned short*)idn16;
+    float* part = (float*)ws;
+    if (const int rc = kind == 2 ? b16::run_stats<true>(st, x, part, B, H, W, C) : b16::run_stats<false>(st, x, part, B, H, W, C)) return rc;
+    const int S = b16::stat_chunks(H * W);
+    if (kind == 2) hipLaunchKernelGGL(b16::k_pool_b16<true>, dim3((unsigned)((C + 255) / 256), (unsigned)B), dim3(256), 0, st, x, idn, part, feats, H, W, C, S);
+    else hipLaunchKernelGGL(b16::k_pool_b16<false>, dim3((unsigned)((C + 255) / 256), (unsigned)B), dim3(256), 0, st, x, idn, part, feats, H, W, C, S);
+    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
+}
+
+size_t dsmil_trunk16_workspace_bytes(int32_t depth, int32_t B, int32_t Hp, int32_t Wp) {
+    const Arch* A = arch_of(depth);
+    if (!A || !b16::arch_ok(*A) || B < 1 || Hp < 1 || Wp < 1 || !t16_map(B, Hp, Wp, 64)) return 0;
+    return al256(b16::packed_bytes(*A)) + b16::scratch_bytes(B, Hp, Wp);
+}
+
+int dsmil_trunk16_forward(int32_t depth, const float* x_nhwc, int32_t B, int32_t Hp, int32_t Wp, const float* const* conv_w,
+                          float* feats, int32_t kind, void* ws, size_t ws_bytes, void* stream) {
+    if (!x_nhwc || !conv_w || !feats || !ws || B < 1 || Hp < 1 || Wp < 1 || !t16_kind(kind)) return DSMIL_E_INVALID;
+    const Arch* A = arch_of(depth);
+    if (!A || !b16::arch_ok(*A)) return DSMIL_E_UNSUPPORTED;
+    for (int i = 1; i < A->nconv; ++i)
+        if (!conv_w[i]) return DSMIL_E_INVALID;                 // (conv_w[0], the stem's, is not read)
+    if (!t16_map(B, Hp, Wp, 64)) return DSMIL_E_UNSUPPORTED;
+    // every conv's form and window, and every layer's map inside an activation buffer sized for the first (act_bytes): the
+    // product path has both from its 64-pixel minimum patch
+    for (int l = 1, ci = 1, H = Hp, W = Wp; l <= 4; ++l)
+        for (int b = 0; b < A->nblk[l - 1]; ++b) {               // (the walk of b16::trunk_t)
+            const int nc = l > 1 && b == 0 ? 3 : 2;              // conv1, conv2 and — first block of layers 2..4 — downsample.0
+            const ConvSpec& s1 = A->specs[ci];
+            const int Ho = (H + 2 * s1.pad - s1.ks) / s1.stride + 1, Wo = (W + 2 * s1.pad - s1.ks) / s1.stride + 1;
+            for (int k = 0; k < nc; ++k)
+                if (const int rc = t16_conv_check(A->specs[ci + k], Wo)) return rc;
+            if ((size_t)b16::npos(B, Ho, Wo) * s1.cout * 2 > b16::act_bytes(B, Hp, Wp)) return DSMIL_E_UNSUPPORTED;
+            ci += nc; H = Ho; W = Wo;
+        }
+    if (!t16_al16(x_nhwc) || ((uintptr_t)feats & 3) || !t16_al256(ws)) return DSMIL_E_ALIGN;
+    if (ws_bytes < dsmil_trunk16_workspace_bytes(depth, B, Hp, Wp)) return DSMIL_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned short* wpk = (unsigned short*)ws;
+    if (const int rc = b16::pack_all(*A, conv_w, wpk, st, kind)) return rc;
+    return b16::trunk(st, *A, x_nhwc, wpk, (char*)ws + al256(b16::packed_bytes(*A)), B, Hp, Wp, feats, kind);
+}
+
 int dsmil_resnet_forward(int32_t depth, const void* x, int32_t x_is_u8_nhwc, int32_t B, int32_t H, int32_t W,
                          const float* conv1_w, const float* packed, const float* bn_mean, const float* bn_rstd,
                          const float* fc_w, const float* fc_b, int32_t C, float* feats, float* classes, void* ws,

@@ -958,6 +958,122 @@ def resnet18in_forward(x, convs, fc_w=None, fc_b=None, bn_norms=None, precision=
 
 
 # ---------------------------------------------------------------------------------------------
+# the stages of the 16-bit activation trunk ALONE (csrc/resnet_b16.h behind dsmil_trunk16_*): FOR TESTS — no product path
+# calls these.  16-bit maps are int16 tensors [positions(B,H,W), C] holding the raw bf16 / fp16 bits in the shared-border
+# layout (include/dsmil_hip.h); uint16 tensors are taken as well.  A shape the kernels do not take raises NotImplementedError
+# (DSMIL_E_UNSUPPORTED), every other refusal RuntimeError; nothing is launched in either case.
+# ---------------------------------------------------------------------------------------------
+TRUNK16_KINDS = {"bf16": 1, "fp16": 2}
+
+
+def _t16_check(rc, what):
+    if rc == _native.DSMIL_E_UNSUPPORTED:
+        raise NotImplementedError(f"{what}: shape outside what the 16-bit trunk's kernels implement")
+    _native.check(rc, what)
+
+
+def _t16_buf(t, name):
+    if not t.is_cuda or t.dtype not in (torch.int16, torch.uint16) or not t.is_contiguous():
+        raise RuntimeError(f"{name} must be a contiguous int16 / uint16 CUDA(HIP) tensor")
+    return t
+
+
+def _t16_scratch(dev, nbytes):
+    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+
+
+def trunk16_positions(B, H, W):
+    """Positions of a [B,H,W] map in the shared-border layout: B (H+1) (W+1) + (W+1)."""
+    return int(_native.lib().dsmil_trunk16_positions(B, H, W))
+
+
+def trunk16_layout(x_nhwc, kind, borders_only=False):
+    """k_b16_pad: fp32 NHWC [B,H,W,C] -> the 16-bit shared-border buffer; ``borders_only``: a buffer of bytes 0x3C of that
+    shape with only k_b16_borders run on it (x supplies the shape and the device)."""
+    x = _f32c(x_nhwc, "x_nhwc")
+    B, H, W, C = x.shape
+    out = torch.empty((trunk16_positions(B, H, W), C), dtype=torch.int16, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = _native.lib().dsmil_trunk16_layout(_ptr(x), _ptr(out), B, H, W, C, TRUNK16_KINDS[kind], 1 if borders_only else 0,
+                                                _stream(x.device))
+    _t16_check(rc, "dsmil_trunk16_layout")
+    return out
+
+
+def trunk16_conv(buf, w, B, Hi, Wi, stride, pad, kind):
+    """k_pack_b16 + b16::run_conv: buf [positions(B,Hi,Wi), Cin], w fp32 OIHW -> (out [positions(B,Ho,Wo), Cout], Ho, Wo)."""
+    buf, w = _t16_buf(buf, "buf"), _f32c(w, "w")
+    Cout, Cin, ks, _ = w.shape
+    if tuple(buf.shape) != (trunk16_positions(B, Hi, Wi), Cin):
+        raise ValueError(f"buf {tuple(buf.shape)} is not a [{B},{Hi},{Wi},{Cin}] map in the shared-border layout")
+    Ho, Wo = (Hi + 2 * pad - ks) // stride + 1, (Wi + 2 * pad - ks) // stride + 1
+    L = _native.lib()
+    ws = _t16_scratch(buf.device, L.dsmil_trunk16_conv_workspace_bytes(Cin, Cout, ks))
+    out = torch.empty((max(trunk16_positions(B, Ho, Wo), 1), Cout), dtype=torch.int16, device=buf.device)
+    with torch.cuda.device(buf.device):
+        rc = L.dsmil_trunk16_conv(_ptr(buf), _ptr(w), _ptr(out), B, Hi, Wi, Cin, Cout, ks, stride, pad, TRUNK16_KINDS[kind],
+                                  _ptr(ws), ws.numel(), _stream(buf.device))
+    _t16_check(rc, "dsmil_trunk16_conv")
+    return out, Ho, Wo
+
+
+def trunk16_norm(buf, B, H, W, kind, idn=None, relu=True, out=None):
+    """run_stats + run_apply: [relu]((x - mean) rstd [+ idn]) per (image, channel).  ``out``: the buffer to write (``buf``
+    itself for the trunk's in-place form); default a new one whose closing row — which the kernel does not write — is zero."""
+    buf = _t16_buf(buf, "buf")
+    C = buf.shape[1]
+    if tuple(buf.shape) != (trunk16_positions(B, H, W), C):
+        raise ValueError(f"buf {tuple(buf.shape)} is not a [{B},{H},{W},{C}] map in the shared-border layout")
+    for t, name in ((idn, "idn"), (out, "out")):
+        if t is not None and (_t16_buf(t, name).shape != buf.shape):
+            raise ValueError(f"{name} must have buf's shape")
+    y = torch.zeros_like(buf) if out is None else out
+    L = _native.lib()
+    ws = _t16_scratch(buf.device, L.dsmil_trunk16_norm_workspace_bytes(B, C))
+    with torch.cuda.device(buf.device):
+        rc = L.dsmil_trunk16_norm(_ptr(buf), _ptr(idn), _ptr(y), B, H, W, C, 1 if relu else 0, TRUNK16_KINDS[kind], _ptr(ws),
+                                  ws.numel(), _stream(buf.device))
+    _t16_check(rc, "dsmil_trunk16_norm")
+    return y
+
+
+def trunk16_pool(buf, idn, B, H, W, kind):
+    """run_stats + k_pool_b16: fp32 [B,C] = mean over pixels of relu((x - mean) rstd + idn)."""
+    buf, idn = _t16_buf(buf, "buf"), _t16_buf(idn, "idn")
+    C = buf.shape[1]
+    if tuple(buf.shape) != (trunk16_positions(B, H, W), C) or idn.shape != buf.shape:
+        raise ValueError(f"buf / idn are not [{B},{H},{W},{C}] maps in the shared-border layout")
+    L = _native.lib()
+    ws = _t16_scratch(buf.device, L.dsmil_trunk16_norm_workspace_bytes(B, C))
+    feats = torch.empty((B, C), dtype=torch.float32, device=buf.device)
+    with torch.cuda.device(buf.device):
+        rc = L.dsmil_trunk16_pool(_ptr(buf), _ptr(idn), _ptr(feats), B, H, W, C, TRUNK16_KINDS[kind], _ptr(ws), ws.numel(),
+                                  _stream(buf.device))
+    _t16_check(rc, "dsmil_trunk16_pool")
+    return feats
+
+
+def trunk16_forward(x_nhwc, convs, kind):
+    """pack_all + b16::trunk: fp32 NHWC [B,Hp,Wp,64] (what the stem hands over) and the trunk's conv weights in state_dict
+    order (the stem's first: it is not read) -> fp32 features [B,512]."""
+    x = _f32c(x_nhwc, "x_nhwc")
+    B, Hp, Wp, C = x.shape
+    depth = resnet_depth_of(convs)
+    if C != 64 or depth not in (18, 34):
+        raise ValueError("the 16-bit trunk takes a 64-channel map and the conv weights of a ResNet-18 / 34")
+    L = _native.lib()
+    keep = [_f32c(w.detach(), "conv weight") for w in convs]
+    arr = (ctypes.c_void_p * len(keep))(*[t.data_ptr() for t in keep])
+    ws = _t16_scratch(x.device, L.dsmil_trunk16_workspace_bytes(depth, B, Hp, Wp))
+    feats = torch.empty((B, L.dsmil_resnet_feature_dim(depth)), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = L.dsmil_trunk16_forward(depth, _ptr(x), B, Hp, Wp, arr, _ptr(feats), TRUNK16_KINDS[kind], _ptr(ws), ws.numel(),
+                                     _stream(x.device))
+    _t16_check(rc, "dsmil_trunk16_forward")
+    return feats
+
+
+# ---------------------------------------------------------------------------------------------
 # background filters of the tilers (deepzoom_tiler.py:56-61, test_crop_single.py:17-24)
 # ---------------------------------------------------------------------------------------------
 def tile_stats(tiles):

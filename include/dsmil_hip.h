@@ -534,6 +534,53 @@ int dsmil_resnet_forward_ex(int32_t depth, const void* x, int32_t x_is_u8_nhwc, 
                             const float* fc_w, const float* fc_b, int32_t C, float* feats, float* classes, void* ws,
                             size_t ws_bytes, int32_t precision, void* stream);
 
+/* ---- the stages of the 16-bit activation trunk ALONE — FOR TESTS (tests/test_trunk16_gpu.py; no reference counterpart: the
+ * reference embeds in fp32, compute_feats.py:70-76).  The trunk of precision 2 / 3 (csrc/resnet_b16.h) is otherwise reachable
+ * only end to end, where sixteen rounded conv + norm layers allow no tight bar; these entries run ONE stage of it on buffers the
+ * caller controls, through the trunk's own host calls and launches (same kernels, same launch geometry), so that each kernel can be
+ * compared with fp64 at a bar derived from its arithmetic.  No product path calls them.
+ *   kind     1 = bf16, 2 = fp16 (the element type of precision 2 / 3)
+ *   layout   a [B,H,W,C] map is stored as 16-bit NHWC with SHARED zero borders: image n owns rows n (H+1) .. n (H+1) + H of a flat
+ *            [rows][W+1][C] array; row 0 of every image and column W of every row are zero, and one more zero row closes the last
+ *            image: dsmil_trunk16_positions(B,H,W) = B (H+1) (W+1) + (W+1) positions of C elements.  16-bit buffers are raw uint16,
+ *            16-byte aligned; every workspace is 256-byte aligned.
+ *   dsmil_trunk16_layout   borders_only = 0: x_nhwc (fp32 [B,H,W,C]) -> out16 (k_b16_pad: rounds to nearest even, writes the zeros).
+ *                          borders_only = 1: fills out16 with bytes 0x3C (finite, non-zero in both kinds), then k_b16_borders
+ *                          alone: exactly the border positions become zero (x_nhwc is not read, may be NULL).
+ *   dsmil_trunk16_conv     k_pack_b16 (fp32 OIHW weights -> fragment order, rounded to nearest even, into ws) + b16::run_conv:
+ *                          in16 [positions(B,Hi,Wi), Cin] -> out16 [positions(B,Ho,Wo), Cout], Ho = (Hi + 2 pad - ks) / stride + 1;
+ *                          border positions and the closing row are written as zeros.  Forms: 3x3 / stride 1 / pad 1 (Cin % 32 == 0,
+ *                          Cout % 64 == 0, maps up to ~126 pixels wide at 64 -> 64 and Cout % 128 != 0, ~254 at Cout % 128 == 0),
+ *                          3x3 / stride 2 / pad 1 and 1x1 / stride 2 / pad 0 (Cin % 64 == 0, Cout % 128 == 0).
+ *   dsmil_trunk16_norm     run_stats + run_apply: y = [relu]((x - mean) rstd [+ idn]) per (image, channel), biased variance,
+ *                          eps 1e-5, f32 statistics; idn16 may be NULL; idn16 with relu = 0 is no form of the trunk
+ *                          (DSMIL_E_UNSUPPORTED); y16 may be x16.  Writes the B (H+1) (W+1) positions of the images (borders
+ *                          as zeros), NOT the closing row.  C / 8 must divide 256, C <= 2048.
+ *   dsmil_trunk16_pool     run_stats + k_pool_b16: feats[B,C] (fp32) = mean over pixels of relu((x - mean) rstd + idn); workspace
+ *                          as for dsmil_trunk16_norm (dsmil_trunk16_norm_workspace_bytes: the statistics partials).
+ *   dsmil_trunk16_forward  pack_all + b16::trunk on x_nhwc = fp32 [B,Hp,Wp,64] (what the stem hands over); conv_w: the
+ *                          dsmil_resnet_num_convs(depth) device pointers of dsmil_resnet_pack (entry 0, the stem's, is not read);
+ *                          depth 18 or 34; feats [B,512].
+ * Every check runs BEFORE the first launch, in the order DSMIL_E_INVALID (null pointers, non-positive sizes, kind),
+ * DSMIL_E_UNSUPPORTED (C % 8, the channel multiples and window limits above, maps of 2^31 elements or more), DSMIL_E_ALIGN,
+ * DSMIL_E_WORKSPACE; the *_workspace_bytes queries answer 0 for arguments the entry refuses.
+ * Added without a change of DSMIL_ABI_VERSION (it stays 6, no existing signature moved): a caller finds them by symbol. */
+size_t dsmil_trunk16_positions(int32_t B, int32_t H, int32_t W);
+int dsmil_trunk16_layout(const float* x_nhwc, void* out16, int32_t B, int32_t H, int32_t W, int32_t C, int32_t kind,
+                         int32_t borders_only, void* stream);
+size_t dsmil_trunk16_conv_workspace_bytes(int32_t Cin, int32_t Cout, int32_t ks);
+int dsmil_trunk16_conv(const void* in16, const float* w_oihw, void* out16, int32_t B, int32_t Hi, int32_t Wi, int32_t Cin,
+                       int32_t Cout, int32_t ks, int32_t stride, int32_t pad, int32_t kind, void* ws, size_t ws_bytes,
+                       void* stream);
+size_t dsmil_trunk16_norm_workspace_bytes(int32_t B, int32_t C);
+int dsmil_trunk16_norm(const void* x16, const void* idn16, void* y16, int32_t B, int32_t H, int32_t W, int32_t C, int32_t relu,
+                       int32_t kind, void* ws, size_t ws_bytes, void* stream);
+int dsmil_trunk16_pool(const void* x16, const void* idn16, float* feats, int32_t B, int32_t H, int32_t W, int32_t C,
+                       int32_t kind, void* ws, size_t ws_bytes, void* stream);
+size_t dsmil_trunk16_workspace_bytes(int32_t depth, int32_t B, int32_t Hp, int32_t Wp);
+int dsmil_trunk16_forward(int32_t depth, const float* x_nhwc, int32_t B, int32_t Hp, int32_t Wp, const float* const* conv_w,
+                          float* feats, int32_t kind, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- background filters of the reference's tilers on decoded tiles -------------------------
  * tiles_nhwc: device uint8 [B,H,W,3] (W <= 1024).  out: device uint64 [B,4] = per tile
  *   {sum over band 0, band 1, band 2 of PIL's ImageFilter.FIND_EDGES image, sum of img_as_ubyte(rgb2hsv(img)[...,1])}.
