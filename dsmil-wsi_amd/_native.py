@@ -166,6 +166,14 @@ SIGNATURES = {
     "dsmil_trunk16_forward": (ctypes.c_int, [ctypes.c_int32, c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                              ctypes.POINTER(ctypes.c_void_p), c_f32p, ctypes.c_int32, ctypes.c_void_p,
                                              ctypes.c_size_t, ctypes.c_void_p]),
+    # the stages of the fp32-class trunk alone (for tests)
+    "dsmil_trunk32_conv_plan": (ctypes.c_int, [ctypes.c_int32] * 10 + [ctypes.POINTER(ctypes.c_int32)]),
+    "dsmil_trunk32_conv_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32] * 9),
+    "dsmil_trunk32_conv": (ctypes.c_int, [c_f32p] * 9 + [ctypes.c_int32] * 9 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "dsmil_trunk32_stem_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32] * 3),
+    "dsmil_trunk32_stem": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32] + [c_f32p] * 6 + [ctypes.c_int32] * 4 +
+                           [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "dsmil_trunk32_tail": (ctypes.c_int, [ctypes.c_int32] + [c_f32p] * 7 + [ctypes.c_int32] * 4 + [ctypes.c_void_p]),
     "dsmil_tile_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
                                         ctypes.c_void_p]),
     "dsmil_jpeg_plan_bytes": (ctypes.c_size_t, [ctypes.c_int32]),

@@ -2499,25 +2499,63 @@ bool launch_stem(const StemPlan& p, bool u8, hipStream_t st, const void* x, cons
     });
 }
 
+// the pack kernels a plan calls for: the stem's weight image, and one conv's OIHW weights -> `out` in the layout its kernel reads
+int pack_stem(const float* conv1_w, unsigned short* wimg, const Form& f, hipStream_t st) {
+    hipLaunchKernelGGL(k_pack_stem_s6, dim3(46), dim3(256), 0, st, conv1_w, wimg, f.conv_np);
+    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
+}
+int pack_conv(const ConvPlan& p, const ConvSpec& s, const float* w, float* out, hipStream_t st) {
+    const long long total = (long long)s.cout * s.cin * (p.wino ? 1 : s.ks * s.ks);
+    const unsigned blocks = (unsigned)std::min<long long>((total + 255) / 256, 4096);
+    if (!p.np) { if (!pack_f32(p, s, blocks, st, w, out)) return DSMIL_E_UNSUPPORTED; }
+    else if (p.wino) hipLaunchKernelGGL(k_pack_wino_s3, dim3(blocks), dim3(256), 0, st, w, (unsigned short*)out, s.cout, s.cin, p.tiled ? 1 : 0, p.np);
+    else hipLaunchKernelGGL(k_pack_conv_s6, dim3(blocks), dim3(256), 0, st, w, (unsigned short*)out, s.cout, s.cin, s.ks * s.ks, p.np);
+    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
+}
+
 int pack_impl(const Arch& A, const float* const* conv_w, float* packed, const Form& f, hipStream_t st) {
     const Expt& e = expt();
     const PackOffsets po = pack_offsets(A, f, e);
     if (!conv_w[0]) return DSMIL_E_INVALID;
-    hipLaunchKernelGGL(k_pack_stem_s6, dim3(46), dim3(256), 0, st, conv_w[0], (unsigned short*)(packed + po.off[A.nconv]), f.conv_np);
-    if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    if (const int rc = pack_stem(conv_w[0], (unsigned short*)(packed + po.off[A.nconv]), f, st)) return rc;
     for (int i = 1; i < A.nconv; ++i) {
         if (!conv_w[i]) return DSMIL_E_INVALID;
-        const ConvSpec& s = A.specs[i];
-        const ConvPlan p = plan_conv(s, 0, 0, 0, false, f, e);
-        const long long total = (long long)s.cout * s.cin * (p.wino ? 1 : s.ks * s.ks);
-        const unsigned blocks = (unsigned)std::min<long long>((total + 255) / 256, 4096);
-        float* out = packed + po.off[i];
-        if (!p.np) { if (!pack_f32(p, s, blocks, st, conv_w[i], out)) return DSMIL_E_UNSUPPORTED; }
-        else if (p.wino) hipLaunchKernelGGL(k_pack_wino_s3, dim3(blocks), dim3(256), 0, st, conv_w[i], (unsigned short*)out, s.cout, s.cin, p.tiled ? 1 : 0, p.np);
-        else hipLaunchKernelGGL(k_pack_conv_s6, dim3(blocks), dim3(256), 0, st, conv_w[i], (unsigned short*)out, s.cout, s.cin, s.ks * s.ks, p.np);
-        if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+        if (const int rc = pack_conv(plan_conv(A.specs[i], 0, 0, 0, false, f, e), A.specs[i], conv_w[i], packed + po.off[i], st)) return rc;
     }
     return DSMIL_OK;
+}
+
+// the stem behind launch_stem: its statistics (the frozen ones, or the finalize of its partials), then the fused pool's fix-up +
+// norm or the unfused norm + ReLU + max-pool, into `pooled`.  b16out: k_pool_fix_norm writes the 16-bit trunk's input instead
+int finish_stem(hipStream_t st, const StemPlan& sp, const float* bn_m, const float* bn_r, const float* part, float* y0, float* pooled,
+                float* mean, float* rstd, int B, const Dims& d, unsigned short* b16out, int b16_is_f16) {
+    if (bn_m) { const int rcf = fill_stats(st, bn_m, bn_r, mean, rstd, B, 64); if (rcf) return rcf; }
+    else hipLaunchKernelGGL(k_in_finalize_stem, dim3((unsigned)B), dim3(64 * FS_G), 0, st, part, mean, rstd, B, sp.nparts);
+    const long long total = (long long)B * d.Hp * d.Wp * 16;
+    long long blocks = (total + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    if (sp.fuse) hipLaunchKernelGGL(k_pool_fix_norm, dim3((unsigned)blocks), dim3(256), 0, st, pooled, y0, mean, rstd,
+                                    B, d.Hp, d.Wp, d.W1, sp.ty, b16out, b16_is_f16);
+    else hipLaunchKernelGGL(k_norm_relu_maxpool, dim3((unsigned)blocks), dim3(256), 0, st, y0, mean, rstd,
+                            pooled, B, d.H1, d.W1, d.Hp, d.Wp, 64);
+    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
+}
+
+// the elementwise pass that closes a block: relu(IN(yout) + identity | IN(yd)) over npix = B * HW pixels of C channels, or — the
+// last block — the same averaged over the pixels into the feature row.  k_norm_add_relu keeps one 4-channel group per thread and
+// grid-strides past 8192 workgroups.
+void launch_tail(hipStream_t st, bool last, bool down, const float* yout, const float* m, const float* r, const float* idn,
+                 const float* md, const float* rd, float* out, int B, int HW, int C) {
+    if (last) {
+        hipLaunchKernelGGL(k_norm_add_relu_pool, dim3((unsigned)((B * C + 255) / 256)), dim3(256), 0, st, yout, m, r, idn, out, B, HW, C);
+        return;
+    }
+    const long long npix = (long long)B * HW;
+    const int c4n = C / 4, tpb = 256 / (c4n < 256 ? c4n : 256);
+    long long nb = (npix + tpb - 1) / tpb;
+    if (nb > 8192) nb = 8192;
+    if (down) hipLaunchKernelGGL(k_norm_add_relu<true>, dim3((unsigned)nb), dim3(256), 0, st, yout, m, r, idn, md, rd, out, npix, HW, C);
+    else hipLaunchKernelGGL(k_norm_add_relu<false>, dim3((unsigned)nb), dim3(256), 0, st, yout, m, r, idn, nullptr, nullptr, out, npix, HW, C);
 }
 
 // One forward of a ResNet-18 / 34 / 50 / 101 trunk (InstanceNorm, or frozen BatchNorm when bn_m / bn_r are given) in `form`
@@ -2558,19 +2596,12 @@ int resnet_forward_impl(int depth, const Form& form, const void* x_nchw, bool u8
     if (!launch_stem(sp, u8, st, x_nchw, conv1_w, (const unsigned short*)(packed + po.off[A.nconv]), y0, buf[0], part, B, H, W, d))
         return DSMIL_E_UNSUPPORTED;
     if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
-    if (bn_m) { const int rcf = fill_stats(st, bn_m, bn_r, mean[0], rstd[0], B, 64); if (rcf) return rcf; }
-    else hipLaunchKernelGGL(k_in_finalize_stem, dim3((unsigned)B), dim3(64 * FS_G), 0, st, part, mean[0], rstd[0], B, sp.nparts);
-    const long long total = (long long)B * d.Hp * d.Wp * 16;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
     // the bf16-activation trunk takes the stem's output as bf16 in its own layout, behind the halo rows of the raw-map region
     const size_t b16_halo_bytes = al256((size_t)B * sp.ty * d.W1 * 64 * sizeof(float));
     const bool b16_direct = form.trunk && sp.fuse && b16_halo_bytes + b16::scratch_bytes(B, d.Hp, d.Wp) <= L.buf[0] - L.y0;
-    if (sp.fuse) hipLaunchKernelGGL(k_pool_fix_norm, dim3((unsigned)blocks), dim3(256), 0, st, buf[0], y0, mean[0], rstd[0],
-                                    B, d.Hp, d.Wp, d.W1, sp.ty, b16_direct ? (unsigned short*)(w8 + L.y0 + b16_halo_bytes) : (unsigned short*)nullptr, form.trunk == 2 ? 1 : 0);
-    else hipLaunchKernelGGL(k_norm_relu_maxpool, dim3((unsigned)blocks), dim3(256), 0, st, y0, mean[0], rstd[0],
-                            buf[0], B, d.H1, d.W1, d.Hp, d.Wp, 64);
-    if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    if (const int rc = finish_stem(st, sp, bn_m, bn_r, part, y0, buf[0], mean[0], rstd[0], B, d,
+                                   b16_direct ? (unsigned short*)(w8 + L.y0 + b16_halo_bytes) : (unsigned short*)nullptr, form.trunk == 2 ? 1 : 0))
+        return rc;
     if (form.trunk) {
         // the bf16-activation trunk: its four activation buffers and statistics partials take the raw-map region (the
         // stem's pooled output sits in buf[0]; the halo rows in y0 are dead behind k_pool_fix_norm); its weight image sits
@@ -2622,17 +2653,7 @@ int resnet_forward_impl(int depth, const Form& form, const void* x_nchw, bool u8
                 yout = y2; sout = 2; Cc = A.specs[ci].cout;
                 ci += down ? 3 : 2;
             }
-            const long long npix = (long long)B * Ho * Wo;
-            if (last) {
-                hipLaunchKernelGGL(k_norm_add_relu_pool, dim3((unsigned)((B * Cc + 255) / 256)), dim3(256), 0, st, yout,
-                                   mean[sout], rstd[sout], cur, feats, B, Ho * Wo, Cc);
-            } else {
-                const int c4n = Cc / 4, tpb = 256 / (c4n < 256 ? c4n : 256);
-                long long nb = (npix + tpb - 1) / tpb;
-                if (nb > 8192) nb = 8192;
-                if (down) hipLaunchKernelGGL(k_norm_add_relu<true>, dim3((unsigned)nb), dim3(256), 0, st, yout, mean[sout], rstd[sout], yd, mean[3], rstd[3], nxt, npix, Ho * Wo, Cc);
-                else hipLaunchKernelGGL(k_norm_add_relu<false>, dim3((unsigned)nb), dim3(256), 0, st, yout, mean[sout], rstd[sout], cur, nullptr, nullptr, nxt, npix, Ho * Wo, Cc);
-            }
+            launch_tail(st, last, down, yout, mean[sout], rstd[sout], down && !last ? yd : cur, mean[3], rstd[3], last ? feats : nxt, B, Ho * Wo, Cc);
             if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
             float* t = cur; cur = nxt; nxt = t;
         }
@@ -2855,6 +2876,138 @@ int dsmil_trunk16_forward(int32_t depth, const float* x_nhwc, int32_t B, int32_t
     unsigned short* wpk = (unsigned short*)ws;
     if (const int rc = b16::pack_all(*A, conv_w, wpk, st, kind)) return rc;
     return b16::trunk(st, *A, x_nhwc, wpk, (char*)ws + al256(b16::packed_bytes(*A)), B, Hp, Wp, feats, kind);
+}
+
+// ---- the stages of the fp32-class trunk (this file and wino_w1.h) ALONE, FOR TESTS (tests/test_trunk32_gpu.py compares each with
+// fp64 at a derived bar; include/dsmil_hip.h states the contracts).  Each entry is the trunk's own host call — plan_conv, pack_conv,
+// run_conv, plan_stem, pack_stem, launch_stem, finish_stem, launch_tail, exactly what pack_impl and resnet_forward_impl call —
+// behind argument checks that all run before the first launch: no kernel, geometry or plan of its own.  precision as in
+// dsmil_resnet_forward_ex: 0 = the process form (NPD: two fp16 planes, three products), 1 = one fp16 plane.
+namespace {
+inline bool t32_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline bool t32_prec(int precision) { return precision == 0 || precision == 1; }
+// the convs the kernels behind run_conv take: 16-channel chunks of the input (S6K, SK), 64-cout workgroups at the narrowest
+// (tile 42, k_conv_wino_s3), element offsets of either map inside an int (the staging offsets of the Winograd kernels), the
+// Winograd weights inside one buffer resource (Cin Cout 96 bytes)
+inline int t32_conv_check(const ConvSpec& s, int B, int H, int W) {
+    if ((s.ks != 1 && s.ks != 3) || (s.stride != 1 && s.stride != 2) || s.pad > s.ks / 2) return DSMIL_E_UNSUPPORTED;
+    if (s.cin % 16 || s.cout % 64 || s.cin > 2048 || s.cout > 2048) return DSMIL_E_UNSUPPORTED;
+    if (H > 32767 || W > 32767 || H + 2 * s.pad < s.ks || W + 2 * s.pad < s.ks) return DSMIL_E_UNSUPPORTED;
+    const long long Ho = outdim(H, s.ks, s.stride, s.pad), Wo = outdim(W, s.ks, s.stride, s.pad);
+    if ((long long)B * H * W * s.cin >= 0x7fffffffLL || (long long)B * Ho * Wo * s.cout >= 0x7fffffffLL) return DSMIL_E_UNSUPPORTED;
+    return DSMIL_OK;
+}
+struct T32ConvWs { size_t packed, part, total; };
+inline T32ConvWs t32_conv_ws(const ConvPlan& p) {
+    T32ConvWs w;
+    w.packed = 0;
+    w.part = al256((size_t)p.wfloats * sizeof(float));
+    w.total = w.part + al256((size_t)p.part_elems * sizeof(float));
+    return w;
+}
+// k_stem_s6 / k_pool_fix_norm: a 32-pixel input at least (as dsmil_resnet_forward), offsets of the input inside an int
+inline int t32_stem_check(int B, int H, int W) {
+    if (H < 32 || W < 32) return DSMIL_E_UNSUPPORTED;
+    if ((long long)B * 3 * H * W >= 0x7fffffffLL || B > 65535) return DSMIL_E_UNSUPPORTED;
+    return DSMIL_OK;
+}
+struct T32StemWs { size_t wimg, y0, part, total; };
+inline T32StemWs t32_stem_ws(int B, const Dims& d) {
+    T32StemWs w;
+    w.wimg = 0;
+    w.y0 = al256((size_t)SS_WIMG * sizeof(unsigned short));
+    w.part = w.y0 + al256((size_t)B * d.H1 * d.W1 * 64 * sizeof(float));
+    // (cnt, mean, M2) per (image, tile, wave, channel): the larger of k_stem's and k_stem_s6's tilings, as rws_layout sizes it
+    const long long stem_rows = std::max<long long>(((d.H1 + 7) / 8) * 4, ((d.H1 + SS_TR - 1) / SS_TR) * 8);
+    w.total = w.part + al256((size_t)((long long)B * stem_rows * ((d.W1 + 15) / 16) * 64 * 3) * sizeof(float));
+    return w;
+}
+// k_norm_add_relu: C / 4 channel groups across the 256 threads (a divisor of 256, or a multiple of it); pixels inside an unsigned
+inline bool t32_tail_c(int C) { return C % 4 == 0 && (C / 4 < 256 ? 256 % (C / 4) == 0 : (C / 4) % 256 == 0); }
+}  // namespace
+
+int dsmil_trunk32_conv_plan(int32_t Cin, int32_t Cout, int32_t ks, int32_t stride, int32_t pad, int32_t B, int32_t H, int32_t W,
+                            int32_t norm, int32_t precision, int32_t* plan) {
+    if (!plan || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || ks < 1 || stride < 1 || pad < 0 || (norm != 0 && norm != 1)) return DSMIL_E_INVALID;
+    if (!t32_prec(precision)) return DSMIL_E_UNSUPPORTED;
+    const ConvSpec s{Cout, Cin, ks, stride, pad};
+    if (const int rc = t32_conv_check(s, B, H, W)) return rc;
+    const ConvPlan p = plan_conv(s, B, H, W, norm != 0, make_form(precision, expt()), expt());
+    const int32_t kern = p.kern == CK_W1 ? DSMIL_T32_W1 : p.kern == CK_UNIT ? DSMIL_T32_UNIT : p.kern == CK_S6 ? DSMIL_T32_S6 : DSMIL_T32_OTHER;
+    const int32_t out[DSMIL_T32_PLAN_INTS] = {kern, p.wino ? 0 : p.tile, p.wino ? p.u.IB : 0, p.wino ? p.u.TYB : 0, p.wino ? p.u.TXB : 0,
+                                              p.wino ? p.u.nby : 0, p.wino ? p.u.nbx : 0, p.wino ? H : p.Ho, p.wino ? W : p.Wo,
+                                              p.wino ? 0 : p.nslots, (int32_t)p.grid.x, (int32_t)p.grid.y, (int32_t)p.block, p.np, 0, 0};
+    for (int i = 0; i < DSMIL_T32_PLAN_INTS; ++i) plan[i] = out[i];
+    return DSMIL_OK;
+}
+
+size_t dsmil_trunk32_conv_workspace_bytes(int32_t Cin, int32_t Cout, int32_t ks, int32_t stride, int32_t pad, int32_t B, int32_t H,
+                                          int32_t W, int32_t precision) {
+    if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || ks < 1 || stride < 1 || pad < 0 || !t32_prec(precision)) return 0;
+    const ConvSpec s{Cout, Cin, ks, stride, pad};
+    if (t32_conv_check(s, B, H, W)) return 0;
+    return t32_conv_ws(plan_conv(s, B, H, W, false, make_form(precision, expt()), expt())).total;
+}
+
+int dsmil_trunk32_conv(const float* x, const float* w_oihw, const float* in_mean, const float* in_rstd, const float* bn_m,
+                       const float* bn_r, float* y, float* mean, float* rstd, int32_t B, int32_t H, int32_t W, int32_t Cin,
+                       int32_t Cout, int32_t ks, int32_t stride, int32_t pad, int32_t precision, void* ws, size_t ws_bytes, void* stream) {
+    if (!x || !w_oihw || !y || !mean || !rstd || !ws || x == y || (in_mean == nullptr) != (in_rstd == nullptr) ||
+        (bn_m == nullptr) != (bn_r == nullptr)) return DSMIL_E_INVALID;
+    if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || ks < 1 || stride < 1 || pad < 0) return DSMIL_E_INVALID;
+    if (!t32_prec(precision)) return DSMIL_E_UNSUPPORTED;
+    const ConvSpec s{Cout, Cin, ks, stride, pad};
+    if (const int rc = t32_conv_check(s, B, H, W)) return rc;
+    if (!t32_al16(x) || !t32_al16(y) || !t32_al16(in_mean) || !t32_al16(in_rstd) || ((uintptr_t)w_oihw & 3) || ((uintptr_t)bn_m & 3) ||
+        ((uintptr_t)bn_r & 3) || ((uintptr_t)mean & 3) || ((uintptr_t)rstd & 3) || ((uintptr_t)ws & 255)) return DSMIL_E_ALIGN;
+    const ConvPlan p = plan_conv(s, B, H, W, in_mean != nullptr, make_form(precision, expt()), expt());
+    const T32ConvWs L = t32_conv_ws(p);
+    if (ws_bytes < L.total) return DSMIL_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    float* packed = (float*)((char*)ws + L.packed);
+    if (const int rc = pack_conv(p, s, w_oihw, packed, st)) return rc;
+    const ConvIO io{x, packed, in_mean, in_rstd, y, (float*)((char*)ws + L.part), mean, rstd, bn_m, bn_r};
+    return run_conv(st, p, s, io, B, H, W);
+}
+
+size_t dsmil_trunk32_stem_workspace_bytes(int32_t B, int32_t H, int32_t W) {
+    if (B < 1 || H < 1 || W < 1 || t32_stem_check(B, H, W)) return 0;
+    return t32_stem_ws(B, dims_for(H, W)).total;
+}
+
+int dsmil_trunk32_stem(const void* x, int32_t x_is_u8_nhwc, const float* conv1_w, const float* bn_m, const float* bn_r, float* pooled,
+                       float* mean, float* rstd, int32_t B, int32_t H, int32_t W, int32_t precision, void* ws, size_t ws_bytes,
+                       void* stream) {
+    if (!x || !conv1_w || !pooled || !mean || !rstd || !ws || (bn_m == nullptr) != (bn_r == nullptr) || B < 1 || H < 1 || W < 1) return DSMIL_E_INVALID;
+    if (!t32_prec(precision)) return DSMIL_E_UNSUPPORTED;
+    if (const int rc = t32_stem_check(B, H, W)) return rc;
+    if ((!x_is_u8_nhwc && ((uintptr_t)x & 3)) || ((uintptr_t)conv1_w & 3) || ((uintptr_t)bn_m & 3) || ((uintptr_t)bn_r & 3) ||
+        !t32_al16(pooled) || !t32_al16(mean) || !t32_al16(rstd) || ((uintptr_t)ws & 255)) return DSMIL_E_ALIGN;
+    const Dims d = dims_for(H, W);
+    const T32StemWs L = t32_stem_ws(B, d);
+    if (ws_bytes < L.total) return DSMIL_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const Form form = make_form(precision, expt());
+    const StemPlan sp = plan_stem(d, B, bn_m != nullptr, form, expt());
+    unsigned short* wimg = (unsigned short*)((char*)ws + L.wimg);
+    float* y0 = (float*)((char*)ws + L.y0);
+    float* part = (float*)((char*)ws + L.part);
+    if (const int rc = pack_stem(conv1_w, wimg, form, st)) return rc;
+    if (!launch_stem(sp, x_is_u8_nhwc != 0, st, x, conv1_w, wimg, y0, pooled, part, B, H, W, d)) return DSMIL_E_UNSUPPORTED;
+    if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    return finish_stem(st, sp, bn_m, bn_r, part, y0, pooled, mean, rstd, B, d, nullptr, 0);
+}
+
+int dsmil_trunk32_tail(int32_t kind, const float* y2, const float* m2, const float* r2, const float* idn, const float* md,
+                       const float* rd, float* out, int32_t B, int32_t HW, int32_t C, int32_t precision, void* stream) {
+    if (!y2 || !m2 || !r2 || !idn || !out || B < 1 || HW < 1 || C < 1 || kind < 0 || kind > 2) return DSMIL_E_INVALID;
+    if (kind == 1 ? (!md || !rd) : (md || rd)) return DSMIL_E_INVALID;
+    if (!t32_prec(precision)) return DSMIL_E_UNSUPPORTED;
+    if (!t32_tail_c(C) || (long long)B * HW * C >= 0x7fffffffLL) return DSMIL_E_UNSUPPORTED;
+    if (!t32_al16(y2) || !t32_al16(m2) || !t32_al16(r2) || !t32_al16(idn) || !t32_al16(md) || !t32_al16(rd) ||
+        (kind == 2 ? ((uintptr_t)out & 3) != 0 : !t32_al16(out))) return DSMIL_E_ALIGN;
+    launch_tail((hipStream_t)stream, kind == 2, kind == 1, y2, m2, r2, idn, md, rd, out, B, HW, C);
+    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 
 int dsmil_resnet_forward(int32_t depth, const void* x, int32_t x_is_u8_nhwc, int32_t B, int32_t H, int32_t W,

@@ -1074,6 +1074,107 @@ def trunk16_forward(x_nhwc, convs, kind):
 
 
 # ---------------------------------------------------------------------------------------------
+# the stages of the fp32-class trunk ALONE (csrc/resnet_fwd.hip, csrc/wino_w1.h behind dsmil_trunk32_*): FOR TESTS — no product
+# path calls these.  Maps are fp32 NHWC tensors, statistics fp32 [B,C].  precision "fp32" = the product form (two fp16 planes,
+# three products), "half" = one fp16 plane.  A shape the kernels do not take raises NotImplementedError (DSMIL_E_UNSUPPORTED),
+# every other refusal RuntimeError; nothing is launched in either case.
+# ---------------------------------------------------------------------------------------------
+TRUNK32_PRECISIONS = {"fp32": 0, "half": 1}
+TRUNK32_KERNELS = {0: "w1", 1: "unit", 2: "s6", 3: "other"}
+TRUNK32_TAILS = {"identity": 0, "down": 1, "pool": 2}
+_T32_PLAN_FIELDS = ("kernel", "tile", "IB", "TYB", "TXB", "nby", "nbx", "Ho", "Wo", "nslots", "grid_x", "grid_y", "block", "products")
+
+
+def _t32_check(rc, what):
+    if rc == _native.DSMIL_E_UNSUPPORTED:
+        raise NotImplementedError(f"{what}: shape or precision outside what the fp32-class trunk's kernels implement")
+    _native.check(rc, what)
+
+
+def trunk32_conv_plan(Cin, Cout, ks, stride, pad, B, H, W, norm=False, precision="fp32"):
+    """What plan_conv decides for this conv on B maps of H x W (no device needed): a dict of ``kernel`` ("w1", "unit", "s6"),
+    ``tile`` (direct: 42 / 22 / 24), the Winograd unit ``IB, TYB, TXB, nby, nbx``, ``Ho, Wo, nslots``, ``grid_x, grid_y, block``
+    and ``products`` (plane products per MAC)."""
+    out = (ctypes.c_int32 * 16)()
+    rc = _native.lib().dsmil_trunk32_conv_plan(Cin, Cout, ks, stride, pad, B, H, W, 1 if norm else 0, TRUNK32_PRECISIONS[precision], out)
+    _t32_check(rc, "dsmil_trunk32_conv_plan")
+    d = dict(zip(_T32_PLAN_FIELDS, list(out)))
+    d["kernel"] = TRUNK32_KERNELS[d["kernel"]]
+    return d
+
+
+def trunk32_conv(x_nhwc, w, stride, pad, in_stats=None, frozen=None, precision="fp32"):
+    """pack + run_conv: x fp32 NHWC [B,H,W,Cin], w fp32 OIHW -> (raw y [B,Ho,Wo,Cout], mean [B,Cout], rstd [B,Cout]).
+    ``in_stats`` = (mean, rstd) [B,Cin]: x is raw and is staged as relu((x - mean) rstd); ``frozen`` = (m, r) [Cout]: the
+    statistics are these per-channel values."""
+    x, w = _f32c(x_nhwc, "x_nhwc"), _f32c(w, "w")
+    B, H, W, Cin = x.shape
+    Cout, Cin_w, ks, _ = w.shape
+    if Cin_w != Cin:
+        raise ValueError(f"w takes {Cin_w} input channels, x has {Cin}")
+    im, ir = (_f32c(t, "in_stats") for t in in_stats) if in_stats is not None else (None, None)
+    bm, br = (_f32c(t, "frozen") for t in frozen) if frozen is not None else (None, None)
+    p = TRUNK32_PRECISIONS[precision]
+    Ho, Wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
+    L = _native.lib()
+    ws = _t16_scratch(x.device, L.dsmil_trunk32_conv_workspace_bytes(Cin, Cout, ks, stride, pad, B, H, W, p))
+    y = torch.empty((B, max(Ho, 0), max(Wo, 0), Cout), dtype=torch.float32, device=x.device)
+    mean = torch.empty((B, Cout), dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    with torch.cuda.device(x.device):
+        rc = L.dsmil_trunk32_conv(_ptr(x), _ptr(w), _ptr(im), _ptr(ir), _ptr(bm), _ptr(br), _ptr(y), _ptr(mean), _ptr(rstd), B, H, W,
+                                  Cin, Cout, ks, stride, pad, p, _ptr(ws), ws.numel(), _stream(x.device))
+    _t32_check(rc, "dsmil_trunk32_conv")
+    return y, mean, rstd
+
+
+def trunk32_stem(x, conv1_w, frozen=None, precision="fp32"):
+    """pack + stem + statistics + pool: x fp32 NCHW [B,3,H,W] or uint8 NHWC [B,H,W,3] -> (pooled fp32 NHWC [B,Hp,Wp,64],
+    mean [B,64], rstd [B,64]).  ``frozen`` = (m, r) [64]: the frozen-statistics route (raw map + k_norm_relu_maxpool)."""
+    if not x.is_cuda or not x.is_contiguous() or x.dtype not in (torch.float32, torch.uint8):
+        raise RuntimeError("x must be a contiguous float32 NCHW or uint8 NHWC CUDA(HIP) tensor")
+    u8 = x.dtype == torch.uint8
+    B, H, W = (x.shape[0], x.shape[1], x.shape[2]) if u8 else (x.shape[0], x.shape[2], x.shape[3])
+    if (x.shape[3] if u8 else x.shape[1]) != 3:
+        raise ValueError("the stem takes three input channels")
+    w = _f32c(conv1_w, "conv1_w")
+    if tuple(w.shape) != (64, 3, 7, 7):
+        raise ValueError("conv1_w must be [64,3,7,7]")
+    bm, br = (_f32c(t, "frozen") for t in frozen) if frozen is not None else (None, None)
+    H1, W1 = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
+    Hp, Wp = (H1 + 2 - 3) // 2 + 1, (W1 + 2 - 3) // 2 + 1
+    L = _native.lib()
+    ws = _t16_scratch(x.device, L.dsmil_trunk32_stem_workspace_bytes(B, H, W))
+    pooled = torch.empty((B, Hp, Wp, 64), dtype=torch.float32, device=x.device)
+    mean = torch.empty((B, 64), dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    with torch.cuda.device(x.device):
+        rc = L.dsmil_trunk32_stem(_ptr(x), 1 if u8 else 0, _ptr(w), _ptr(bm), _ptr(br), _ptr(pooled), _ptr(mean), _ptr(rstd), B, H, W,
+                                  TRUNK32_PRECISIONS[precision], _ptr(ws), ws.numel(), _stream(x.device))
+    _t32_check(rc, "dsmil_trunk32_stem")
+    return pooled, mean, rstd
+
+
+def trunk32_tail(kind, y2, stats, idn, down_stats=None):
+    """The pass that closes a block, y2 / idn fp32 [B,...,C], stats = (mean, rstd) [B,C]: "identity" relu(IN(y2) + idn),
+    "down" relu(IN(y2) + IN(idn)) with ``down_stats`` of the raw downsample branch idn, "pool" the pixel mean of "identity"
+    -> [B,C]."""
+    y2, idn = _f32c(y2, "y2"), _f32c(idn, "idn")
+    if idn.shape != y2.shape:
+        raise ValueError("idn must have y2's shape")
+    B, C = y2.shape[0], y2.shape[-1]
+    HW = y2.numel() // (B * C)
+    m2, r2 = (_f32c(t, "stats") for t in stats)
+    md, rd = (_f32c(t, "down_stats") for t in down_stats) if down_stats is not None else (None, None)
+    out = torch.empty((B, C) if kind == "pool" else y2.shape, dtype=torch.float32, device=y2.device)
+    with torch.cuda.device(y2.device):
+        rc = _native.lib().dsmil_trunk32_tail(TRUNK32_TAILS[kind], _ptr(y2), _ptr(m2), _ptr(r2), _ptr(idn), _ptr(md), _ptr(rd), _ptr(out),
+                                              B, HW, C, 0, _stream(y2.device))
+    _t32_check(rc, "dsmil_trunk32_tail")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # background filters of the tilers (deepzoom_tiler.py:56-61, test_crop_single.py:17-24)
 # ---------------------------------------------------------------------------------------------
 def tile_stats(tiles):

@@ -581,6 +581,62 @@ size_t dsmil_trunk16_workspace_bytes(int32_t depth, int32_t B, int32_t Hp, int32
 int dsmil_trunk16_forward(int32_t depth, const float* x_nhwc, int32_t B, int32_t Hp, int32_t Wp, const float* const* conv_w,
                           float* feats, int32_t kind, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the stages of the fp32-class trunk ALONE — FOR TESTS (tests/test_trunk32_gpu.py; no reference counterpart).  The default
+ * embedder path (fp32 activations, conv operands as two fp16 planes and three plane products: csrc/resnet_fwd.hip, csrc/wino_w1.h)
+ * is otherwise reachable only as a whole network, where an InstanceNorm behind every conv rescales what a kernel got wrong; these
+ * entries run ONE stage of it on buffers the caller controls, through the trunk's own host calls (plan_conv / pack_conv / run_conv,
+ * plan_stem / pack_stem / launch_stem / finish_stem, launch_tail: what dsmil_resnet_pack and dsmil_resnet_forward call — same
+ * kernels, same plans, same launch geometry).  No product path calls them.
+ *   precision  0 = the product form (two fp16 planes of each operand, products h0 w0 + h0 w1 + h1 w0), 1 = one fp16 plane
+ *              (what precision 1 of dsmil_resnet_forward_ex runs); anything else is DSMIL_E_UNSUPPORTED.
+ *   maps       fp32 NHWC, 16-byte aligned; statistics [B,C] fp32 (16-byte aligned where a kernel reads them: in_mean / in_rstd,
+ *              the stem's and the tail's); every workspace is 256-byte aligned.
+ *   dsmil_trunk32_conv_plan  host only, no launch: what plan_conv decides for this conv on B maps of H x W, as
+ *                          DSMIL_T32_PLAN_INTS int32: [0] kernel (DSMIL_T32_W1 = k_conv_wino_w1, _UNIT = k_conv_wino_s3, _S6 =
+ *                          k_conv_s6), [1] direct tile digits (42 = 128 px x 64 couts, 22 = 64 x 128, 24 = 64 x 256; 0 for
+ *                          Winograd), [2..6] Winograd unit IB, TYB, TXB, nby, nbx (0 for direct), [7] Ho, [8] Wo, [9] statistics
+ *                          slots per 32-pixel tile (direct; 0 for Winograd), [10] grid.x, [11] grid.y, [12] threads per
+ *                          workgroup, [13] plane products per MAC, [14..15] 0.
+ *   dsmil_trunk32_conv     the pack kernel the plan calls for (k_pack_wino_s3 / k_pack_conv_s6: w_oihw -> ws), then run_conv:
+ *                          x [B,H,W,Cin] -> raw y [B,Ho,Wo,Cout] and mean / rstd [B,Cout] (biased variance, eps 1e-5) from the
+ *                          conv's statistics partials (k_in_finalize_cnt / _flat) — or, with bn_m / bn_r [Cout] (both or neither),
+ *                          those per-channel values for every image (fill_stats).  in_mean / in_rstd [B,Cin] (both or neither):
+ *                          x is a raw map and is staged as relu((x - in_mean) in_rstd).  3x3 / stride 1 / pad 1 runs as Winograd
+ *                          F(2x2,3x3), everything else direct.  ks 1 or 3, stride 1 or 2, pad <= ks / 2, Cin % 16 == 0,
+ *                          Cout % 64 == 0, both <= 2048, each map under 2^31 elements.
+ *   dsmil_trunk32_stem     k_pack_stem_s6 + k_stem_s6 + statistics + pool: x fp32 NCHW [B,3,H,W] or (x_is_u8_nhwc) uint8 NHWC, as
+ *                          dsmil_resnet_forward takes -> pooled [B,Hp,Wp,64] = maxpool3x3/2(relu(norm(conv7x7/2(x)))), mean / rstd
+ *                          [B,64].  Without bn_m / bn_r the InstanceNorm route (pool fused into the stem, k_in_finalize_stem,
+ *                          k_pool_fix_norm); with bn_m / bn_r [64] (negative bn_r allowed) the frozen route (raw map, fill_stats,
+ *                          k_norm_relu_maxpool).  H, W >= 32.
+ *   dsmil_trunk32_tail     kind 0: out = relu((y2 - m2) r2 + idn); kind 1: out = relu((y2 - m2) r2 + (idn - md) rd) (idn = the raw
+ *                          downsample branch; md / rd only here); kind 2: out [B,C] = mean over pixels of kind 0.  y2, idn, out
+ *                          [B,HW,C]; k_norm_add_relu's grid is the forward's (8192 workgroups at most, grid stride beyond).  C / 4
+ *                          must divide 256 or be a multiple of it.
+ * Every check runs BEFORE the first launch, in the order DSMIL_E_INVALID (null pointers, pointer pairs half given, in place,
+ * non-positive sizes, kind), DSMIL_E_UNSUPPORTED (precision, the forms, channel multiples and sizes above), DSMIL_E_ALIGN,
+ * DSMIL_E_WORKSPACE; the *_workspace_bytes queries answer 0 for arguments the entry refuses.
+ * Added without a change of DSMIL_ABI_VERSION (it stays 6, no existing signature moved): a caller finds them by symbol. */
+#define DSMIL_T32_W1 0
+#define DSMIL_T32_UNIT 1
+#define DSMIL_T32_S6 2
+#define DSMIL_T32_OTHER 3       /* a kernel of experiment builds */
+#define DSMIL_T32_PLAN_INTS 16
+int dsmil_trunk32_conv_plan(int32_t Cin, int32_t Cout, int32_t ks, int32_t stride, int32_t pad, int32_t B, int32_t H, int32_t W,
+                            int32_t norm, int32_t precision, int32_t* plan);
+size_t dsmil_trunk32_conv_workspace_bytes(int32_t Cin, int32_t Cout, int32_t ks, int32_t stride, int32_t pad, int32_t B, int32_t H,
+                                          int32_t W, int32_t precision);
+int dsmil_trunk32_conv(const float* x, const float* w_oihw, const float* in_mean, const float* in_rstd, const float* bn_m,
+                       const float* bn_r, float* y, float* mean, float* rstd, int32_t B, int32_t H, int32_t W, int32_t Cin,
+                       int32_t Cout, int32_t ks, int32_t stride, int32_t pad, int32_t precision, void* ws, size_t ws_bytes,
+                       void* stream);
+size_t dsmil_trunk32_stem_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int dsmil_trunk32_stem(const void* x, int32_t x_is_u8_nhwc, const float* conv1_w, const float* bn_m, const float* bn_r,
+                       float* pooled, float* mean, float* rstd, int32_t B, int32_t H, int32_t W, int32_t precision, void* ws,
+                       size_t ws_bytes, void* stream);
+int dsmil_trunk32_tail(int32_t kind, const float* y2, const float* m2, const float* r2, const float* idn, const float* md,
+                       const float* rd, float* out, int32_t B, int32_t HW, int32_t C, int32_t precision, void* stream);
+
 /* ---- background filters of the reference's tilers on decoded tiles -------------------------
  * tiles_nhwc: device uint8 [B,H,W,3] (W <= 1024).  out: device uint64 [B,4] = per tile
  *   {sum over band 0, band 1, band 2 of PIL's ImageFilter.FIND_EDGES image, sum of img_as_ubyte(rgb2hsv(img)[...,1])}.
