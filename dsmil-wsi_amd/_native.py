@@ -229,6 +229,10 @@ SIGNATURES = {
     "dsmil_value_forward_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, c_f32p, c_f32p,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                                 ctypes.c_void_p]),
+    "dsmil_value_backward_bf16_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
+    "dsmil_value_backward_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_f32p, ctypes.c_int64, ctypes.c_int32,
+                                                 ctypes.c_int32, c_f32p, c_f32p, ctypes.c_void_p, ctypes.c_size_t,
+                                                 ctypes.c_void_p]),
     "dsmil_agg_train_step_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "dsmil_agg_train_step": (ctypes.c_int, [c_f32p, ctypes.c_int64, c_i64p, c_f32p, ctypes.POINTER(AggParams),
                                             ctypes.POINTER(AdamState), c_f32p, ctypes.c_void_p, ctypes.c_size_t,

@@ -1690,6 +1690,46 @@ int dsmil_value_backward(const float* feats, const float* V, const float* g_vals
     return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 
+// bf16-stored rows (k_value_tn_b16): the same partial layout and reduce; no weight image in front of the partials
+struct VtnB16Ws { size_t part, pb, total; };
+static VtnB16Ws vtn_b16_ws_layout(long long rows, int K, int Kv) {
+    VtnB16Ws L;
+    int S, R;
+    vtn_plan(rows, K, Kv, S, R);
+    L.part = 0;
+    L.pb = vp_al((size_t)S * Kv * K * 4);
+    L.total = L.pb + vp_al((size_t)S * Kv * 4);
+    return L;
+}
+
+size_t dsmil_value_backward_bf16_workspace_bytes(int64_t rows, int32_t K, int32_t Kv) {
+    if (rows <= 0 || K <= 0 || Kv <= 0) return 0;
+    return vtn_b16_ws_layout(rows, K, Kv).total;
+}
+
+int dsmil_value_backward_bf16(const void* feats_bf16, const void* V_bf16, const float* g_vals, int64_t rows, int32_t K,
+                              int32_t Kv, float* g_v_w, float* g_v_b, void* ws, size_t ws_bytes, void* stream) {
+    if (!feats_bf16 || !V_bf16 || !g_vals || !g_v_w || !g_v_b || !ws || rows <= 0 || K <= 0 || Kv <= 0) return DSMIL_E_INVALID;
+    if (K % 8 || Kv % 4) return DSMIL_E_UNSUPPORTED;
+    VtnB16Args a{};
+    vtn_plan(rows, K, Kv, a.S, a.R);
+    a.nsk = (K + 63) / 64; a.nsu = (Kv + 127) / 128;
+    const long long wgs = (long long)a.nsk * a.nsu * a.S;
+    if (wgs > 0x7fffffffLL) return DSMIL_E_UNSUPPORTED;
+    if ((uintptr_t)feats_bf16 % 16 || (uintptr_t)V_bf16 % 8 || (uintptr_t)g_vals % 16 || (uintptr_t)ws % 256) return DSMIL_E_ALIGN;
+    const VtnB16Ws L = vtn_b16_ws_layout(rows, K, Kv);
+    if (ws_bytes < L.total) return DSMIL_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    a.G = g_vals; a.V = (const bf16_t*)V_bf16; a.X = (const bf16_t*)feats_bf16;
+    a.part = (float*)((char*)ws + L.part); a.pb = (float*)((char*)ws + L.pb);
+    a.N = rows; a.K = K; a.Kv = Kv;
+    hipLaunchKernelGGL(k_value_tn_b16, dim3((unsigned)wgs), dim3(256), 0, st, a);
+    if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    const long long n = (long long)Kv * K + Kv;
+    hipLaunchKernelGGL(k_value_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.part, a.pb, g_v_w, g_v_b, K, Kv, a.S);
+    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
+}
+
 int dsmil_value_backward_rows(const float* feats, const float* V, const float* g_vals, int64_t rows, int32_t K, int32_t Kv,
                               const float* v_w, const void* packed, int32_t accumulate, float* g_feats, void* ws,
                               size_t ws_bytes, void* stream) {

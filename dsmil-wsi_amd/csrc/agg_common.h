@@ -167,6 +167,16 @@ __device__ __forceinline__ f32x4 load4_nocheck(const T* __restrict__ p, int k) {
     }
 }
 
+// bf16 rows: the same 8-byte fetch with the four elements left packed (element c in bits 16 (c & 1) of word c >> 1), for a
+// consumer that keeps them in flight as two registers and widens (bf16x4_at) or repacks them when it uses them
+__device__ __forceinline__ u32x2 load4_bits(const bf16_t* __restrict__ p, long long k) {
+    return *(const DSMIL_GLOBAL u32x2*)(p + k);
+}
+__device__ __forceinline__ float bf16x4_at(u32x2 t, int c) {   // element c of load4_bits as a float (c: a literal)
+    const unsigned w = c < 2 ? t.x : t.y;
+    return __uint_as_float((c & 1) ? (w & 0xffff0000u) : (w << 16));
+}
+
 // Staging variant: never branches for VEC=4 — the address is clamped into the row (klim % 4 == 0,
 // klim >= 4) and the caller zeroes out-of-range k later (at LDS-write time), so a run of these
 // loads issues back to back and stays in flight under the MFMAs.

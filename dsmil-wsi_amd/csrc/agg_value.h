@@ -1,7 +1,7 @@
 // agg_value.h — the value stream of BClassifier(passing_v=True), dsmil.py:35-39,48:  V = ReLU(x Wv^T + bv)  and its
 // parameter gradients.  Included from agg_fwd.hip (DSMIL_VALUE_FWD: k_pack_value, k_value_proj, k_value_proj_valu and, for
 // bf16-stored rows, k_pack_value_b16, k_value_proj_b16, k_value_proj_b16_valu: described above them) and from agg_bwd.hip
-// (DSMIL_VALUE_BWD: k_value_tn, k_value_reduce).
+// (DSMIL_VALUE_BWD: k_value_tn, k_value_reduce and, for bf16-stored rows, k_value_tn_b16: described above it).
 //
 // Forward, k_value_proj.  A GEMM with Kv output columns per row on v_mfma_f32_32x32x16_f16 in the arithmetic of agg_f2.h:
 // x' = x * 2^e per ROW, Wv' = Wv * 2^f per TENSOR (f2_scale), both cut into two fp16 planes (split2h_scaled / the pack
@@ -583,6 +583,175 @@ __global__ __launch_bounds__(256, 2) void k_value_tn(VtnArgs a) {
         s_cs[tid] = colsum;
         __syncthreads();
         if (tid < 128 && u0 + tid < a.Kv) a.pb[(long long)split * a.Kv + u0 + tid] = s_cs[tid] + s_cs[tid + 128];
+    }
+}
+
+// ---- bf16-stored rows: k_value_tn_b16 ---------------------------------------------------------------------------------------
+// The same contraction on the operands of the bf16 path: x [rows, K] and V [rows, Kv] raw bf16, g_vals [rows, Kv] fp32 (the
+// bf16 aggregator backward's, unrounded).  A bf16 row is ONE exact bf16 MFMA operand, so x is staged as one plane — no zero
+// planes in LDS, no MFMA on them: the three exact planes of gZ times that plane, THREE products per 16-deep step and
+// accumulator, all kept (the fp32 kernel issues six of nine); sB is a third of k_value_tn's.  Tile geometry, row ranges
+// (vtn_plan), partial layout and k_value_reduce are k_value_tn's.  K % 8 == 0, Kv % 4 == 0.
+// Staging is k_tn_split's wide form: a thread owns FOUR columns and 8 consecutive rows, one load per row — 8 bytes of x or V
+// (load4_bits), 16 bytes of g_vals — and the LDS holds the columns permuted (unit u0 + 4g + c at position 32c + g, column
+// col0 + 4g + c at position 16c + g) so that consecutive lanes write consecutive positions; the epilogue undoes it.  Waves 0, 1
+// stage A (gZ = V > 0 ? g : 0 as a select on the bf16 value: +0, -0 and a NaN V mask, a NaN / inf g at a masked position gives
+// 0; cut into three planes), wave 2 stages B (x repacked, never widened: 8 rows of a column = 4 words), wave 3 only
+// multiplies.  Each role takes its own straight-line loop, steps come in pairs and four pairs are unrolled (R is a multiple of
+// 64; the A rows past a range are zero): see k_tn_split for why the wait-count pass needs that shape.
+struct VtnB16Args {
+    const float* G;              // g_vals [N, Kv]
+    const bf16_t* V;             // the forward's V [N, Kv]
+    const bf16_t* X;             // feats [N, K]
+    float* part;                 // [S][Kv][K]
+    float* pb;                   // [S][Kv]
+    long long N;
+    int K, Kv, R, nsk, nsu, S;
+};
+
+__global__ __launch_bounds__(256, 2) void k_value_tn_b16(VtnB16Args a) {
+    __shared__ __attribute__((aligned(16))) unsigned sA[3 * 128 * VTN_LDW];
+    __shared__ __attribute__((aligned(16))) unsigned sB[64 * VTN_LDW];
+    __shared__ float s_cs[512];
+    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int cs = (int)(blockIdx.x % a.nsk);
+    const int q = (int)(blockIdx.x / a.nsk);
+    const int us = q % a.nsu, split = q / a.nsu;
+    const int u0 = us * 128, col0 = cs * 64;
+    const long long rbeg = (long long)split * a.R, rend = (rbeg + a.R < a.N) ? rbeg + a.R : a.N;
+    const bool want_cs = cs == 0;
+    f32x16 acc[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    const int ct = wave & 1, up = wave >> 1;
+    auto mfma_phase = [&]() {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const int j = 2 * ks + hi;    // this lane's 8-row group: MFMA k = 8 hi + i  <->  row 16 ks + 8 hi + i
+            S3Frag fb;
+            fb.f = *reinterpret_cast<const f32x4*>(&sB[(32 * ct + l31) * VTN_LDW + 4 * j]);
+            S3Frag fa[2][3];
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+                for (int p = 0; p < 3; ++p)
+                    fa[tt][p].f = *reinterpret_cast<const f32x4*>(&sA[(p * 128 + 32 * (2 * up + tt) + l31) * VTN_LDW + 4 * j]);
+#pragma unroll
+            for (int p = 2; p >= 0; --p)                 // all three plane products, smallest first; the accumulators in turn
+#pragma unroll
+                for (int tt = 0; tt < 2; ++tt)
+                    acc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tt][p].v, fb.v, acc[tt], 0, 0, 0);
+        }
+    };
+    float cs4[4] = {0.f, 0.f, 0.f, 0.f};
+    int csg = 0, csj = 0;                                // the A role's (column group, 8-row group), for the bias sum
+    auto stage_loop = [&](auto rolec) {
+        constexpr bool RA = decltype(rolec)::value;
+        const int g = RA ? (tid & 31) : (tid & 15), jg = RA ? (tid >> 5) : ((tid >> 4) & 3);
+        const int ld = RA ? a.Kv : a.K;
+        int c4 = (RA ? u0 : col0) + 4 * g;
+        const bool c_ok = c4 < ld;                       // (K, Kv % 4 == 0: a group of four is inside or outside together)
+        c4 = c_ok ? c4 : ld - 4;                         // a clamped unit's values are zeroed, a clamped column's never stored
+        const bf16_t* p16 = (RA ? a.V : a.X) + c4;
+        const float* pg = a.G + c4;
+        csg = g; csj = jg;
+        u32x2 vb[2][8];
+        f32x4 vg[2][RA ? 8 : 1];
+        auto prefetch = [&](auto setc, long long r0) {   // branch-free: rows past the range re-read its last row
+            constexpr int SET = decltype(setc)::value;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                long long r = r0 + 8 * jg + e;
+                r = r < rend ? r : rend - 1;
+                vb[SET][e] = load4_bits(p16, r * ld);
+                if constexpr (RA) vg[SET][e] = *(const DSMIL_GLOBAL f32x4*)(pg + r * ld);
+            }
+        };
+        auto step = [&](auto setc, long long r0) {
+            constexpr int SET = decltype(setc)::value;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if constexpr (RA) {
+                    float gz[8];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const bool live = c_ok && r0 + 8 * jg + e < rend && bf16x4_at(vb[SET][e], c) > 0.f;   // ReLU mask (dsmil.py:39)
+                        gz[e] = live ? vg[SET][e][c] : 0.f;
+                    }
+                    if (want_cs) {
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) cs4[c] += gz[e];
+                    }
+                    S3Frag f[3];
+                    split3(gz, f);
+#pragma unroll
+                    for (int p = 0; p < 3; ++p)
+                        *reinterpret_cast<f32x4*>(&sA[(p * 128 + 32 * c + g) * VTN_LDW + 4 * jg]) = f[p].f;
+                } else {
+                    S3Frag f;                            // rows 2i, 2i + 1 of column c: the halves 16 (c & 1) of word c >> 1
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const unsigned w1 = c < 2 ? vb[SET][2 * i + 1].x : vb[SET][2 * i + 1].y;
+                        const unsigned w0 = c < 2 ? vb[SET][2 * i].x : vb[SET][2 * i].y;
+                        f.u[i] = __builtin_amdgcn_perm(w1, w0, (c & 1) ? 0x07060302u : 0x05040100u);
+                    }
+                    *reinterpret_cast<f32x4*>(&sB[(16 * c + g) * VTN_LDW + 4 * jg]) = f.f;
+                }
+            }
+            __syncthreads();
+            prefetch(setc, r0 + 64);
+            mfma_phase();
+            __syncthreads();
+        };
+        prefetch(std::integral_constant<int, 0>{}, rbeg);
+        prefetch(std::integral_constant<int, 1>{}, rbeg + 32);
+        for (long long r0 = rbeg; r0 < rend; r0 += 256) {   // four pairs straight-line, forward exits only
+#pragma unroll
+            for (int h = 0; h < 4; ++h) {
+                if (r0 + 64 * h >= rend) break;
+                step(std::integral_constant<int, 0>{}, r0 + 64 * h);
+                step(std::integral_constant<int, 1>{}, r0 + 64 * h + 32);
+            }
+        }
+    };
+    if (wave < 2) {
+        stage_loop(std::true_type{});
+    } else if (wave == 2) {
+        stage_loop(std::false_type{});
+    } else {
+        for (long long r0 = rbeg; r0 < rend; r0 += 64) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                __syncthreads();
+                mfma_phase();
+                __syncthreads();
+            }
+        }
+    }
+    // D[m position][n position]: position -> unit u0 + 4 (m & 31) + (m >> 5), column col0 + 4 (n & 15) + (n >> 4)
+    const int npos = 32 * ct + l31, col = col0 + 4 * (npos & 15) + (npos >> 4);
+    if (col < a.K) {
+        float* o = a.part + (long long)split * a.Kv * a.K;
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int mp = 32 * (2 * up + tt) + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                const int m = u0 + 4 * (mp & 31) + (mp >> 5);
+                if (m < a.Kv) o[(long long)m * a.K + col] = acc[tt][r];
+            }
+    }
+    if (want_cs) {
+        if (wave < 2) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) s_cs[csj * 128 + 4 * csg + c] = cs4[c];
+        }
+        __syncthreads();
+        if (tid < 128 && u0 + tid < a.Kv)
+            a.pb[(long long)split * a.Kv + u0 + tid] = (s_cs[tid] + s_cs[128 + tid]) + (s_cs[256 + tid] + s_cs[384 + tid]);
     }
 }
 

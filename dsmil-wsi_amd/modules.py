@@ -103,6 +103,14 @@ class IClassifier(nn.Module):
 class BClassifier(nn.Module):
     """dsmil.py:27-62."""
 
+    train_value_on_bf16 = False
+    """Opt-in (set it on an instance): train the value layer of a ``passing_v`` model on bf16-stored rows.  The projection
+    then runs INSIDE the aggregator's autograd Function (dsmil_value_forward_bf16 in its forward; in its backward the fp32
+    g_vals of dsmil_agg_backward_bags_bf16 go unrounded to dsmil_value_backward_bf16), and v.1.weight / v.1.bias get their
+    gradients in their own dtype.  Off, that combination raises NotImplementedError as it always has; the default flips in a
+    follow-up that may touch the test pinning the refusal (tests/test_bwd_b16_gpu.py::test_refusals).  Rows that require a
+    gradient are refused either way, an ACTIVE dropout keeps the torch route, a frozen value layer stays a constant."""
+
     def __init__(self, input_size, output_class, dropout_v=0.0, nonlinear=True, passing_v=False):
         super().__init__()
         if nonlinear:
@@ -151,29 +159,42 @@ class BClassifier(nn.Module):
         mode, p > 0) is torch's own, applied to the rows first — the native projection then runs on the dropped rows; torch's
         random stream is not reproduced inside a kernel.  bf16-stored rows take the native projection of the bf16 path
         (dsmil_value_forward_bf16: fp32 master weights are rounded inside, as ops.agg_forward does with the aggregator's),
-        which has no backward: under autograd a TRAINABLE value layer on bf16 rows raises (the aggregator trains on bf16
-        rows, the value layer does not — detaching it here would train without it and say nothing); a frozen one is a
-        constant.  With an ACTIVE dropout they keep the torch route (nn.Linear + ReLU)."""
+        as a constant: under autograd a TRAINABLE value layer on bf16 rows is projected inside _AggFunction instead
+        (_value_args, with ``train_value_on_bf16``) and raises here (detaching it would train without it and say nothing);
+        a frozen one is a constant.  With an ACTIVE dropout they keep the torch route (nn.Linear + ReLU)."""
         if not self.passing_v:
             return None
         drop, lin = self.v[0], self.v[1]
         active = drop.training and drop.p > 0
         if feats.dtype == torch.bfloat16 and not active:
             if torch.is_grad_enabled() and (lin.weight.requires_grad or lin.bias.requires_grad):
-                raise NotImplementedError("passing_v with a trainable value layer on bf16-stored rows: the bf16 value "
-                                          "projection has no backward (freeze b_classifier.v or store the rows in fp32)")
+                raise NotImplementedError("passing_v with a trainable value layer on bf16-stored rows is opt-in: set "
+                                          "b_classifier.train_value_on_bf16 = True (or freeze b_classifier.v, or store "
+                                          "the rows in fp32)")
             return ops.value_proj(feats.detach(), lin.weight.detach(), lin.bias.detach())
         if feats.dtype != torch.float32:
             return self.v(feats)
         x = drop(feats) if active else feats
         return _ValueProjFunction.apply(x, lin.weight, lin.bias)
 
+    def _value_args(self, feats):
+        """(vals, v_w, v_b) for _AggFunction: ``vals`` = _values(feats) and no layer — except for bf16-stored rows with a
+        TRAINABLE value layer under autograd on an instance that set ``train_value_on_bf16`` (no active dropout): then no
+        ``vals`` and the layer's two parameters, and the Function projects the rows itself (a bf16 V tensor in the graph
+        between two Functions would have the engine round g_vals to bf16 on its way to the value layer)."""
+        if self.passing_v and self.train_value_on_bf16 and feats.dtype == torch.bfloat16 and torch.is_grad_enabled():
+            drop, lin = self.v[0], self.v[1]
+            if not (drop.training and drop.p > 0) and (lin.weight.requires_grad or lin.bias.requires_grad):
+                return None, lin.weight, lin.bias
+        return self._values(feats), None, None
+
     def forward(self, feats, c):
         if not feats.is_cuda:
             return self._forward_cpu(feats, c)
         MILNet._loss_dtype(feats)   # (bf16 rows that require a gradient are refused here, under grad mode)
         w = _wdict(None, None, **self._weights())
-        pred, A, B = _AggFunction.apply(feats, c, self._values(feats), None, *w.values(), self.nonlinear)[1:4]
+        vals, v_w, v_b = self._value_args(feats)
+        pred, A, B = _AggFunction.apply(feats, c, vals, None, *w.values(), self.nonlinear, False, v_w, v_b)[1:4]
         return pred, A, B
 
 
@@ -211,7 +232,8 @@ class MILNet(nn.Module):
             # rows that require a gradient get it from the native backward (k_bwd_gx, k_value_gx).
             # _f32_out (bag_loss / batch_loss): on bf16 rows keep the call's fp32 outputs — the loss is formed from those
             _, w = self._lin_weights()
-            return _AggFunction.apply(x, None, bc._values(x), None, *w.values(), bc.nonlinear, _f32_out)[0:4]
+            vals, v_w, v_b = bc._value_args(x)
+            return _AggFunction.apply(x, None, vals, None, *w.values(), bc.nonlinear, _f32_out, v_w, v_b)[0:4]
         feats, classes = ic(x)
         prediction_bag, A, B = bc(feats, classes)
         return classes, prediction_bag, A, B
@@ -334,7 +356,8 @@ class MILNet(nn.Module):
         if self._batch_native(feats):
             bc = self.b_classifier
             _, w = self._lin_weights()
-            return _AggFunction.apply(feats, None, bc._values(feats), tuple(lengths), *w.values(), bc.nonlinear, _f32_out)[0:4]
+            vals, v_w, v_b = bc._value_args(feats)
+            return _AggFunction.apply(feats, None, vals, tuple(lengths), *w.values(), bc.nonlinear, _f32_out, v_w, v_b)[0:4]
         outs, o = [], 0
         for n in lengths:
             classes, pred, A, B = self._forward(feats[o:o + n], _f32_out)
@@ -482,12 +505,23 @@ class _AggFunction(torch.autograd.Function):
     bf16-stored rows: the bf16 forward, outputs cast to the rows' dtype (``f32_out``: left fp32, for the loss); the backward widens the incoming gradients to fp32
     and is dsmil_agg_backward_bags_bf16 — the gradient of the reference function at the bf16 rows and the bf16-rounded
     parameters with the forward's A, B, idx, straight-through for the roundings; fp32 masters get fp32 gradients, a module
-    after ``.bfloat16()`` gets them in bf16.  The rows themselves and caller-supplied ``vals`` get no gradient there."""
+    after ``.bfloat16()`` gets them in bf16.  The rows themselves and caller-supplied ``vals`` get no gradient there.
+    ``v_w``, ``v_b`` (bf16 rows, no ``vals``): the trainable value layer of a passing_v model.  The forward projects the rows
+    itself (ops.value_proj, bf16 V, saved); the backward asks the bf16 aggregator backward for g_vals and hands them — fp32,
+    as that call wrote them — with the stored bf16 rows and V to ops.value_proj_backward (dsmil_value_backward_bf16: one
+    call over all rows of a batch), whose results come back in those two slots in the parameters' dtype."""
 
     @staticmethod
-    def forward(ctx, feats, c_in, vals, lengths, fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, nonlinear, f32_out=False):
+    def forward(ctx, feats, c_in, vals, lengths, fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, nonlinear, f32_out=False,
+                v_w=None, v_b=None):
         det = lambda t: t.detach() if t is not None else None
         w = _wdict(fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, detach=True)
+        ctx.proj = v_w is not None
+        if ctx.proj:
+            if feats.dtype != torch.bfloat16 or vals is not None or v_b is None:
+                raise ValueError("v_w / v_b: the value layer of bf16-stored rows (no vals); fp32 rows take _ValueProjFunction")
+            ctx.v_dtype = v_w.dtype
+            vals = ops.value_proj(feats.detach(), v_w.detach(), v_b.detach())
         classes, pred, A, B, idx = ops.agg_forward(feats.detach(), [feats.shape[0]] if lengths is None else lengths, w,
                                                    classes_in=det(c_in), vals=det(vals), nonlinear=nonlinear)
         ctx.bf16 = feats.dtype == torch.bfloat16
@@ -504,8 +538,8 @@ class _AggFunction(torch.autograd.Function):
     def backward(ctx, g_cls, g_pred, g_A, g_B, _g_idx):
         if ctx.bf16 and (ctx.needs_input_grad[0] or (ctx.has_vals and ctx.needs_input_grad[2])):
             # (MILNet / BClassifier refuse these at the forward, under grad mode; a direct caller of the Function gets here)
-            raise NotImplementedError("bf16-stored rows: the parameters have a native backward, the rows and the value "
-                                      "layer do not")
+            raise NotImplementedError("bf16-stored rows: the parameters (with v_w / v_b the value layer's too) have a native "
+                                      "backward, the rows and caller-supplied vals do not")
         if ctx.bf16 or ctx.lengths is not None or not ctx.needs_input_grad[0] or _AggFunction._native_accepts(ctx):
             return _AggFunction._backward_native(ctx, g_cls, g_pred, g_A, g_B)
         return _AggFunction._backward_dense(ctx, g_cls, g_pred, g_A, g_B)
@@ -533,13 +567,20 @@ class _AggFunction(torch.autograd.Function):
         # (vals sharing feats' memory IS v = Identity to the kernels: the rows' gradient then already holds A gB)
         same = ctx.has_vals and vals.data_ptr() == feats.data_ptr()
         want_v = ctx.has_vals and ctx.needs_input_grad[2] and not (want_x and same)
+        if ctx.proj:
+            want_v = ctx.needs_input_grad[14] or ctx.needs_input_grad[15]
         kw = dict(g_classes=None if ctx.has_cin else g_cls, g_A=g_A, vals=vals if ctx.has_vals else None,
                   nonlinear=ctx.nonlinear, want_g_vals=want_v, want_g_feats=want_x)
         if ctx.lengths is None:
             g = ops.agg_backward(feats, w, A, B, idx, g_pred, g_B=g_B[0] if g_B is not None else None, **kw)
         else:
             g = ops.agg_backward_bags(feats, ctx.lengths, w, A, B, idx, g_pred, g_B=g_B, **kw)
-        return (g.get("feats"), None, g.get("vals"), None, *_param_grads(g, w), None, None)
+        if ctx.proj:
+            g_v_w = g_v_b = None
+            if want_v:   # g["vals"]: fp32, as the aggregator backward wrote it — one call over all rows of the batch
+                g_v_w, g_v_b = (t.to(ctx.v_dtype) for t in ops.value_proj_backward(feats, vals, g["vals"]))
+            return (None, None, None, None, *_param_grads(g, w), None, None, g_v_w, g_v_b)
+        return (g.get("feats"), None, g.get("vals"), None, *_param_grads(g, w), None, None, None, None)
 
     @staticmethod
     def _backward_dense(ctx, g_cls, g_pred, g_A, g_B):
@@ -601,4 +642,4 @@ class _AggFunction(torch.autograd.Function):
         if ctx.has_vals and ctx.needs_input_grad[2]:
             g_vals = A.mm(gB)
         return (g_x, g_cin, g_vals, None, g_fc_w, g_fc_b, g_q0_w, g_q0_b, g_q2_w, g_q2_b,
-                g_fcc_w, g_fcc_b, None, None)
+                g_fcc_w, g_fcc_b, None, None, None, None)

@@ -407,7 +407,8 @@ def value_proj(feats, v_w, v_b, row_map=None):
     native launch (fp32 in, fp32 out; the weight planes are cut once per weight set).  feats [rows, K] fp32 CUDA, v_w [Kv, K],
     v_b [Kv]; ``row_map`` (int64 [n]): logical row i is physical row row_map[i] of feats.  Returns V [n, Kv] in logical order.
     bf16 ``feats`` select dsmil_value_forward_bf16 (the bf16-storage path: v_w and v_b — fp32 masters or bf16 parameters —
-    are rounded to bf16, fp32 accumulation, one bf16 MFMA product per MAC): bf16 V [rows, Kv], inference only, no row map."""
+    are rounded to bf16, fp32 accumulation, one bf16 MFMA product per MAC): bf16 V [rows, Kv], no row map (its
+    parameter gradients: value_proj_backward on the same bf16 rows)."""
     if feats.dtype == torch.bfloat16:
         if row_map is not None:
             raise ValueError("row_map is implemented for the fp32 path")
@@ -431,10 +432,45 @@ def value_proj(feats, v_w, v_b, row_map=None):
     return V
 
 
+def _value_proj_backward_b16(feats, V, g_vals):
+    """dsmil_value_backward_bf16: bf16 rows [rows, K], bf16 V [rows, Kv], fp32 g_vals -> fp32 (g_v_w, g_v_b), two native
+    launches."""
+    if not (feats.is_cuda and V.is_cuda and g_vals.is_cuda):
+        raise RuntimeError("feats, V and g_vals must be CUDA(HIP) tensors for the native path")
+    if V.dtype != torch.bfloat16 or g_vals.dtype != torch.float32:
+        raise ValueError(f"bf16 rows take a bf16 V and fp32 g_vals, got {V.dtype} / {g_vals.dtype}")
+    if feats.dim() != 2 or V.dim() != 2 or V.shape[0] != feats.shape[0] or g_vals.shape != V.shape:
+        raise ValueError(f"V / g_vals must be [{feats.shape[0]},Kv], got {tuple(V.shape)} / {tuple(g_vals.shape)}")
+    feats = feats if feats.is_contiguous() else feats.contiguous()
+    V = V if V.is_contiguous() else V.contiguous()
+    g_vals = g_vals if g_vals.is_contiguous() else g_vals.contiguous()
+    dev = feats.device
+    n, K = feats.shape
+    Kv = V.shape[1]
+    g_w = torch.empty((Kv, K), dtype=torch.float32, device=dev)
+    g_b = torch.empty((Kv,), dtype=torch.float32, device=dev)
+    if n == 0:
+        return g_w.zero_(), g_b.zero_()
+    L = _native.lib()
+    ws = _workspace(dev, L.dsmil_value_backward_bf16_workspace_bytes(n, K, Kv))
+    with torch.cuda.device(dev):
+        rc = L.dsmil_value_backward_bf16(_ptr(feats), _ptr(V), _ptr(g_vals), n, K, Kv, _ptr(g_w), _ptr(g_b), _ptr(ws),
+                                         ws.numel(), _stream(dev))
+    _native.check(rc, "dsmil_value_backward_bf16")
+    return g_w, g_b
+
+
 def value_proj_backward(feats, V, g_vals, row_map=None):
     """dsmil_value_backward: the PARAMETER gradients of BClassifier.v's Linear behind g_vals (what agg_backward returns as
     ``vals``):  gZ = g_vals * (V > 0),  g_v_w [Kv, K] = gZ^T feats,  g_v_b [Kv] = colsum gZ — deterministic (fixed-order
-    sums).  The gradient of the input rows (gZ v_w) is value_proj_backward_rows.  Returns (g_v_w, g_v_b)."""
+    sums).  The gradient of the input rows (gZ v_w) is value_proj_backward_rows.  Returns (g_v_w, g_v_b).
+    bf16 ``feats`` select dsmil_value_backward_bf16 (the bf16-storage path): V must then be the bf16 V of ``value_proj`` and
+    g_vals fp32 (the bf16 aggregator backward's, unrounded); the operands are read as they are stored — no fp32 copy of
+    either — and the results are fp32; no row map."""
+    if feats.dtype == torch.bfloat16:
+        if row_map is not None:
+            raise ValueError("row_map is implemented for the fp32 path")
+        return _value_proj_backward_b16(feats, V, g_vals)
     feats = _f32c(feats, "feats"); V = _f32c(V, "V"); g_vals = _f32c(g_vals, "g_vals")
     dev = feats.device
     K = feats.shape[1]

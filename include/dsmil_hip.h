@@ -380,7 +380,8 @@ int dsmil_value_backward_rows(const float* feats, const float* V, const float* g
  *     V[n, j] = bf16(max(0, sum_k feats[n, k] w_b[j, k] + v_b[j])),   w_b = bf16(v_w),  round to nearest even both times,
  * bf16 rows in, bf16 rows out, fp32 accumulation: one bf16 MFMA product per MAC (csrc/agg_value.h, k_value_proj_b16).  Every
  * output's sum runs in an order that depends on K alone — not on the row's place in the call or the number of rows — so a
- * row's result has the same bits in any batch.  Inference only (there is no backward for bf16 rows), no row map.
+ * row's result has the same bits in any batch.  No row map.  Its parameter gradients on the same operands are
+ * dsmil_value_backward_bf16 below (the input rows of the bf16 path take no gradient).
  *   v_w [Kv, K] fp32 (rounded inside), v_b [Kv] fp32, read as it is (the caller passes bf16-rounded values there if it wants
  *                        what module.bfloat16() holds, as with every bias of the bf16 path).  K % 8 == 0 and Kv % 4 == 0, else
  *                        DSMIL_E_UNSUPPORTED (dsmil_agg_forward_bf16's own condition on its operands).
@@ -399,6 +400,24 @@ int dsmil_value_pack_bf16(const float* v_w, int32_t K, int32_t Kv, void* packed,
 size_t dsmil_value_workspace_bf16_bytes(int64_t rows, int32_t K, int32_t Kv);
 int dsmil_value_forward_bf16(const void* feats_bf16, int64_t rows, int32_t K, int32_t Kv, const float* v_w, const float* v_b,
                              const void* packed, void* V_out_bf16, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- the value layer's parameter gradients on bf16-stored rows (ABI 6, additive: detected by SYMBOL) ----------------------------
+ * What autograd derives for dsmil.py:35-39 behind g_vals (= dsmil_agg_backward_bags_bf16's g_vals, fp32, unrounded) for the
+ * layer's PARAMETERS, on the operands of the bf16 path as they are stored:
+ *     gZ = V > 0 ? g_vals : 0   (a select on the bf16 V: +0, -0 and NaN mask; a NaN / inf in g_vals at a masked position gives 0),
+ *     g_v_w [Kv, K] = gZ^T feats,   g_v_b [Kv] = column sums of gZ          (both fp32, OVERWRITTEN),
+ * straight-through for the forward's roundings.  feats_bf16 [rows, K] and V_bf16 [rows, Kv] raw bfloat16 (dsmil_value_forward_bf16's
+ * input and output), g_vals [rows, Kv] fp32.  A bf16 row is one exact bf16 MFMA operand: the three exact planes of gZ times the
+ * one plane of feats, all three products kept, fp32 accumulation (csrc/agg_value.h, k_value_tn_b16); gZ and fp32 copies of feats
+ * or V are never written to memory.  Fixed-order two-stage sums, no atomics: two runs give the same bits.  No row map.
+ *   Checks, in this order, all before any launch:  DSMIL_E_INVALID (a NULL operand; rows, K or Kv not positive);
+ *   DSMIL_E_UNSUPPORTED (K % 8 != 0 or Kv % 4 != 0 — dsmil_value_forward_bf16's condition — or a grid beyond 2^31 - 1
+ *   workgroups);  DSMIL_E_ALIGN (feats_bf16 or g_vals not 16-B aligned, V_bf16 not 8-B aligned, ws not 256-B aligned);
+ *   DSMIL_E_WORKSPACE (ws_bytes < dsmil_value_backward_bf16_workspace_bytes(rows, K, Kv); that is 0 for non-positive
+ *   arguments).  Two launches (contraction, reduce).  Never allocates or synchronises: capturable in a graph. */
+size_t dsmil_value_backward_bf16_workspace_bytes(int64_t rows, int32_t K, int32_t Kv);
+int dsmil_value_backward_bf16(const void* feats_bf16, const void* V_bf16, const float* g_vals, int64_t rows, int32_t K, int32_t Kv,
+                              float* g_v_w, float* g_v_b, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- one training step per C call (ABI 3) --------------------------------------------------------
  * Replaces the body of the reference's training loop for one bag, train_tcga.py:60-75 (train_mil.py:44-56 likewise):
