@@ -694,6 +694,29 @@ __global__ __launch_bounds__(F2_THREADS, 1) void k_attend_f2(AttendArgs a, const
     }
 }
 
+// ---- k_attend_f3's fragments (v_mfma_f32_16x16x32_f16; agg_f3.h) in the image below.  A fragment is one 16-unit block
+// ub = 0..7 (wave ub / 2, unit half ub % 2) of one 32-k step; lane (m = lane & 15, g = lane >> 4) holds the eight k-slots
+// 8g .. 8g+7 of the block's row m.  chunk < nk1: GEMM-1 step `chunk` (k = feature index); chunk >= nk1: GEMM-2 step
+// chunk - nk1 (k = hidden unit).  Row m of block ub is unit 32 (ub / 2) + 16 (m / 8) + 8 (ub % 2) + m % 8: with this order of
+// the units the eight hidden units a lane of k_attend_f3 holds for a row, {c + e, c + 8 + e}, e = 0..3, c = 32 wave +
+// 16 (g / 2) + 4 (g % 2), are one 16-byte piece of k_attend_f2's k order, so BOTH weight matrices are read from the image
+// as it is — the same 16 bytes, held by another lane (f3_frag_slot) — and the image has one order.
+struct F3UnitK {
+    int unit, k;
+};
+__host__ __device__ constexpr int f3_unit(int ub, int m) { return 32 * (ub >> 1) + 16 * (m >> 3) + 8 * (ub & 1) + (m & 7); }
+__host__ __device__ constexpr F3UnitK f3_frag_map(int nk1, int chunk, int ub, int lane, int e) {
+    const int m = lane & 15, g = lane >> 4;
+    if (chunk < nk1) return {f3_unit(ub, m), 32 * chunk + 8 * g + e};
+    return {f3_unit(ub, m), 32 * (chunk - nk1) + 16 * (g >> 1) + 4 * (g & 1) + (e & 3) + 8 * (e >> 2)};
+}
+// the 16-byte unit of the image that holds the fragment's lane: 16-k chunk 2 chunk + g / 2, piece (tile ub / 2, plane), lane
+// (l31 = the unit within its tile, hi = g % 2)
+__host__ __device__ constexpr long long f3_frag_slot(int chunk, int ub, int plane, int lane) {
+    const int m = lane & 15, g = lane >> 4;
+    return (long long)(2 * chunk + (g >> 1)) * F2_CHUNK_F4 + ((ub >> 1) * 2 + plane) * 64 + 32 * (g & 1) + (f3_unit(ub, m) & 31);
+}
+
 // fp32 query weights -> two fp16 planes (round to nearest) of the power-of-two scaled values, MFMA-fragment order:
 //   chunk s < nks (GEMM 1):  [t][p][lane (l31,hi)][e] = plane_p(a1 W1[32t + l31][16s + 8hi + e])   (0 past K)
 //   chunk nks + 2t + sx:     [t2][p][lane][e] = plane_p(a2 W2[32t2 + l31][32t + 16sx + (e&3) + 8(e>>2) + 4hi])

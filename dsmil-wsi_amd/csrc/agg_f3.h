@@ -1,5 +1,5 @@
 // agg_f3.h — k_attend_f3: k_attend_f2's arithmetic (fp32 bags, two fp16 planes by round-to-nearest per operand, three plane
-// products on v_mfma_f32_32x32x16_f16, every feature byte read ONCE) with the query weights RESIDENT IN REGISTERS.
+// products, every feature byte read ONCE) with the query weights RESIDENT IN REGISTERS, on v_mfma_f32_16x16x32_f16.
 //
 // Why (round 5, DESIGN.md §3 "what bounds the tile").  k_attend_f2 pulls its weight planes from L2 for every 64-row tile:
 // 320 KB of weights next to 128 KB of features through the CU's 64 B/clk vector L1 — the tile's bound, whatever the grid size
@@ -13,8 +13,11 @@
 //   * tile = 32 rows, TWO plane buffers in LDS (row-major [row][plane][K] fp16 with a 16-B pad: B fragments, the value
 //     sum's k-contiguous reads and the cut's writes are all conflict-free).  While tile t is in GEMM 1, every wave cuts
 //     ITS eight rows of tile t+1 out of a register ring (filled a tile earlier, as k_attend_f2's cutters do) into the other
-//     buffer and refills the ring with tile t+2 — the cut in two-instruction pieces BETWEEN the 96 MFMAs (a wave issues in
+//     buffer and refills the ring with tile t+2 — the cut in two-instruction pieces BETWEEN the 192 MFMAs (a wave issues in
 //     order: a whole group behind three queued MFMAs left the matrix pipe idle), then the plane writes, then the loads;
+//   * the MFMA shape is 16x16x32 (DESIGN.md §3 "f3 on 16x16x32"): per wave four independent 16 x 16 accumulator blocks
+//     (unit half x row block) instead of two alternating 32 x 32 accumulators and their 32 adds per lane and tile; a row
+//     block is every second row of the tile, which keeps the 16-lane groups of ds_read_b128 on distinct banks;
 //   * a workgroup owns a CONTIGUOUS run of tiles (k_attend_bf16_res's scheme): consecutive tiles belong to the same bag, the
 //     softmax reference is a constant of the bag (tanh bounds the queries: |s| <= sum_j |q_max[j]| / sqrt(128) — no tile
 //     maximum, no rescaling), the value sum accumulates ACROSS tiles in eight registers per class (lane = k-octet, wave =
@@ -26,7 +29,7 @@
 // Per-row power-of-two feature scales, the cut, the three products, the packed weight image (k_pack_agg_f2) and the error class
 // are k_attend_f2's (agg_f2.h); so are the tests (tests/test_agg_gpu.py::test_batch_form_*).
 // Only the two-layer query (dsmil.py:31-32 nonlinear, the default) and C <= 2: everything else stays on k_attend_f2.
-// LDS: planes 2 x 32 x (4 K + 16) B (129 KiB at K = 512) | hidden planes 32 x 528 B | 6.3 KiB scratch = 151.8 KiB.
+// LDS: planes 2 x 32 x (4 K + 16) B (129 KiB at K = 512) | hidden planes 32 x 528 B | 7.3 KiB scratch = 152.8 KiB.
 // Barriers per 32-row tile: S (planes of this tile complete, the other buffer and the scratch released), B2 (hidden
 // planes), T1 (partial scores).
 #pragma once
@@ -38,28 +41,30 @@ constexpr int F3_BM = 32;                   // rows per tile
 constexpr int F3_THREADS = 256;             // one wave per SIMD
 constexpr int F3_MAX_WG = 1024;             // (= RS_MAX_WG: the workspace holds that many + n_bags partial slots)
 constexpr int F3_HROW = 528;                // bytes per row of the hidden planes: 2 planes x 256 B + 16 pad
-constexpr int F3_SCR = 1600;                // floats of scratch
+constexpr int F3_SCR = 1856;                // floats of scratch
 __host__ __device__ constexpr int f3_row_bytes(int K) { return 4 * K + 16; }
 __host__ __device__ constexpr int f3_lds_bytes(int K) { return 2 * F3_BM * f3_row_bytes(K) + F3_BM * F3_HROW + F3_SCR * 4; }
 
-// v_mfma_f32_32x32x16_f16 as inline asm (k_attend_bf16_res's recipe, agg_res.h): the A operand in the accumulator file ("a":
+// v_mfma_f32_16x16x32_f16 as inline asm (k_attend_bf16_res's recipe, agg_res.h): the A operand in the accumulator file ("a":
 // the resident W1) or in a VGPR (W2), the accumulator in VGPRs.  With the builtin hipcc put the ACCUMULATORS into the
 // accumulator file, moved W1 fragments out through v_mov copies and — its scheduler in minimum-pressure mode — issued every LDS
-// read right in front of its MFMA (stamps: 5 200 cycles for the 96 MFMAs of a tile).  Inside an asm statement nothing is padded:
-// *0 variants start a chain from the inline constant 0, F3_NOP() stands between the last MFMA and the VALU reads of its result.
-__device__ __forceinline__ void f3_mfma_a(f32x16& acc, const f32x4& a_agpr, const f32x4& b) {
-    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "a"(a_agpr), "v"(b));
+// read right in front of its MFMA.  Inside an asm statement nothing is padded: *0 variants start a chain from the inline
+// constant 0, F3_NOP() stands between the last MFMA and the VALU reads of its result.
+// Fragments: lane (l15 = lane & 15, g = lane >> 4) holds A[row l15][k 8g .. 8g+7], B[k 8g .. 8g+7][col l15] of a 32-k step and
+// D[row 4g + e][col l15], e = 0..3.
+__device__ __forceinline__ void f3_mfma_a(f32x4& acc, const f32x4& a_agpr, const f32x4& b) {
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "a"(a_agpr), "v"(b));
 }
-__device__ __forceinline__ void f3_mfma_a0(f32x16& acc, const f32x4& a_agpr, const f32x4& b) {
-    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(acc) : "a"(a_agpr), "v"(b));
+__device__ __forceinline__ void f3_mfma_a0(f32x4& acc, const f32x4& a_agpr, const f32x4& b) {
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(acc) : "a"(a_agpr), "v"(b));
 }
-__device__ __forceinline__ void f3_mfma_v(f32x16& acc, const f32x4& a, const f32x4& b) {
-    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
+__device__ __forceinline__ void f3_mfma_v(f32x4& acc, const f32x4& a, const f32x4& b) {
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
 }
-__device__ __forceinline__ void f3_mfma_v0(f32x16& acc, const f32x4& a, const f32x4& b) {
-    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(b));
+__device__ __forceinline__ void f3_mfma_v0(f32x4& acc, const f32x4& a, const f32x4& b) {
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(b));
 }
-#define F3_NOP() asm volatile("s_nop 15" ::: "memory")   // 16 states >= the 12 an 8-pass MFMA result needs before a VALU read
+#define F3_NOP() asm volatile("s_nop 15" ::: "memory")   // 16 states: more than a 4-pass MFMA result needs before a VALU read
 
 // f(integral_constant<int, I>) for I = B .. E-1: every index inside the body is a constant expression (register arrays stay
 // registers whatever the optimiser's pass order)
@@ -119,7 +124,7 @@ template <int NK1, bool TWO, int DBG = 0>   // DBG 1 (experiment builds, with DS
 __global__ __launch_bounds__(F3_THREADS, 1) void k_attend_f3(AttendArgs a, const float* __restrict__ rowmax, int tiles_per_bag,
                                                              int n_items, int per_wg) {
     static_assert(NK1 % 4 == 0 && NK1 >= 4 && NK1 <= 16, "K a multiple of 128 up to 512");
-    constexpr int K = 32 * NK1, NKS = 2 * NK1, NG = NK1 / 2;   // 16-k steps of GEMM 1; 64-k groups of the feature ring
+    constexpr int K = 32 * NK1, NKS = 2 * NK1, NG = NK1 / 2;   // NK1 32-k steps of GEMM 1 (NKS 16-k chunks of the image); 64-k groups of the feature ring
     constexpr int RB = f3_row_bytes(K), BUF = F3_BM * RB;
     constexpr int NC = TWO ? 2 : 1;
     constexpr bool W2_STREAM = NK1 > 8;
@@ -130,14 +135,16 @@ __global__ __launch_bounds__(F3_THREADS, 1) void k_attend_f3(AttendArgs a, const
     float* scr = reinterpret_cast<float*>(sH + F3_BM * F3_HROW);
     // (partial results of the two lane halves go to LDS side by side: an exchange between the halves is a ds_bpermute round trip
     // in the middle of a dependent chain, two per tile)
-    float* sS = scr;            // [4 waves][2 halves][2 classes][32 rows] partial scores
-    float* sBias = scr + 768;   // [2][128]: q.0 / q.2 biases
-    float* sPall = scr + 1024;  // [4 waves][2 classes][32 rows]: every wave's private value-sum weights p / row scale
-    float* sInvAll = scr + 1280; // [2 buffers][32 rows]: 1 / row scale of the rows whose planes sit in that buffer
-    float* sQ = scr + 1344;     // [2 classes][128]: critical queries of the current bag
+    float* sS = scr;            // [4 waves][4 lane groups][2 classes][32 rows] partial scores
+    float* sBias = scr + 1024;  // [2][128]: q.0 / q.2 biases
+    float* sPall = scr + 1280;  // [4 waves][2 classes][32 rows]: every wave's private value-sum weights p / row scale
+    float* sInvAll = scr + 1536; // [2 buffers][32 rows]: 1 / row scale of the rows whose planes sit in that buffer
+    float* sQ = scr + 1600;     // [2 classes][128]: critical queries of the current bag
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, hi = lane >> 5;
+    const int l31 = lane & 31, hi = lane >> 5;            // scores, softmax: lane = row
+    const int l15 = lane & 15, g = lane >> 4;             // MFMA fragments
+    const int ubase = 32 * wave + 16 * (g >> 1) + 4 * (g & 1);   // first of the units this lane holds of an accumulator block
     const f32x4* wimg = reinterpret_cast<const f32x4*>(a.wpk);
     const float* trailer = reinterpret_cast<const float*>(wimg + (long long)(NKS + 8) * F2_CHUNK_F4);
     const float* feats = reinterpret_cast<const float*>(a.feats);
@@ -162,20 +169,26 @@ __global__ __launch_bounds__(F3_THREADS, 1) void k_attend_f3(AttendArgs a, const
     // ---- resident weights: this wave's A fragments of every 16-k step, both planes.  W1 is pinned to the accumulator file
     //      (an MFMA may take its A operand from there; the empty asm makes the tuple live there for the whole launch), W2 and
     //      everything the VALU touches stay in VGPRs.
-    F2Frag w1[NKS][2], w2[8][2];
+    //      Fragments are per 16-unit block: [32-k step][unit half uh][plane], gathered from the image's 16-k chunks
+    //      (f3_frag_slot: the same 16 bytes, other lanes; f3_unit: which units a block holds).
+    F2Frag w1[NK1][2][2], w2[4][2][2];
 #pragma unroll
-    for (int s = 0; s < NKS; ++s)
+    for (int s = 0; s < NK1; ++s)
 #pragma unroll
-        for (int p = 0; p < 2; ++p) w1[s][p].f = wimg[(long long)s * F2_CHUNK_F4 + (2 * wave + p) * 64 + lane];
+        for (int uh = 0; uh < 2; ++uh)
+#pragma unroll
+            for (int p = 0; p < 2; ++p) w1[s][uh][p].f = wimg[f3_frag_slot(s, 2 * wave + uh, p, lane)];
     // (W2's second plane is NOT resident at K = 512: 2 x 256 + 64 weight registers left too few for the LDS reads of GEMM 1 to
     // run ahead of their MFMAs — hipcc issued every read right in front of its MFMA.  Its 32 KB per tile come from L2 behind
     // GEMM 1, under the hidden-layer exchange.)
-    const f32x4* w2p1 = wimg + (long long)NKS * F2_CHUNK_F4 + (2 * wave + 1) * 64 + lane;
+    const f32x4* w2p1 = wimg + f3_frag_slot(NK1, 2 * wave, 1, lane);   // + 2 st chunks + 8 uh
 #pragma unroll
-    for (int st = 0; st < 8; ++st) {
-        w2[st][0].f = wimg[(long long)(NKS + st) * F2_CHUNK_F4 + (2 * wave) * 64 + lane];
-        if constexpr (!W2_STREAM) w2[st][1].f = w2p1[(long long)st * F2_CHUNK_F4];
-    }
+    for (int st = 0; st < 4; ++st)
+#pragma unroll
+        for (int uh = 0; uh < 2; ++uh) {
+            w2[st][uh][0].f = wimg[f3_frag_slot(NK1 + st, 2 * wave + uh, 0, lane)];
+            if constexpr (!W2_STREAM) w2[st][uh][1].f = w2p1[(long long)2 * st * F2_CHUNK_F4 + 8 * uh];
+        }
     const float ia1 = trailer[0], ia2 = trailer[1];
     // Bound of a row's hidden layer: relu(W1 x + b)[j] <= ||W1[j]||_1 max|x| + |b[j]|, and max|x| < 2^14 / (row scale).  The
     // hidden planes are scaled by THIS bound (a power of two from it) instead of by the row's true maximum: no exchange of
@@ -187,9 +200,11 @@ __global__ __launch_bounds__(F3_THREADS, 1) void k_attend_f3(AttendArgs a, const
     const float hb_b = wave_max(fmaxf(fabsf(a.q0_b[lane]), fabsf(a.q0_b[lane + 64])));
     sBias[tid] = tid < QD ? a.q0_b[tid] : a.q2_b[tid - QD];
 #pragma unroll
-    for (int s = 0; s < NKS; ++s)                         // (behind ALL the loads: a pin waits for its tuple)
+    for (int s = 0; s < NK1; ++s)                         // (behind ALL the loads: a pin waits for its tuple)
 #pragma unroll
-        for (int p = 0; p < 2; ++p) asm volatile("" : "+a"(w1[s][p].f));
+        for (int uh = 0; uh < 2; ++uh)
+#pragma unroll
+            for (int p = 0; p < 2; ++p) asm volatile("" : "+a"(w1[s][uh][p].f));
 
     // ---- the feature stream of this wave: rows 8 wave .. 8 wave + 7 of every tile; lane (rr = lane & 7, o = lane >> 3) holds
     //      the k-octet o of every 64-k group of row 8 wave + rr
@@ -235,11 +250,13 @@ __global__ __launch_bounds__(F3_THREADS, 1) void k_attend_f3(AttendArgs a, const
 
     // the same cut in pieces that fit into the gaps between the MFMAs of GEMM 1 (a wave issues in order: a 16-instruction cut
     // behind three queued MFMAs leaves the matrix pipe idle — stamps: 250 cycles per group, 2 000 per tile; four v_fma_mix
-    // per gap still 150 per group): two v_fma_mix per gap, then the two plane writes, then the refill
+    // per gap still 150 per group): two v_fma_mix per gap (a 16x16x32 MFMA holds the vector issue for 8 of its 16 cycles: two
+    // 4-cycle instructions fill the rest), then the two plane writes, then the refill.  Of a step's twelve gaps the first four
+    // carry the LDS reads of the next step's B fragments, the other eight a piece each.
     F2Frag cutf[2];
-    auto cut_piece = [&](int pb, auto s_c, auto j_c, float sc, const float* refill_src) {   // behind MFMA j of step s
+    auto cut_piece = [&](int pb, auto s_c, auto j_c, float sc, const float* refill_src) {   // piece j (0..7) of step s
         constexpr int s_ = decltype(s_c)::value, j = decltype(j_c)::value;
-        constexpr int c = s_ / 4, ph = (s_ % 4) * 3 + j;  // group c owns the twelve gaps of steps 4c .. 4c+3
+        constexpr int c = s_ / 2, ph = (s_ % 2) * 8 + j;  // group c owns the sixteen piece gaps of steps 2c, 2c+1 (eleven used)
         if constexpr (c < NG) {
             char* d = cut_dst + pb * BUF + 128 * c;
             if constexpr (ph < 8) {                       // pair ph / 2: its first plane (even ph), its second (odd ph) — two v_fma_mix per gap
@@ -342,126 +359,136 @@ __global__ __launch_bounds__(F3_THREADS, 1) void k_attend_f3(AttendArgs a, const
         row_raw(n3, rm_n3, phys_n3, log_n3);                    // (unconditional: no tile behind -> a harmless re-read of nn's rows)
         __syncthreads();                                  // S
         STAMP(1);
-        const char* xb_ = sX + buf * BUF + l31 * RB + 16 * hi;
+        // (rows: lane l15 of row block rh holds row 2 l15 + rh.  ds_read_b128 is served in groups of 16 lanes that mix two lane
+        // groups g — {0-3, 12-15, 20-27}, ... — and the row pitch is 4 banks past a multiple of 64: with rows 16 rh + l15 lanes
+        // 12 and 27 of such a group meet on one bank (counters: 34 % of the LDS cycles were conflicts), with every second row
+        // per block one g takes the even and the other the odd 16-byte columns)
+        const char* xb_ = sX + buf * BUF + (2 * l15) * RB + 16 * g;
         const float* sInv = sInvAll + buf * F3_BM;
-        // ---- GEMM 1: H^T[j][n] += W1[j][k] x[n][k], j = this wave's 32 units, n = the 32 rows; Behind every fourth step: one 64-k group of the NEXT tile is cut
-        //      into the other buffer and its ring slot refilled with the tile after next.
-        // (two accumulators taken in turn by consecutive MFMAs: back to back on ONE accumulator a 32x32x16 MFMA issues every
-        // ~60 cycles instead of 32 — stamps: 5 964 cycles for the 96 MFMAs of a tile)
-        f32x16 Hacc[2];
+        // ---- GEMM 1: H^T[j][n] += W1[j][k] x[n][k], j = this wave's 32 units (two halves uh), n = the 32 rows (two blocks rh: the even and the odd rows):
+        //      four independent 16x16 accumulator blocks, twelve MFMAs per 32-k step.  Every accumulator takes its three plane
+        //      products of a step in one fixed order (smallest first), the steps in k order.  Behind every second step one 64-k
+        //      group of the NEXT tile is cut into the other buffer and its ring slot refilled with the tile after next.
+        f32x4 Hacc[2][2];                                 // [uh][rh]: lane holds units ubase + 8 uh + e of row 2 l15 + rh
         {
-            F2Frag xs[3][2];                              // B fragments, read two steps ahead of their MFMAs (order pinned below)
-            auto rd = [&](int s_, F2Frag (&d)[2]) {
-                d[0].f = *reinterpret_cast<const f32x4*>(xb_ + 32 * s_);
-                d[1].f = *reinterpret_cast<const f32x4*>(xb_ + 2 * K + 32 * s_);
+            F2Frag xs[2][2][2];                           // B fragments [slot][rh][plane], read a step (192 cycles) ahead of their MFMAs
+            auto rd = [&](int s_, int rh, int p, F2Frag& d) {
+                d.f = *reinterpret_cast<const f32x4*>(xb_ + rh * RB + p * (2 * K) + 64 * s_);
             };
-            rd(0, xs[0]);
-            rd(1, xs[1]);
-            f3_static_for<0, NKS>([&](auto s_c) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) rd(0, q >> 1, q & 1, xs[0][q >> 1][q & 1]);
+            f3_static_for<0, NK1>([&](auto s_c) {
                 constexpr int s = decltype(s_c)::value;
-                using J0 = std::integral_constant<int, 0>;
-                using J1 = std::integral_constant<int, 1>;
-                using J2 = std::integral_constant<int, 2>;
-                if constexpr (DBG != 3 && DBG != 5 && s + 2 < NKS) rd(s + 2, xs[(s + 2) % 3]);   // (DBG 3: timing without the LDS reads of GEMM 1)
+                f3_static_for<0, 12>([&](auto j_c) {
+                    constexpr int j = decltype(j_c)::value;
+                    constexpr int pr = j / 4, uh = (j >> 1) & 1, rh = j & 1;   // product: W1 plane 1 x plane 0, 0 x 1, 0 x 0
+                    constexpr int pa = pr == 0 ? 1 : 0, pb = pr == 1 ? 1 : 0;
+                    __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (s == 0 && pr == 0) f3_mfma_a0(Hacc[uh][rh], w1[s][uh][pa].f, xs[s % 2][rh][pb].f);
+                    else f3_mfma_a(Hacc[uh][rh], w1[s][uh][pa].f, xs[s % 2][rh][pb].f);
+                    if constexpr (j < 4) {                // (DBG 3: timing without the LDS reads of GEMM 1)
+                        if constexpr (DBG != 3 && DBG != 5 && s + 1 < NK1) rd(s + 1, j >> 1, j & 1, xs[(s + 1) % 2][j >> 1][j & 1]);
+                    } else if constexpr (DBG != 2 && DBG != 5) {   // (DBG 2: timing without the cut of the next tile)
+                        cut_piece(buf ^ 1, s_c, std::integral_constant<int, j - 4>{}, sc_n, src_nn);
+                    }
+                });
                 __builtin_amdgcn_sched_barrier(0);
-                // (two accumulators taken in turn: back to back on ONE accumulator the MFMAs issue every ~60 cycles instead of 32)
-                if constexpr (s == 0) f3_mfma_a0(Hacc[0], w1[s][1].f, xs[s % 3][0].f);
-                else f3_mfma_a(Hacc[s & 1], w1[s][1].f, xs[s % 3][0].f);
-                if constexpr (DBG != 2 && DBG != 5) cut_piece(buf ^ 1, s_c, J0{}, sc_n, src_nn);   // (DBG 2: timing without the cut of the next tile)
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (s == 0) f3_mfma_a0(Hacc[1], w1[s][0].f, xs[s % 3][1].f);
-                else f3_mfma_a(Hacc[~s & 1], w1[s][0].f, xs[s % 3][1].f);
-                if constexpr (DBG != 2 && DBG != 5) cut_piece(buf ^ 1, s_c, J1{}, sc_n, src_nn);
-                __builtin_amdgcn_sched_barrier(0);
-                f3_mfma_a(Hacc[s & 1], w1[s][0].f, xs[s % 3][0].f);
-                if constexpr (DBG != 2 && DBG != 5) cut_piece(buf ^ 1, s_c, J2{}, sc_n, src_nn);
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (s == 7) STAMP(10);
-                if constexpr (s == 15) STAMP(11);
-                if constexpr (s == 23) STAMP(12);
+                if constexpr (s == 3) STAMP(10);
+                if constexpr (s == 7) STAMP(11);
+                if constexpr (s == 11) STAMP(12);
             });
             F3_NOP();
         }
         if (o == 0) sInvAll[(buf ^ 1) * F3_BM + myrow] = sinv_n;
         if constexpr (W2_STREAM) {
 #pragma unroll
-            for (int st = 0; st < 8; ++st) w2[st][1].f = *(const DSMIL_GLOBAL f32x4*)(w2p1 + (long long)st * F2_CHUNK_F4);
+            for (int st = 0; st < 4; ++st)
+#pragma unroll
+                for (int uh = 0; uh < 2; ++uh) w2[st][uh][1].f = *(const DSMIL_GLOBAL f32x4*)(w2p1 + (long long)2 * st * F2_CHUNK_F4 + 8 * uh);
         }
         STAMP(2);
-        // ---- un-scale, bias, ReLU: reg 4q+e <-> unit 32 wave + 8q + 4hi + e, row l31
-        const float rinv1 = sInv[l31];
-        const float iv1 = ia1 * rinv1;
-        f32x16 H;
+        // ---- un-scale, bias, ReLU: Hacc[uh][rh][e] <-> unit ubase + 8 uh + e (f3_unit of block row 4 g + e), row 2 l15 + rh
+        const float rinv1[2] = {sInv[2 * l15], sInv[2 * l15 + 1]};
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 bq = *reinterpret_cast<const f32x4*>(sBias + 32 * wave + 8 * q + 4 * hi);
+        for (int uh = 0; uh < 2; ++uh) {
+            const f32x4 bq = *reinterpret_cast<const f32x4*>(sBias + ubase + 8 * uh);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) H[4 * q + e] = fmaxf(fmaf(Hacc[0][4 * q + e] + Hacc[1][4 * q + e], iv1, bq[e]), 0.f);
+            for (int rh = 0; rh < 2; ++rh) {
+                const float iv1 = ia1 * rinv1[rh];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) Hacc[uh][rh][e] = fmaxf(fmaf(Hacc[uh][rh][e], iv1, bq[e]), 0.f);
+            }
         }
         STAMP(3);
-        float hsc, hinv;
-        hsc = f2_scale(fmaf(hb_n1, rinv1, hb_b), hinv);
-        // registers 8sx .. 8sx+7 are, for row l31, the 8 hidden units of GEMM-2 step 2 wave + sx (the k permutation the packed
-        // W2 carries): scale, cut, publish
+        // a lane's eight hidden units of a row, {ubase + e, ubase + 8 + e}, are the k-slots 8 g .. 8 g + 7 of GEMM-2 step `wave`
+        // (the k permutation the packed W2 carries: f3_frag_map): scale, cut, publish one 16-byte piece per plane and row
+        float hinv[2];
 #pragma unroll
-        for (int sx = 0; sx < 2; ++sx) {
-            const f32x4 h0 = {H[8 * sx], H[8 * sx + 1], H[8 * sx + 2], H[8 * sx + 3]};
-            const f32x4 h1 = {H[8 * sx + 4], H[8 * sx + 5], H[8 * sx + 6], H[8 * sx + 7]};
+        for (int rh = 0; rh < 2; ++rh) {
+            const float hsc = f2_scale(fmaf(hb_n1, rinv1[rh], hb_b), hinv[rh]);
             F2Frag f[2];
-            split2h_scaled(h0, h1, hsc, f);
-            char* d = sH + l31 * F3_HROW + ((2 * wave + sx) * 2 + hi) * 16;
+            split2h_scaled(Hacc[0][rh], Hacc[1][rh], hsc, f);
+            char* d = sH + (2 * l15 + rh) * F3_HROW + 64 * wave + 16 * g;
             *reinterpret_cast<f32x4*>(d) = f[0].f;
             *reinterpret_cast<f32x4*>(d + 256) = f[1].f;
         }
         __syncthreads();                                  // B2
         STAMP(4);
-        f32x16 Qacc[2];
+        // ---- GEMM 2: four 32-k steps (step st contracts wave st's hidden units), the same four blocks and product order
+        f32x4 Qacc[2][2];
         {
-            const char* hb_ = sH + l31 * F3_HROW + 16 * hi;
-            F2Frag hs[3][2];
-            auto rdh = [&](int st_, F2Frag (&d)[2]) {
-                d[0].f = *reinterpret_cast<const f32x4*>(hb_ + 32 * st_);
-                d[1].f = *reinterpret_cast<const f32x4*>(hb_ + 256 + 32 * st_);
+            const char* hb_ = sH + (2 * l15) * F3_HROW + 16 * g;
+            F2Frag hs[2][2][2];                           // a step ahead, as GEMM 1's
+            auto rdh = [&](int st_, F2Frag (&d)[2][2]) {
+#pragma unroll
+                for (int rh = 0; rh < 2; ++rh)
+#pragma unroll
+                    for (int p = 0; p < 2; ++p) d[rh][p].f = *reinterpret_cast<const f32x4*>(hb_ + rh * F3_HROW + 256 * p + 64 * st_);
             };
             rdh(0, hs[0]);
-            rdh(1, hs[1]);
-#pragma unroll
-            for (int st = 0; st < 8; ++st) {
-                if (st + 2 < 8) rdh(st + 2, hs[(st + 2) % 3]);
+            f3_static_for<0, 4>([&](auto st_c) {
+                constexpr int st = decltype(st_c)::value;
+                if constexpr (st + 1 < 4) rdh(st + 1, hs[(st + 1) % 2]);
+                f3_static_for<0, 12>([&](auto j_c) {
+                    constexpr int j = decltype(j_c)::value;
+                    constexpr int pr = j / 4, uh = (j >> 1) & 1, rh = j & 1;
+                    constexpr int pa = pr == 0 ? 1 : 0, pb = pr == 1 ? 1 : 0;
+                    __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (st == 0 && pr == 0) f3_mfma_v0(Qacc[uh][rh], w2[st][uh][pa].f, hs[st % 2][rh][pb].f);
+                    else f3_mfma_v(Qacc[uh][rh], w2[st][uh][pa].f, hs[st % 2][rh][pb].f);
+                    // (the last NMOVE ring groups are refilled here, 96 cycles of MFMAs apart)
+                    if constexpr (DBG != 4 && st == 0 && j % 6 == 5 && j / 6 < NMOVE) fill(src_nn, NG - NMOVE + j / 6);
+                });
                 __builtin_amdgcn_sched_barrier(0);
-                if (st == 0) {
-                    f3_mfma_v0(Qacc[0], w2[st][1].f, hs[st % 3][0].f);
-                    f3_mfma_v0(Qacc[1], w2[st][0].f, hs[st % 3][1].f);
-                } else {
-                    f3_mfma_v(Qacc[st & 1], w2[st][1].f, hs[st % 3][0].f);
-                    f3_mfma_v(Qacc[~st & 1], w2[st][0].f, hs[st % 3][1].f);
-                }
-                f3_mfma_v(Qacc[st & 1], w2[st][0].f, hs[st % 3][0].f);
-                if (DBG != 4 && st < NMOVE) fill(src_nn, NG - NMOVE + st);
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            });
             F3_NOP();
         }
         STAMP(5);
-        // ---- tanh; partial scores over this wave's 32 query units (dsmil.py:55-56)
+        // ---- tanh; partial scores over this lane's eight query units of each of its two rows (dsmil.py:55-56)
         {
-            const float iv2 = ia2 * hinv;
-            float s0 = 0.f, s1 = 0.f;
+            float s0[2] = {0.f, 0.f}, s1[2] = {0.f, 0.f};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const f32x4 bq = *reinterpret_cast<const f32x4*>(sBias + QD + 32 * wave + 8 * q + 4 * hi);
-                const f32x4 u0 = *reinterpret_cast<const f32x4*>(sQ + 32 * wave + 8 * q + 4 * hi);
+            for (int uh = 0; uh < 2; ++uh) {
+                const f32x4 bq = *reinterpret_cast<const f32x4*>(sBias + QD + ubase + 8 * uh);
+                const f32x4 u0 = *reinterpret_cast<const f32x4*>(sQ + ubase + 8 * uh);
                 f32x4 u1 = u0;
-                if constexpr (TWO) u1 = *reinterpret_cast<const f32x4*>(sQ + QD + 32 * wave + 8 * q + 4 * hi);
+                if constexpr (TWO) u1 = *reinterpret_cast<const f32x4*>(sQ + QD + ubase + 8 * uh);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float qv = fast_tanh(fmaf(Qacc[0][4 * q + e] + Qacc[1][4 * q + e], iv2, bq[e]));
-                    s0 = fmaf(qv, u0[e], s0);
-                    if constexpr (TWO) s1 = fmaf(qv, u1[e], s1);
+                for (int rh = 0; rh < 2; ++rh) {
+                    const float iv2 = ia2 * hinv[rh];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float qv = fast_tanh(fmaf(Qacc[uh][rh][e], iv2, bq[e]));
+                        s0[rh] = fmaf(qv, u0[e], s0[rh]);
+                        if constexpr (TWO) s1[rh] = fmaf(qv, u1[e], s1[rh]);
+                    }
                 }
             }
-            sS[((wave * 2 + hi) * 2 + 0) * F3_BM + l31] = s0;
-            if constexpr (TWO) sS[((wave * 2 + hi) * 2 + 1) * F3_BM + l31] = s1;
+#pragma unroll
+            for (int rh = 0; rh < 2; ++rh) {
+                sS[((wave * 4 + g) * 2 + 0) * F3_BM + 2 * l15 + rh] = s0[rh];
+                if constexpr (TWO) sS[((wave * 4 + g) * 2 + 1) * F3_BM + 2 * l15 + rh] = s1[rh];
+            }
         }
         STAMP(6);
         __syncthreads();                                  // T1
@@ -474,8 +501,9 @@ __global__ __launch_bounds__(F3_THREADS, 1) void k_attend_f3(AttendArgs a, const
             const float rinv = sInv[l31];
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-                auto part = [&](int i) { return sS[(i * 2 + c) * F3_BM + l31]; };   // i = 2 wave + half: a fixed order
-                const float s = (((part(0) + part(1)) + (part(2) + part(3))) + ((part(4) + part(5)) + (part(6) + part(7)))) * scale;
+                auto part = [&](int i) { return sS[(i * 2 + c) * F3_BM + l31]; };   // i = 4 wave + lane group: a fixed order
+                auto quad = [&](int i) { return (part(i) + part(i + 1)) + (part(i + 2) + part(i + 3)); };
+                const float s = ((quad(0) + quad(4)) + (quad(8) + quad(12))) * scale;
                 const float p = valid ? expf(s - m_bag[c]) : 0.f;
                 if (hi == 0) l_run[c] += p;
                 if (DBG == 0 && wave == 0 && hi == 0 && valid) a.scores[(cur.off0 + grow) * (long long)a.C + c] = s;
