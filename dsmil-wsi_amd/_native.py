@@ -237,6 +237,17 @@ SIGNATURES = {
     "dsmil_agg_train_step": (ctypes.c_int, [c_f32p, ctypes.c_int64, c_i64p, c_f32p, ctypes.POINTER(AggParams),
                                             ctypes.POINTER(AdamState), c_f32p, ctypes.c_void_p, ctypes.c_size_t,
                                             ctypes.c_void_p]),
+    "dsmil_agg_train_step_bags_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                                                    ctypes.c_int32, ctypes.c_int32]),
+    "dsmil_agg_train_step_bags": (ctypes.c_int, [c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, c_i64p,
+                                                 c_f32p, ctypes.POINTER(AggParams), ctypes.POINTER(AdamState), c_f32p,
+                                                 c_f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "dsmil_agg_train_step_bags_bf16_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                                                         ctypes.c_int32, ctypes.c_int32]),
+    "dsmil_agg_train_step_bags_bf16": (ctypes.c_int, [ctypes.c_void_p, c_i64p, ctypes.c_int32, ctypes.c_int64,
+                                                      ctypes.c_int64, c_f32p, ctypes.POINTER(AggParams),
+                                                      ctypes.POINTER(AdamState), c_f32p, c_f32p, ctypes.c_void_p,
+                                                      ctypes.c_size_t, ctypes.c_void_p]),
     "dsmil_adam_step": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
                                        ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
                                        ctypes.POINTER(ctypes.c_int64), ctypes.c_int64, ctypes.c_double, ctypes.c_double,

@@ -1662,6 +1662,34 @@ int dsmil_agg_train_step(const float* feats, int64_t N, const int64_t* row_map, 
                              bw8, L.bwd_bytes, stream, nullptr, qmax, true, &lh, &af, (unfuse & 2) != 0);
 }
 
+// ---- one optimiser step on a BATCH of bags per call (agg_bwd_bags.h: agg_train_step_bags_impl) ----
+size_t dsmil_agg_train_step_bags_workspace_bytes(int32_t n_bags, int64_t total_rows, int32_t K, int32_t C, int32_t nonlinear) {
+    if (n_bags <= 0 || total_rows < n_bags || K <= 0 || C <= 0) return 0;
+    return step_bags_layout(n_bags, total_rows, K, C, nonlinear, false).total;
+}
+
+int dsmil_agg_train_step_bags(const float* feats, const int64_t* offsets, int32_t n_bags, int64_t total_rows, int64_t max_rows,
+                              const int64_t* row_map, const float* labels, const dsmil_agg_params* p,
+                              const dsmil_adam_state* opt, float* loss_each, float* loss, void* ws, size_t ws_bytes,
+                              void* stream) {
+    return agg_train_step_bags_impl<float>(feats, offsets, n_bags, total_rows, max_rows, row_map, labels, p, opt, loss_each, loss,
+                                           ws, ws_bytes, stream);
+}
+
+size_t dsmil_agg_train_step_bags_bf16_workspace_bytes(int32_t n_bags, int64_t total_rows, int32_t K, int32_t C,
+                                                      int32_t nonlinear) {
+    if (n_bags <= 0 || total_rows < n_bags || K <= 0 || C <= 0 || K % 8) return 0;
+    return step_bags_layout(n_bags, total_rows, K, C, nonlinear, true).total;
+}
+
+int dsmil_agg_train_step_bags_bf16(const void* feats_bf16, const int64_t* offsets, int32_t n_bags, int64_t total_rows,
+                                   int64_t max_rows, const float* labels, const dsmil_agg_params* p,
+                                   const dsmil_adam_state* opt, float* loss_each, float* loss, void* ws, size_t ws_bytes,
+                                   void* stream) {
+    return agg_train_step_bags_impl<bf16_t>((const bf16_t*)feats_bf16, offsets, n_bags, total_rows, max_rows, nullptr, labels, p,
+                                            opt, loss_each, loss, ws, ws_bytes, stream);
+}
+
 // ---- the value stream's parameter gradients (agg_value.h): what autograd derives for dsmil.py:39 behind g_vals ----
 size_t dsmil_value_workspace_bytes(int64_t rows, int32_t K, int32_t Kv) {
     if (rows <= 0 || K <= 0 || Kv <= 0) return 0;

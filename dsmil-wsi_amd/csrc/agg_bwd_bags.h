@@ -26,6 +26,10 @@
 // Tile regime (from total_rows alone, so that it is the one-bag rule at n_bags = 1): total_rows / 128 >= 512 -> the four-wave
 // 128-row tile (k_bwd_rows<4,*>, k_bwd_gh<4>); fewer rows -> the hidden-split 64-row tile (k_bwd_rows_hs, k_bwd_gh_hs), or
 // the one-wave register-staged tile when the rows are not 16-B aligned (K % 4 != 0).  n_bags only adds idle slots.
+//
+// dsmil_agg_train_step_bags / dsmil_agg_train_step_bags_bf16 (the end of this file) chain the batched forward, the mean
+// objective (k_loss_head_bags_mean) and this backward with Adam applied by its last two launches (k_bwd_reduce's AdamFuse,
+// the same hook in k_bags_head): one C call per minibatch step; on bf16 rows k_round_bf16 rebuilds the rounded weight set.
 #pragma once
 
 namespace {
@@ -128,6 +132,7 @@ struct BagsHeadArgs {
     float* g_fc_w; float* g_fc_b;
     const float* g_pred; const float* Bm; float* g_fcc_w; float* g_fcc_b;
     int n_bags, K, Kv, C, accumulate;
+    AdamFuse af;   // dsmil_agg_train_step_bags: the update of fc_w, fc_b, fcc_w, fcc_b (tensors 0, 1, 6, 7) by the thread that sums the element
 };
 template <typename XT = float>
 __global__ __launch_bounds__(256) void k_bags_head(BagsHeadArgs a) {
@@ -145,11 +150,13 @@ __global__ __launch_bounds__(256) void k_bags_head(BagsHeadArgs a) {
                 g += a.g_max[(long long)b * C + c] * load1<XT>(feats, phys_row(a.rowmap, row) * (long long)a.K + k);
             }
             a.g_fc_w[i] = g;
+            if (a.af.on) adam_elem(a.af.p[0] + i, a.af.m[0] + i, a.af.v[0] + i, g, a.af.h);
         } else {
             const int c = (int)(i - (long long)C * a.K);
             float g = a.accumulate ? a.g_fc_b[c] + a.g_max[c] : a.g_max[c];
             for (int b = 1; b < a.n_bags; ++b) g += a.g_max[(long long)b * C + c];
             a.g_fc_b[c] = g;
+            if (a.af.on) adam_elem(a.af.p[1] + c, a.af.m[1] + c, a.af.v[1] + c, g, a.af.h);
         }
         return;
     }
@@ -161,6 +168,7 @@ __global__ __launch_bounds__(256) void k_bags_head(BagsHeadArgs a) {
         float g = a.g_pred[o] * a.Bm[e];
         for (int b = 1; b < a.n_bags; ++b) g += a.g_pred[(long long)b * C + o] * a.Bm[(long long)b * ck + e];
         a.g_fcc_w[i] = g;
+        if (a.af.on) adam_elem(a.af.p[6] + i, a.af.m[6] + i, a.af.v[6] + i, g, a.af.h);
         return;
     }
     i -= nw;
@@ -168,6 +176,7 @@ __global__ __launch_bounds__(256) void k_bags_head(BagsHeadArgs a) {
         float g = a.g_pred[i];
         for (int b = 1; b < a.n_bags; ++b) g += a.g_pred[(long long)b * C + i];
         a.g_fcc_b[i] = g;
+        if (a.af.on) adam_elem(a.af.p[7] + i, a.af.m[7] + i, a.af.v[7] + i, g, a.af.h);
     }
 }
 
@@ -216,6 +225,61 @@ __global__ __launch_bounds__(64) void k_loss_head_bags(const float* __restrict__
     if (threadIdx.x == 0) loss[b] = l;
 }
 
+// dsmil_agg_train_step_bags: k_loss_head_bags for the MEAN objective of the batch, in one launch of ONE workgroup (its 16
+// waves take the bags in turn, so no hand-off between workgroups is needed for the batch loss):
+//   loss_each[b]             the bag's own loss                  — k_loss_head_bags' value
+//   g_pred, g_max [b,c]      k_loss_head_bags' value times `scale` = 1.0f / n_bags (formed on the host in fp32): the separate
+//                            fp32 product MILNet.batch_loss's backward forms (g * (g_loss / n), g_loss = 1), so the batched
+//                            backward is handed the same bits by either path.  The value is rounded by the division before
+//                            the product and nothing is added behind it: there is nothing to contract.
+//   loss[0]                  the mean: the fp32 sum of loss_each in bag order, divided by n_bags (torch.mean may sum in
+//                            another order: the two agree to rounding, not to the bit)
+__global__ __launch_bounds__(1024) void k_loss_head_bags_mean(const float* __restrict__ classes, const int64_t* __restrict__ offsets,
+                                                              const float* __restrict__ pred, const int64_t* __restrict__ idx,
+                                                              const float* __restrict__ label, int n_bags, int C, float scale,
+                                                              float* __restrict__ loss_each, float* __restrict__ loss,
+                                                              float* __restrict__ g_pred, float* __restrict__ g_max) {
+    const int c = threadIdx.x & 63;
+    for (int b = threadIdx.x >> 6; b < n_bags; b += 16) {
+        const long long bc = (long long)b * C + c;
+        float l = 0.f;
+        if (c < C) {
+            const float y = label[bc];
+            const float zb = pred[bc], zm = classes[((long long)offsets[b] + (long long)idx[bc]) * C + c];
+            const float lb = fmaxf(zb, 0.f) - zb * y + log1pf(expf(-fabsf(zb)));
+            const float lm = fmaxf(zm, 0.f) - zm * y + log1pf(expf(-fabsf(zm)));
+            l = 0.5f * (lb + lm) / (float)C;
+            const float sb = 1.f / (1.f + expf(-zb)), sm = 1.f / (1.f + expf(-zm));
+            const float gp = 0.5f * (sb - y) / (float)C, gm = 0.5f * (sm - y) / (float)C;
+            g_pred[bc] = gp * scale;
+            g_max[bc] = gm * scale;
+        }
+        l = wave_sum(l);   // C <= 64: one wave
+        if (c == 0) loss_each[b] = l;
+    }
+    __syncthreads();       // the workgroup's own stores to loss_each are out behind the barrier ...
+    if (threadIdx.x == 0) {
+        const volatile float* le = loss_each;   // ... and read back by vector loads (never through the scalar cache)
+        float s = 0.f;
+        for (int b = 0; b < n_bags; ++b) s += le[b];
+        *loss = s / (float)n_bags;
+    }
+}
+
+// dsmil_agg_train_step_bags_bf16: the eight parameter tensors rounded to bf16 (round to nearest even) and kept as fp32 —
+// what ops._bf16_params holds per weight set, rebuilt here from the fp32 masters at the head of every step
+struct RoundTensors { const float* src[8]; float* dst[8]; long long end[8]; };
+__global__ __launch_bounds__(256) void k_round_bf16(RoundTensors t) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= t.end[7]) return;
+    int k = 0;
+#pragma unroll
+    for (int j = 0; j < 7; ++j)
+        if (i >= t.end[j]) k = j + 1;
+    const long long o = i - (k ? t.end[k - 1] : 0);
+    t.dst[k][o] = bf2f(f2bf(t.src[k][o]));
+}
+
 // workspace: the one-bag layout over total_rows with one gB / D / q_max / g_q set per bag, the idle tile slots in gqp,
 // and the row -> bag table
 struct BagsWs {
@@ -262,8 +326,9 @@ int agg_backward_bags_impl(const XT* feats, const XT* vals, const int64_t* offse
                            int64_t max_rows, const dsmil_agg_params* p, const float* A, const float* Bm, const int64_t* idx,
                            const float* g_classes, const float* g_max, const float* g_pred, const float* g_A,
                            const float* g_B, const dsmil_agg_grads* g, float* g_vals, const int64_t* rowmap, void* ws,
-                           size_t ws_bytes, void* stream, float* g_feats) {
+                           size_t ws_bytes, void* stream, float* g_feats, const AdamFuse* adam = nullptr) {
     // the checks of agg_backward_impl, in its order
+    if (adam && (!g_max || g_classes || g_vals || g_feats)) return DSMIL_E_INVALID;   // the fused optimizer step is the training loop's
     if (!feats || !offsets || !p || !A || !Bm || !idx || !g_pred || !g || !ws) return DSMIL_E_INVALID;
     if (g_max && (!g->fc_w || !g->fc_b)) return DSMIL_E_INVALID;
     if (n_bags < 1 || T < n_bags || max_rows < 1 || max_rows > T || p->K <= 0 || p->Kv <= 0 || p->C <= 0) return DSMIL_E_INVALID;
@@ -380,11 +445,23 @@ int agg_backward_bags_impl(const XT* feats, const XT* vals, const int64_t* offse
     ra.part0 = part0; ra.part1 = part1; ra.pb0 = pb0; ra.pb1 = pb1;
     ra.g_w0 = g->q0_w; ra.g_b0 = g->q0_b; ra.g_w1 = g->q2_w; ra.g_b1 = g->q2_b;
     ra.S = L.S; ra.K = K; ra.nonlinear = p->nonlinear; ra.C = C;
+    // `adam` (dsmil_agg_train_step_bags): optimizer.step() where the gradient elements are formed, every thread on its own
+    // element.  Each parameter tensor's LAST READER is an earlier launch than its updater:
+    //   q0_w, q2_w   forward (their cut image), k_train_prologue, k_bags_qrow            -> updated by k_bwd_reduce
+    //   q0_b, q2_b   forward, k_bags_qrow, k_bwd_rows / k_bwd_rows_hs (launch 4)          -> updated by k_bwd_reduce
+    //                (k_bwd_gh reads the zero bias and W2^T's planes, k_tn_split no parameter at all)
+    //   fcc_w        forward (k_finish), k_bags_prep;   fcc_b: forward (k_pred)            -> updated by k_bags_head
+    //   fc_w, fc_b   forward (the logits pass)                                            -> updated by k_bags_head
+    // k_bags_head itself reads the rows, offsets, idx, g_max, g_pred and B only, and with `adam` no launch follows it.  On
+    // bf16 rows every reader above reads the ROUNDED set of the step's workspace; the fp32 masters are read by the step's
+    // first launch (k_round_bf16) and written here.
+    if (adam) { ra.af = *adam; ra.af.g_fcc_w = nullptr; ra.af.g_fcc_b = nullptr; ra.af.n_fcc_w = 0; ra.af.n_fcc_b = 0; }
     const long long nred = (long long)QD * K + (p->nonlinear ? QD * QD + 2 * QD : QD);
     hipLaunchKernelGGL(k_bwd_reduce, dim3((unsigned)((nred + 255) / 256)), dim3(256), 0, st, ra);
     // the sums over the bags: bag head and the sparse FCLayer term
     BagsHeadArgs ha{feats, offsets, idx, g_max, rowmap, g->fc_w, g->fc_b, g_pred, Bm, g->fcc_w, g->fcc_b, n_bags, K, Kv, C,
-                    g_classes ? 1 : 0};
+                    g_classes ? 1 : 0, AdamFuse{}};
+    if (adam) ha.af = *adam;
     const long long nhead = (g_max ? (long long)C * K + C : 0) + (long long)C * C * Kv + C;
     hipLaunchKernelGGL(k_bags_head<XT>, dim3((unsigned)((nhead + 255) / 256)), dim3(256), 0, st, ha);
     if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
@@ -407,6 +484,138 @@ int agg_backward_bags_impl(const XT* feats, const XT* vals, const int64_t* offse
         if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
     }
     return DSMIL_OK;
+}
+
+// ---- dsmil_agg_train_step_bags / _bf16: one optimiser step on a batch of bags per C call ----------------------------
+// workspace: the batched forward's, bags_layout, the step's own tensors, the eight gradient tensors and, for bf16 rows,
+// the rounded parameter set with its packed MFMA image
+struct BagsStepWs {
+    size_t fwd, bwd, classes, A, B, pred, idx, gpred, gmax, grads, rounded, image, total;
+    size_t fwd_bytes, bwd_bytes;
+};
+inline void step_bags_sizes(int K, int C, int nonlinear, long long (&sizes)[8]) {   // parameter order (ops.W_KEYS)
+    const long long s[8] = {(long long)C * K, C, (long long)QD * K, QD, nonlinear ? QD * QD : 0, nonlinear ? QD : 0,
+                            (long long)C * C * K, C};
+    for (int i = 0; i < 8; ++i) sizes[i] = s[i];
+}
+BagsStepWs step_bags_layout(int n_bags, long long T, int K, int C, int nonlinear, bool b16) {
+    BagsStepWs s;
+    s.fwd_bytes = dsmil_agg_workspace_bytes(n_bags, T, K, K, C);
+    s.bwd_bytes = bags_layout(n_bags, T, K, K, C, nonlinear).total;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t p = o; o = al(o + bytes); return p; };
+    s.fwd = take(s.fwd_bytes);
+    s.bwd = take(s.bwd_bytes);
+    s.classes = take((size_t)T * C * 4);
+    s.A = take((size_t)T * C * 4);
+    s.B = take((size_t)n_bags * C * K * 4);
+    s.pred = take((size_t)n_bags * C * 4);
+    s.idx = take((size_t)n_bags * C * 8);
+    s.gpred = take((size_t)n_bags * C * 4);
+    s.gmax = take((size_t)n_bags * C * 4);
+    long long sizes[8];
+    step_bags_sizes(K, C, nonlinear, sizes);
+    s.grads = o;
+    for (int i = 0; i < 8; ++i) take((size_t)sizes[i] * 4);       // each tensor 256-B aligned
+    s.rounded = o;
+    if (b16)
+        for (int i = 0; i < 8; ++i) take((size_t)sizes[i] * 4);
+    s.image = take(b16 ? dsmil_agg_packed_bf16_bytes(K) : 0);
+    s.total = o;
+    return s;
+}
+
+// XT = float: dsmil_agg_train_step_bags; XT = bf16_t: dsmil_agg_train_step_bags_bf16.  A fixed launch sequence:
+//   bf16 rows only: k_round_bf16 (masters -> rounded set), k_pack_agg_bf16 (its MFMA image; dsmil_agg_pack_bf16)
+//   the batched forward (dsmil_agg_forward_ex, which cuts its own weight image / dsmil_agg_forward_bf16)
+//   k_loss_head_bags_mean
+//   the batched backward (agg_backward_bags_impl: k_train_prologue first) with Adam in its last two launches
+// Every check runs here, before the first launch, and covers what the chained calls would refuse.
+template <typename XT>
+int agg_train_step_bags_impl(const XT* feats, const int64_t* offsets, int32_t n_bags, int64_t T, int64_t max_rows,
+                             const int64_t* row_map, const float* labels, const dsmil_agg_params* p,
+                             const dsmil_adam_state* opt, float* loss_each, float* loss, void* ws, size_t ws_bytes,
+                             void* stream) {
+    constexpr bool B16 = sizeof(XT) == 2;
+    // 1. DSMIL_E_INVALID
+    if (!feats || !offsets || !labels || !p || !opt || !loss_each || !loss || !ws) return DSMIL_E_INVALID;
+    if (n_bags < 1 || T < n_bags || max_rows < 1 || max_rows > T) return DSMIL_E_INVALID;
+    if (p->K <= 0 || p->C <= 0 || p->Kv != p->K) return DSMIL_E_INVALID;
+    if (!p->fc_w || !p->fc_b || !p->q0_w || !p->q0_b || !p->fcc_w || !p->fcc_b || (p->nonlinear && (!p->q2_w || !p->q2_b)))
+        return DSMIL_E_INVALID;
+    if (opt->step <= 0 || !opt->exp_avg || !opt->exp_avg_sq) return DSMIL_E_INVALID;
+    const int K = p->K, C = p->C;
+    long long sizes[8];
+    step_bags_sizes(K, C, p->nonlinear, sizes);
+    for (int i = 0; i < 8; ++i)
+        if (sizes[i] && (!opt->exp_avg[i] || !opt->exp_avg_sq[i])) return DSMIL_E_INVALID;
+    // 2. DSMIL_E_UNSUPPORTED: the limits of the calls the step chains
+    if (C > 64 || n_bags > 65535 || T > BAGS_MAX_ROWS) return DSMIL_E_UNSUPPORTED;
+    if (B16 && K % 8) return DSMIL_E_UNSUPPORTED;
+    if (((long long)T * ((K + 3) / 4) + 255) / 256 > 0x7fffffffLL) return DSMIL_E_UNSUPPORTED;
+    // 3. DSMIL_E_ALIGN (the rounded set of the bf16 step lies in the workspace: aligned with it)
+    if ((uintptr_t)ws % 256) return DSMIL_E_ALIGN;
+    if (((uintptr_t)labels | (uintptr_t)loss_each | (uintptr_t)loss) % 4 || (uintptr_t)offsets % 8 || (uintptr_t)row_map % 8)
+        return DSMIL_E_ALIGN;
+    if (B16 ? ((uintptr_t)feats % 16 != 0) : ((uintptr_t)p->q0_b % 16 || (p->nonlinear && (uintptr_t)p->q2_b % 16))) return DSMIL_E_ALIGN;
+    // 4. DSMIL_E_WORKSPACE
+    const BagsStepWs L = step_bags_layout(n_bags, T, K, C, p->nonlinear, B16);
+    if (ws_bytes < L.total) return DSMIL_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    char* w8 = (char*)ws;
+    float* classes = (float*)(w8 + L.classes); float* A = (float*)(w8 + L.A); float* Bm = (float*)(w8 + L.B);
+    float* pred = (float*)(w8 + L.pred); int64_t* idx = (int64_t*)(w8 + L.idx);
+    float* gpred = (float*)(w8 + L.gpred); float* gmax = (float*)(w8 + L.gmax);
+    float* masters[8] = {const_cast<float*>(p->fc_w), const_cast<float*>(p->fc_b), const_cast<float*>(p->q0_w),
+                         const_cast<float*>(p->q0_b), const_cast<float*>(p->q2_w), const_cast<float*>(p->q2_b),
+                         const_cast<float*>(p->fcc_w), const_cast<float*>(p->fcc_b)};
+    float* gr[8];
+    float* rnd[8];
+    {
+        size_t o = L.grads, r = L.rounded;
+        for (int i = 0; i < 8; ++i) {
+            gr[i] = (float*)(w8 + o); o = al(o + (size_t)sizes[i] * 4);
+            rnd[i] = (float*)(w8 + r); r = al(r + (size_t)sizes[i] * 4);
+        }
+    }
+    int rc;
+    dsmil_agg_params pr = *p;   // what the forward and the backward read: the masters, or (bf16 rows) the rounded set
+    if constexpr (B16) {
+        // straight-through (dsmil_agg_backward_bags_bf16): forward and backward at the rounded weights, Adam on the masters
+        RoundTensors rt{};
+        long long tot = 0;
+        for (int i = 0; i < 8; ++i) { rt.src[i] = masters[i]; rt.dst[i] = rnd[i]; tot += sizes[i]; rt.end[i] = tot; }
+        hipLaunchKernelGGL(k_round_bf16, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, rt);
+        if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+        pr.fc_w = rnd[0]; pr.fc_b = rnd[1]; pr.q0_w = rnd[2]; pr.q0_b = rnd[3];
+        pr.q2_w = p->nonlinear ? rnd[4] : nullptr; pr.q2_b = p->nonlinear ? rnd[5] : nullptr; pr.fcc_w = rnd[6]; pr.fcc_b = rnd[7];
+        rc = dsmil_agg_pack_bf16(pr.q0_w, pr.q2_w, K, w8 + L.image, stream);
+        if (rc) return rc;
+        rc = dsmil_agg_forward_bf16(feats, nullptr, offsets, n_bags, T, max_rows, &pr, w8 + L.image, nullptr, classes, A, Bm, pred,
+                                    idx, w8 + L.fwd, L.fwd_bytes, stream);
+    } else {
+        dsmil_agg_opts fo{};
+        fo.row_map = row_map;
+        rc = dsmil_agg_forward_ex(feats, nullptr, offsets, n_bags, T, max_rows, &pr, &fo, nullptr, classes, A, Bm, pred, idx,
+                                  w8 + L.fwd, L.fwd_bytes, stream);
+    }
+    if (rc) return rc;
+    // objective (train_tcga.py:68-71 per bag, the mean over the bags) and both upstream gradients, scaled for the mean
+    hipLaunchKernelGGL(k_loss_head_bags_mean, dim3(1), dim3(1024), 0, st, classes, offsets, pred, idx, labels, (int)n_bags, C,
+                       1.0f / (float)n_bags, loss_each, loss, gpred, gmax);
+    if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    // backward + optimizer.step(): scalars formed in double as in dsmil_agg_train_step / dsmil_adam_step
+    dsmil_agg_grads g{};
+    g.fc_w = gr[0]; g.fc_b = gr[1]; g.q0_w = gr[2]; g.q0_b = gr[3]; g.q2_w = p->nonlinear ? gr[4] : nullptr;
+    g.q2_b = p->nonlinear ? gr[5] : nullptr; g.fcc_w = gr[6]; g.fcc_b = gr[7];
+    AdamFuse af{};
+    af.on = 1;
+    for (int i = 0; i < 8; ++i) { af.p[i] = masters[i]; af.m[i] = opt->exp_avg[i]; af.v[i] = opt->exp_avg_sq[i]; }
+    const double bc1 = 1.0 - pow(opt->beta1, (double)opt->step), bc2 = 1.0 - pow(opt->beta2, (double)opt->step);
+    af.h = AdamScalars{(float)(opt->lr / bc1), (float)(1.0 - opt->beta1), (float)opt->beta2, (float)(1.0 - opt->beta2),
+                       (float)opt->eps, (float)opt->weight_decay, (float)sqrt(bc2)};
+    return agg_backward_bags_impl<XT>(feats, nullptr, offsets, n_bags, T, max_rows, &pr, A, Bm, idx, nullptr, gmax, gpred, nullptr,
+                                      nullptr, &g, nullptr, row_map, w8 + L.bwd, L.bwd_bytes, stream, nullptr, &af);
 }
 
 }  // namespace

@@ -751,6 +751,22 @@ def agg_backward_bags(feats, lengths, w, A, B, idx, g_pred, g_classes=None, g_A=
                          g_max, row_map, want_g_feats)
 
 
+def _step_operands(what, params, exp_avg, exp_avg_sq, K, C, nonlinear, step, lr, betas, eps, weight_decay):
+    """struct dsmil_agg_params over the eight ``params`` and struct dsmil_adam_state over their moments for the one-call
+    training steps.  Returns (params struct, state struct, the pointer arrays the state points into: hold them until the
+    call is enqueued)."""
+    for t in list(params) + list(exp_avg) + list(exp_avg_sq):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise RuntimeError(f"{what}: parameters and Adam moments must be contiguous fp32 CUDA tensors")
+    ptr = lambda t: (t.data_ptr() if t is not None else 0)
+    p = _native.AggParams(*[ptr(t) for t in params], K, K, C, 1 if nonlinear else 0)
+    arr = ctypes.c_void_p * 8
+    m_arr, v_arr = arr(*[ptr(t) for t in exp_avg]), arr(*[ptr(t) for t in exp_avg_sq])
+    st = _native.AdamState(ctypes.cast(m_arr, ctypes.POINTER(ctypes.c_void_p)), ctypes.cast(v_arr, ctypes.POINTER(ctypes.c_void_p)),
+                           int(step), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay))
+    return p, st, (m_arr, v_arr)
+
+
 def agg_train_step(feats, label, params, exp_avg, exp_avg_sq, step, lr, betas, eps, weight_decay, nonlinear=True,
                    row_map=None, loss_out=None):
     """dsmil_agg_train_step: one train_tcga.py:60-75 step (forward, 0.5 BCE(bag) + 0.5 BCE(max instance), backward,
@@ -764,15 +780,7 @@ def agg_train_step(feats, label, params, exp_avg, exp_avg_sq, step, lr, betas, e
     N = int(row_map.numel()) if row_map is not None else rows
     label = _f32c(label.reshape(-1).to(torch.float32), "label")
     C = int(label.numel())
-    for t in list(params) + list(exp_avg) + list(exp_avg_sq):
-        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-            raise RuntimeError("agg_train_step: parameters and Adam moments must be contiguous fp32 CUDA tensors")
-    ptr = lambda t: (t.data_ptr() if t is not None else 0)
-    p = _native.AggParams(*[ptr(t) for t in params], K, K, C, 1 if nonlinear else 0)
-    arr = ctypes.c_void_p * 8
-    m_arr, v_arr = arr(*[ptr(t) for t in exp_avg]), arr(*[ptr(t) for t in exp_avg_sq])
-    st = _native.AdamState(ctypes.cast(m_arr, ctypes.POINTER(ctypes.c_void_p)), ctypes.cast(v_arr, ctypes.POINTER(ctypes.c_void_p)),
-                           int(step), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay))
+    p, st, keep = _step_operands("agg_train_step", params, exp_avg, exp_avg_sq, K, C, nonlinear, step, lr, betas, eps, weight_decay)
     loss = loss_out if loss_out is not None else torch.empty((1,), dtype=torch.float32, device=dev)
     L = _native.lib()
     ws = _workspace(dev, L.dsmil_agg_train_step_workspace_bytes(N, K, C, 1 if nonlinear else 0))
@@ -780,7 +788,52 @@ def agg_train_step(feats, label, params, exp_avg, exp_avg_sq, step, lr, betas, e
         rc = L.dsmil_agg_train_step(_ptr(feats), N, _ptr(row_map), _ptr(label), ctypes.byref(p), ctypes.byref(st), _ptr(loss),
                                     _ptr(ws), ws.numel(), _stream(dev))
     _native.check(rc, "dsmil_agg_train_step")
+    del keep
     return loss
+
+
+def agg_train_step_bags(feats, lengths, labels, params, exp_avg, exp_avg_sq, step, lr, betas, eps, weight_decay,
+                        nonlinear=True, row_map=None, offsets=None):
+    """dsmil_agg_train_step_bags / dsmil_agg_train_step_bags_bf16 (by ``feats.dtype``): ONE optimiser step on a batch of
+    bags stored back to back as ONE native call — batched forward, the mean over the bags of ``agg_train_step``'s objective,
+    batched backward, Adam.  ``lengths``: the bags' LOGICAL row counts; labels [n_bags, C]; ``params`` / ``exp_avg`` /
+    ``exp_avg_sq`` / ``step`` as in ``agg_train_step`` (updated IN PLACE).  ``row_map``: int64 [sum(lengths)] as in
+    ``agg_forward``; the bf16 entry has none, so bf16 rows are gathered by one index_select in front of the call (as
+    MILNet.batch_loss does).  Returns (loss [1], loss_each [n_bags]) as device tensors (no host sync)."""
+    bf16 = feats.dtype == torch.bfloat16
+    if not feats.is_cuda:
+        raise RuntimeError("feats must be a CUDA(HIP) tensor for the native path")
+    row_map = _i64c(row_map, "row_map")
+    if bf16:
+        if row_map is not None:
+            feats, row_map = feats.index_select(0, row_map), None
+        feats = feats if feats.is_contiguous() else feats.contiguous()
+    else:
+        feats = _f32c(feats, "feats")
+    dev = feats.device
+    rows, K = feats.shape
+    total = int(row_map.numel()) if row_map is not None else rows
+    lengths = [int(n) for n in lengths]
+    n = len(lengths)
+    if n < 1 or sum(lengths) != total or any(m <= 0 for m in lengths):
+        raise ValueError(f"bag lengths must be positive and sum to {total}")
+    labels = _f32c(labels.reshape(n, -1).to(torch.float32), "labels")
+    C = int(labels.shape[1])
+    p, st, keep = _step_operands("agg_train_step_bags", params, exp_avg, exp_avg_sq, K, C, nonlinear, step, lr, betas, eps,
+                                 weight_decay)
+    off = offsets if offsets is not None else offsets_tensor(lengths, dev)
+    out = torch.empty((1 + n,), dtype=torch.float32, device=dev)
+    loss, each = out[0:1], out[1:]
+    L = _native.lib()
+    entry = "dsmil_agg_train_step_bags_bf16" if bf16 else "dsmil_agg_train_step_bags"
+    ws = _workspace(dev, getattr(L, entry + "_workspace_bytes")(n, total, K, C, 1 if nonlinear else 0))
+    rmap = () if bf16 else (_ptr(row_map),)
+    with torch.cuda.device(dev):
+        rc = getattr(L, entry)(_ptr(feats), _ptr(off), n, total, max(lengths), *rmap, _ptr(labels), ctypes.byref(p),
+                               ctypes.byref(st), _ptr(each), _ptr(loss), _ptr(ws), ws.numel(), _stream(dev))
+    _native.check(rc, entry)
+    del keep
+    return loss, each
 
 
 def adam_step(params, grads, exp_avg, exp_avg_sq, step, lr, betas, eps, weight_decay):

@@ -141,7 +141,9 @@ class FusedTrainStep:
     """train_tcga.py:60-75 as ONE native call per bag (dsmil_agg_train_step): forward, the two-BCE objective, backward and
     the Adam update of all parameter tensors are enqueued by a single C call — the Python side of a step is that call plus
     the loss read-back of the progress line.  Numerically it is the step the generic path takes (same kernels, same Adam
-    arithmetic as torch.optim.Adam's; tests/test_agg_bwd_gpu.py compares the two trajectories).
+    arithmetic as torch.optim.Adam's; tests/test_agg_bwd_gpu.py compares the two trajectories).  ``step_bags`` is the same for a
+    group of bags (``bags_per_step`` > 1: dsmil_agg_train_step_bags, the mean objective of MILNet.batch_loss) and for
+    bf16-stored bags (dsmil_agg_train_step_bags_bf16; a lone bag is a batch of one); tests/test_step_bags_gpu.py.
 
     Eligible (``FusedTrainStep.create`` returns None otherwise, and ``train`` keeps the generic autograd path):
     MILNet(FCLayer, BClassifier) with v = Identity on a GPU, every parameter trainable fp32, the stock
@@ -198,12 +200,35 @@ class FusedTrainStep:
             return None
 
     def accepts(self, bag_feats):
-        # (fp32 bags only: bf16-stored bags take the generic loop around bag_loss / batch_loss)
-        return bag_feats.is_cuda and bag_feats.dtype == torch.float32 and bag_feats.dim() == 2 and bag_feats.is_contiguous()
+        """Rows the fused steps take: a contiguous 2-D CUDA tensor, fp32, or bf16-stored with K % 8 == 0."""
+        if not (bag_feats.is_cuda and bag_feats.dim() == 2 and bag_feats.is_contiguous()):
+            return False
+        return bag_feats.dtype == torch.float32 or (bag_feats.dtype == torch.bfloat16 and bag_feats.shape[1] % 8 == 0)
+
+    def step_bags(self, feats, lengths, labels, row_map=None):
+        """One optimiser step on a BATCH of bags stored back to back (dsmil_agg_train_step_bags, or its bf16 form for
+        bf16-stored rows): the objective is the mean of the bags' losses (MILNet.batch_loss).  ``lengths`` count logical
+        rows, ``row_map`` as in batch_loss.  Returns (loss, each bag's own loss [n]) as detached device tensors."""
+        from . import ops
+        g = self.group
+        if row_map is not None and row_map.numel() and feats.dtype == torch.float32:
+            # (as MILNet.batch_loss: an out-of-range index would be an out-of-bounds device read in the row loads)
+            torch._assert_async((row_map.min() >= 0) & (row_map.max() < feats.shape[0]), "row_map index out of range")
+        with torch.no_grad():
+            loss, each = ops.agg_train_step_bags(feats, lengths, labels, [p.data if p is not None else None for p in self.params],
+                                                 self.m, self.v, self.step + 1, g["lr"], g["betas"], g["eps"], g["weight_decay"],
+                                                 nonlinear=self.nonlinear, row_map=row_map)
+        self.step += 1   # only once the native step was enqueued (see __call__)
+        torch.autograd.graph.increment_version(self._live)
+        return loss.reshape(()), each
 
     def __call__(self, bag_feats, bag_label, row_map=None):
-        """One optimiser step on one bag; returns the loss (0-dim device tensor, detached)."""
+        """One optimiser step on one bag; returns the loss (0-dim device tensor, detached).  fp32 bags: dsmil_agg_train_step;
+        bf16-stored bags: ``step_bags`` with one length."""
         from . import ops
+        if bag_feats.dtype == torch.bfloat16:
+            n = int(row_map.numel()) if row_map is not None else bag_feats.shape[0]
+            return self.step_bags(bag_feats, [n], bag_label.reshape(1, -1), row_map)[0]
         g = self.group
         with torch.no_grad():
             loss = ops.agg_train_step(bag_feats, bag_label, [p.data if p is not None else None for p in self.params], self.m,
@@ -300,10 +325,14 @@ class LossReadback:
 def _train_groups(args, dirs, milnet, criterion, optimizer, cache, log, per_step):
     """``train`` with ``bags_per_step`` > 1: consecutive bags of the shuffled order, per_step at a time (the last group may
     be short), ONE summed objective (batch_loss: the mean of the bags' losses), one backward and one optimizer.step() per
-    group.  This is minibatch training — a different optimisation schedule from the reference's one step per bag."""
+    group.  This is minibatch training — a different optimisation schedule from the reference's one step per bag.
+    With the reference's model / criterion / optimiser (FusedTrainStep.create) a group's whole step is one native call
+    (FusedTrainStep.step_bags) unless ``args.fused_step`` is false; the generic lines remain for everything else."""
     device = next(milnet.parameters()).device
     readback = LossReadback(device)
     losses, done = [], 0
+    # the whole step of a group as one native call when the model / criterion / optimiser are the reference's
+    fused = FusedTrainStep.create(milnet, criterion, optimizer) if getattr(args, "fused_step", True) else None
 
     def report(vals):
         nonlocal done
@@ -321,17 +350,26 @@ def _train_groups(args, dirs, milnet, criterion, optimizer, cache, log, per_step
                 off += bag_feats.size(0)
                 bags.append(bag_feats); labels.append(bag_label.reshape(1, -1))
             feats = torch.cat(bags, dim=0) if len(bags) > 1 else bags[0]
-            optimizer.zero_grad()
-            loss, _, _, each = batch_loss(milnet, criterion, feats, [int(m.numel()) for m in maps], torch.cat(labels),
-                                          torch.cat(maps) if any_map else None)
-            loss.backward()
-            optimizer.step()
+            lengths, row_map = [int(m.numel()) for m in maps], torch.cat(maps) if any_map else None
+            if fused is not None and fused.accepts(feats):
+                _, each = fused.step_bags(feats, lengths, torch.cat(labels), row_map)
+            else:
+                if fused is not None:
+                    fused.sync()          # (as in the per-bag loop of ``train``)
+                optimizer.zero_grad()
+                loss, _, _, each = batch_loss(milnet, criterion, feats, lengths, torch.cat(labels), row_map)
+                loss.backward()
+                optimizer.step()
+                if fused is not None:
+                    fused.resync()
             losses.append(each)
             if log:   # every bag's own loss, one step late
                 report(readback.push_many(each))
     finally:
         if log and dirs:
             report(readback.flush_many())
+        if fused is not None:
+            fused.sync()
     return float(torch.cat(losses).sum().item()) / max(1, len(dirs)) if losses else 0.0
 
 

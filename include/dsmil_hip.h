@@ -455,6 +455,46 @@ int dsmil_adam_step(int32_t n_tensors, float* const* params, const float* const*
                     float* const* exp_avg_sq, const int64_t* numel, int64_t step, double lr, double beta1,
                     double beta2, double eps, double weight_decay, void* stream);
 
+/* ---- one training step on a BATCH of bags per C call ------------------------------------------------
+ * The body of train_tcga.py:60-75 applied to n_bags bags stored back to back (offsets / total_rows / max_rows as in
+ * dsmil_agg_forward) with ONE optimiser step: the objective is the MEAN over the bags of
+ *     0.5 * BCEWithLogitsLoss(bag_prediction, y) + 0.5 * BCEWithLogitsLoss(max instance prediction, y)      (:68-71)
+ * and there is one Adam update per call (optimizer as for dsmil_agg_train_step).  The call enqueues, on `stream`: the
+ * batched forward, one launch for the objective (each bag's loss, their mean, both logit gradients scaled by 1 / n_bags),
+ * and the batched backward (dsmil_agg_backward_bags' launch sequence) whose last two launches apply Adam to the gradient
+ * elements they have just summed.  Parameters (*p) and moments (*opt) are UPDATED IN PLACE.  Nothing allocates, nothing
+ * synchronises; there are no atomics and every sum runs in a fixed order: two runs from the same state give the same bits,
+ * and the gradients are bit for bit those of dsmil_agg_loss_head_bags + dsmil_agg_backward_bags on the same batch.
+ *   feats      device [rows, K] fp32;  row_map int64 [total_rows] or NULL (every bag's dropout_patches list, offset added)
+ *   labels     device [n_bags, C] fp32 (0/1)
+ *   loss_each  device [n_bags]: each bag's own loss;   loss  device [1]: their mean (fp32 sum in bag order / n_bags)
+ *   opt        as for dsmil_agg_train_step (step = the 1-based index of THIS update; step <= 0 -> DSMIL_E_INVALID)
+ *   ws         dsmil_agg_train_step_bags_workspace_bytes(n_bags, total_rows, K, C, nonlinear) bytes, 256-B aligned: the
+ *              batched forward's workspace, the batched backward's, the forward's outputs, the eight gradient tensors
+ * dsmil_agg_train_step_bags_bf16: the same on bf16-STORED rows (no row map; a lone bag is a batch of one).  Two launches at
+ * its head round the eight fp32 master tensors to bf16 (nearest even, kept as fp32) into the workspace and pack the MFMA
+ * image of the rounded query weights (dsmil_agg_pack_bf16); forward (dsmil_agg_forward_bf16) and backward
+ * (dsmil_agg_backward_bags_bf16) both read that rounded set (straight-through), Adam updates the fp32 masters.  Its
+ * workspace adds the rounded set and the image.
+ * Limits are those of the chained calls: C <= 64, v = Identity (Kv == K), n_bags <= 65535, total_rows <= 2^30; bf16 needs
+ * K % 8 == 0.  Checks run in this order, ALL before the first launch, so a refused call has changed nothing:
+ * DSMIL_E_INVALID (a NULL operand or moment, sizes, Kv != K, step <= 0), DSMIL_E_UNSUPPORTED (the limits above),
+ * DSMIL_E_ALIGN (ws not 256-B aligned; labels / loss_each / loss not 4-B, offsets / row_map not 8-B aligned; fp32: q0_b or
+ * q2_b not 16-B aligned; bf16: rows not 16-B aligned), DSMIL_E_WORKSPACE.  The *_workspace_bytes queries answer 0 for
+ * sizes the entry refuses as invalid (and, bf16, for K % 8 != 0).
+ * Added without a change of DSMIL_ABI_VERSION (it stays 6, no existing signature moved): detected by SYMBOL. */
+size_t dsmil_agg_train_step_bags_workspace_bytes(int32_t n_bags, int64_t total_rows, int32_t K, int32_t C, int32_t nonlinear);
+int dsmil_agg_train_step_bags(const float* feats, const int64_t* offsets, int32_t n_bags, int64_t total_rows, int64_t max_rows,
+                              const int64_t* row_map, const float* labels, const dsmil_agg_params* p,
+                              const dsmil_adam_state* opt, float* loss_each, float* loss, void* ws, size_t ws_bytes,
+                              void* stream);
+size_t dsmil_agg_train_step_bags_bf16_workspace_bytes(int32_t n_bags, int64_t total_rows, int32_t K, int32_t C,
+                                                      int32_t nonlinear);
+int dsmil_agg_train_step_bags_bf16(const void* feats_bf16, const int64_t* offsets, int32_t n_bags, int64_t total_rows,
+                                   int64_t max_rows, const float* labels, const dsmil_agg_params* p,
+                                   const dsmil_adam_state* opt, float* loss_each, float* loss, void* ws, size_t ws_bytes,
+                                   void* stream);
+
 /* ---- patch embedder: ResNet-18 with InstanceNorm2d, fc = Identity --------------------------
  * Replaces the torchvision backbone that compute_feats.py:157,170 builds and dsmil.IClassifier
  * wraps (dsmil.py:21-25): feats[B,512] = flatten(avgpool(resnet18_IN(x))), and, when `classes`
