@@ -72,6 +72,11 @@ class AggGrads(ctypes.Structure):
                 ("fc_w", "fc_b", "q0_w", "q0_b", "q2_w", "q2_b", "fcc_w", "fcc_b")]
 
 
+class BceWeights(ctypes.Structure):
+    """struct dsmil_bce_weights (include/dsmil_hip.h): device pointers, [C] fp32 each, either may be NULL."""
+    _fields_ = [("pos_weight", ctypes.c_void_p), ("weight", ctypes.c_void_p)]
+
+
 class AdamState(ctypes.Structure):
     """struct dsmil_adam_state (include/dsmil_hip.h)."""
     _fields_ = [("exp_avg", ctypes.POINTER(ctypes.c_void_p)), ("exp_avg_sq", ctypes.POINTER(ctypes.c_void_p)),
@@ -99,6 +104,8 @@ SIGNATURES = {
                                             ctypes.c_size_t, ctypes.c_void_p]),
     "dsmil_agg_loss_head": (ctypes.c_int, [c_f32p, c_f32p, c_i64p, c_f32p, ctypes.c_int32, c_f32p, c_f32p, c_f32p,
                                            c_f32p, ctypes.c_void_p]),
+    "dsmil_agg_loss_head_w": (ctypes.c_int, [c_f32p, c_f32p, c_i64p, c_f32p, ctypes.c_int32, c_f32p, c_f32p, c_f32p,
+                                             c_f32p, ctypes.POINTER(BceWeights), ctypes.c_void_p]),
     "dsmil_agg_backward_ex": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64, ctypes.POINTER(AggParams), c_f32p,
                                              c_f32p, c_i64p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
                                              ctypes.POINTER(AggGrads), c_f32p, c_i64p, ctypes.c_void_p, ctypes.c_size_t,
@@ -213,6 +220,8 @@ SIGNATURES = {
                                                     ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "dsmil_agg_loss_head_bags": (ctypes.c_int, [c_f32p, c_i64p, c_f32p, c_i64p, c_f32p, ctypes.c_int32, ctypes.c_int32,
                                                 c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
+    "dsmil_agg_loss_head_bags_w": (ctypes.c_int, [c_f32p, c_i64p, c_f32p, c_i64p, c_f32p, ctypes.c_int32, ctypes.c_int32,
+                                                  c_f32p, c_f32p, c_f32p, c_f32p, ctypes.POINTER(BceWeights), ctypes.c_void_p]),
     "dsmil_value_backward_rows": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                                  c_f32p, ctypes.c_void_p, ctypes.c_int32, c_f32p, ctypes.c_void_p,
                                                  ctypes.c_size_t, ctypes.c_void_p]),
@@ -248,6 +257,15 @@ SIGNATURES = {
                                                       ctypes.c_int64, c_f32p, ctypes.POINTER(AggParams),
                                                       ctypes.POINTER(AdamState), c_f32p, c_f32p, ctypes.c_void_p,
                                                       ctypes.c_size_t, ctypes.c_void_p]),
+    # the weighted-BCE forms: the sibling's signature + const dsmil_bce_weights* in front of the stream
+    "dsmil_agg_train_step_bags_w": (ctypes.c_int, [c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, c_i64p,
+                                                   c_f32p, ctypes.POINTER(AggParams), ctypes.POINTER(AdamState), c_f32p,
+                                                   c_f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(BceWeights),
+                                                   ctypes.c_void_p]),
+    "dsmil_agg_train_step_bags_bf16_w": (ctypes.c_int, [ctypes.c_void_p, c_i64p, ctypes.c_int32, ctypes.c_int64,
+                                                        ctypes.c_int64, c_f32p, ctypes.POINTER(AggParams),
+                                                        ctypes.POINTER(AdamState), c_f32p, c_f32p, ctypes.c_void_p,
+                                                        ctypes.c_size_t, ctypes.POINTER(BceWeights), ctypes.c_void_p]),
     "dsmil_adam_step": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
                                        ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
                                        ctypes.POINTER(ctypes.c_int64), ctypes.c_int64, ctypes.c_double, ctypes.c_double,

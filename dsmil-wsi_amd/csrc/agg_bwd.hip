@@ -1534,10 +1534,20 @@ int dsmil_agg_backward_bags_bf16(const void* feats_bf16, const void* vals_bf16, 
 int dsmil_agg_loss_head_bags(const float* classes, const int64_t* offsets, const float* pred, const int64_t* idx,
                              const float* labels, int32_t n_bags, int32_t C, float* loss, float* max_pred, float* g_pred,
                              float* g_max, void* stream) {
+    return dsmil_agg_loss_head_bags_w(classes, offsets, pred, idx, labels, n_bags, C, loss, max_pred, g_pred, g_max, nullptr,
+                                      stream);
+}
+
+int dsmil_agg_loss_head_bags_w(const float* classes, const int64_t* offsets, const float* pred, const int64_t* idx,
+                               const float* labels, int32_t n_bags, int32_t C, float* loss, float* max_pred, float* g_pred,
+                               float* g_max, const dsmil_bce_weights* bw, void* stream) {
     if (!classes || !offsets || !pred || !idx || !labels || !loss || n_bags < 1 || C <= 0) return DSMIL_E_INVALID;
     if (C > 64) return DSMIL_E_UNSUPPORTED;
+    const float* pos_weight = bw ? bw->pos_weight : nullptr;
+    const float* weight = bw ? bw->weight : nullptr;
+    if (((uintptr_t)pos_weight | (uintptr_t)weight) % 4) return DSMIL_E_ALIGN;
     hipLaunchKernelGGL(k_loss_head_bags, dim3((unsigned)n_bags), dim3(64), 0, (hipStream_t)stream, classes, offsets, pred, idx,
-                       labels, C, loss, max_pred, g_pred, g_max);
+                       labels, C, loss, max_pred, g_pred, g_max, pos_weight, weight);
     return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 
@@ -1673,7 +1683,15 @@ int dsmil_agg_train_step_bags(const float* feats, const int64_t* offsets, int32_
                               const dsmil_adam_state* opt, float* loss_each, float* loss, void* ws, size_t ws_bytes,
                               void* stream) {
     return agg_train_step_bags_impl<float>(feats, offsets, n_bags, total_rows, max_rows, row_map, labels, p, opt, loss_each, loss,
-                                           ws, ws_bytes, stream);
+                                           ws, ws_bytes, nullptr, stream);
+}
+
+int dsmil_agg_train_step_bags_w(const float* feats, const int64_t* offsets, int32_t n_bags, int64_t total_rows, int64_t max_rows,
+                                const int64_t* row_map, const float* labels, const dsmil_agg_params* p,
+                                const dsmil_adam_state* opt, float* loss_each, float* loss, void* ws, size_t ws_bytes,
+                                const dsmil_bce_weights* bw, void* stream) {
+    return agg_train_step_bags_impl<float>(feats, offsets, n_bags, total_rows, max_rows, row_map, labels, p, opt, loss_each, loss,
+                                           ws, ws_bytes, bw, stream);
 }
 
 size_t dsmil_agg_train_step_bags_bf16_workspace_bytes(int32_t n_bags, int64_t total_rows, int32_t K, int32_t C,
@@ -1687,7 +1705,15 @@ int dsmil_agg_train_step_bags_bf16(const void* feats_bf16, const int64_t* offset
                                    const dsmil_adam_state* opt, float* loss_each, float* loss, void* ws, size_t ws_bytes,
                                    void* stream) {
     return agg_train_step_bags_impl<bf16_t>((const bf16_t*)feats_bf16, offsets, n_bags, total_rows, max_rows, nullptr, labels, p,
-                                            opt, loss_each, loss, ws, ws_bytes, stream);
+                                            opt, loss_each, loss, ws, ws_bytes, nullptr, stream);
+}
+
+int dsmil_agg_train_step_bags_bf16_w(const void* feats_bf16, const int64_t* offsets, int32_t n_bags, int64_t total_rows,
+                                     int64_t max_rows, const float* labels, const dsmil_agg_params* p,
+                                     const dsmil_adam_state* opt, float* loss_each, float* loss, void* ws, size_t ws_bytes,
+                                     const dsmil_bce_weights* bw, void* stream) {
+    return agg_train_step_bags_impl<bf16_t>((const bf16_t*)feats_bf16, offsets, n_bags, total_rows, max_rows, nullptr, labels, p,
+                                            opt, loss_each, loss, ws, ws_bytes, bw, stream);
 }
 
 // ---- the value stream's parameter gradients (agg_value.h): what autograd derives for dsmil.py:39 behind g_vals ----

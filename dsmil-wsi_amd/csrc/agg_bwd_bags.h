@@ -205,21 +205,23 @@ __global__ __launch_bounds__(64) void k_loss_head_bags(const float* __restrict__
                                                        const float* __restrict__ pred, const int64_t* __restrict__ idx,
                                                        const float* __restrict__ label, int C, float* __restrict__ loss,
                                                        float* __restrict__ max_pred, float* __restrict__ g_pred,
-                                                       float* __restrict__ g_max) {
+                                                       float* __restrict__ g_max, const float* __restrict__ pos_weight,
+                                                       const float* __restrict__ weight) {
     const int c = threadIdx.x, b = blockIdx.x;
     const long long bc = (long long)b * C + c;
+    const bool weighted = pos_weight || weight;   // class weights (dsmil_agg_loss_head_bags_w), [C] each or null = ones
     float l = 0.f;
     if (c < C) {
         const float y = label[bc];
         const float zb = pred[bc], zm = classes[((long long)offsets[b] + (long long)idx[bc]) * C + c];
-        // BCEWithLogits(z, y) = max(z,0) - z y + log1p(exp(-|z|))  (torch's stable form)
-        const float lb = fmaxf(zb, 0.f) - zb * y + log1pf(expf(-fabsf(zb)));
-        const float lm = fmaxf(zm, 0.f) - zm * y + log1pf(expf(-fabsf(zm)));
+        const float pw = pos_weight ? pos_weight[c] : 1.f, w = weight ? weight[c] : 1.f;
+        float lb, lm, db, dm;   // BCEWithLogits(z, y) and its derivative in z (bce_logit, agg_common.h)
+        bce_logit(weighted, zb, y, pw, w, lb, db);
+        bce_logit(weighted, zm, y, pw, w, lm, dm);
         l = 0.5f * (lb + lm) / (float)C;
-        const float sb = 1.f / (1.f + expf(-zb)), sm = 1.f / (1.f + expf(-zm));
         if (max_pred) max_pred[bc] = zm;
-        if (g_pred) g_pred[bc] = 0.5f * (sb - y) / (float)C;
-        if (g_max) g_max[bc] = 0.5f * (sm - y) / (float)C;
+        if (g_pred) g_pred[bc] = 0.5f * db / (float)C;
+        if (g_max) g_max[bc] = 0.5f * dm / (float)C;
     }
     l = wave_sum(l);   // C <= 64: one wave
     if (threadIdx.x == 0) loss[b] = l;
@@ -238,19 +240,23 @@ __global__ __launch_bounds__(1024) void k_loss_head_bags_mean(const float* __res
                                                               const float* __restrict__ pred, const int64_t* __restrict__ idx,
                                                               const float* __restrict__ label, int n_bags, int C, float scale,
                                                               float* __restrict__ loss_each, float* __restrict__ loss,
-                                                              float* __restrict__ g_pred, float* __restrict__ g_max) {
+                                                              float* __restrict__ g_pred, float* __restrict__ g_max,
+                                                              const float* __restrict__ pos_weight,
+                                                              const float* __restrict__ weight) {
     const int c = threadIdx.x & 63;
+    const bool weighted = pos_weight || weight;   // class weights (dsmil_agg_train_step_bags_w), [C] each or null = ones
+    const float pw = (pos_weight && c < C) ? pos_weight[c] : 1.f, w = (weight && c < C) ? weight[c] : 1.f;
     for (int b = threadIdx.x >> 6; b < n_bags; b += 16) {
         const long long bc = (long long)b * C + c;
         float l = 0.f;
         if (c < C) {
             const float y = label[bc];
             const float zb = pred[bc], zm = classes[((long long)offsets[b] + (long long)idx[bc]) * C + c];
-            const float lb = fmaxf(zb, 0.f) - zb * y + log1pf(expf(-fabsf(zb)));
-            const float lm = fmaxf(zm, 0.f) - zm * y + log1pf(expf(-fabsf(zm)));
+            float lb, lm, db, dm;   // BCEWithLogits(z, y) and its derivative in z (bce_logit, agg_common.h)
+            bce_logit(weighted, zb, y, pw, w, lb, db);
+            bce_logit(weighted, zm, y, pw, w, lm, dm);
             l = 0.5f * (lb + lm) / (float)C;
-            const float sb = 1.f / (1.f + expf(-zb)), sm = 1.f / (1.f + expf(-zm));
-            const float gp = 0.5f * (sb - y) / (float)C, gm = 0.5f * (sm - y) / (float)C;
+            const float gp = 0.5f * db / (float)C, gm = 0.5f * dm / (float)C;
             g_pred[bc] = gp * scale;
             g_max[bc] = gm * scale;
         }
@@ -535,8 +541,10 @@ template <typename XT>
 int agg_train_step_bags_impl(const XT* feats, const int64_t* offsets, int32_t n_bags, int64_t T, int64_t max_rows,
                              const int64_t* row_map, const float* labels, const dsmil_agg_params* p,
                              const dsmil_adam_state* opt, float* loss_each, float* loss, void* ws, size_t ws_bytes,
-                             void* stream) {
+                             const dsmil_bce_weights* bw, void* stream) {
     constexpr bool B16 = sizeof(XT) == 2;
+    const float* pos_weight = bw ? bw->pos_weight : nullptr;   // the _w entries' class weights, [C] each or null = ones
+    const float* weight = bw ? bw->weight : nullptr;
     // 1. DSMIL_E_INVALID
     if (!feats || !offsets || !labels || !p || !opt || !loss_each || !loss || !ws) return DSMIL_E_INVALID;
     if (n_bags < 1 || T < n_bags || max_rows < 1 || max_rows > T) return DSMIL_E_INVALID;
@@ -555,7 +563,8 @@ int agg_train_step_bags_impl(const XT* feats, const int64_t* offsets, int32_t n_
     if (((long long)T * ((K + 3) / 4) + 255) / 256 > 0x7fffffffLL) return DSMIL_E_UNSUPPORTED;
     // 3. DSMIL_E_ALIGN (the rounded set of the bf16 step lies in the workspace: aligned with it)
     if ((uintptr_t)ws % 256) return DSMIL_E_ALIGN;
-    if (((uintptr_t)labels | (uintptr_t)loss_each | (uintptr_t)loss) % 4 || (uintptr_t)offsets % 8 || (uintptr_t)row_map % 8)
+    if (((uintptr_t)labels | (uintptr_t)loss_each | (uintptr_t)loss | (uintptr_t)pos_weight | (uintptr_t)weight) % 4 ||
+        (uintptr_t)offsets % 8 || (uintptr_t)row_map % 8)
         return DSMIL_E_ALIGN;
     if (B16 ? ((uintptr_t)feats % 16 != 0) : ((uintptr_t)p->q0_b % 16 || (p->nonlinear && (uintptr_t)p->q2_b % 16))) return DSMIL_E_ALIGN;
     // 4. DSMIL_E_WORKSPACE
@@ -602,7 +611,7 @@ int agg_train_step_bags_impl(const XT* feats, const int64_t* offsets, int32_t n_
     if (rc) return rc;
     // objective (train_tcga.py:68-71 per bag, the mean over the bags) and both upstream gradients, scaled for the mean
     hipLaunchKernelGGL(k_loss_head_bags_mean, dim3(1), dim3(1024), 0, st, classes, offsets, pred, idx, labels, (int)n_bags, C,
-                       1.0f / (float)n_bags, loss_each, loss, gpred, gmax);
+                       1.0f / (float)n_bags, loss_each, loss, gpred, gmax, pos_weight, weight);
     if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
     // backward + optimizer.step(): scalars formed in double as in dsmil_agg_train_step / dsmil_adam_step
     dsmil_agg_grads g{};

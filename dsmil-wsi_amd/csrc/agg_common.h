@@ -84,6 +84,32 @@ __device__ __forceinline__ float wave_max(float v) {
     return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
 }
 
+// One logit of the training objective (k_loss_head, k_loss_head_bags, k_loss_head_bags_mean): the BCEWithLogitsLoss term of
+// logit z against label y, and its derivative in z.  `weighted` is uniform across the launch (either class-weight vector was
+// given); pw / w are this class's pos_weight / weight entries (train_mil.py:52-55), 1 for a vector that was not given.
+//   stock criterion:  term = max(z,0) - z y + log1p(exp(-|z|))   (torch's stable form),  d/dz = sigma(z) - y
+//   class weights (torch's binary_cross_entropy_with_logits):  lw = 1 + (pw - 1) y,
+//                     term = w ((1 - y) z + lw (max(-z,0) + log1p(exp(-|z|)))),  d/dz = w ((1 - y) - lw sigma(-z))
+//   The derivative is evaluated as torch's backward evaluates the same function, w (((pw y + 1) - y) sigma(z) - pw y)
+//   (lw sigma(z) - pw y = (1 - y) - lw sigma(-z): lw - 1 + y = pw y), product and difference rounded separately as torch's
+//   two kernels round them: the first form cancels where torch's does not and the other way round, and six Adam steps on
+//   the first form left single parameter elements 1.4e-4 .. 1.8e-4 of their tensor's scale away from torch autograd +
+//   torch.optim.Adam (tests/test_wbce_gpu.py asks for 1e-4); on this form the largest such distance was 0.5e-4, in one
+//   case, and below 1e-6 of scale elsewhere, as for the stock criterion.
+//   sigma(z) = 1 / (1 + e) for z >= 0 (torch's own bits) and e / (1 + e) below, e = exp(-|z|) <= 1: nothing overflows.
+__device__ __forceinline__ void bce_logit(bool weighted, float z, float y, float pw, float w, float& term, float& dz) {
+    if (!weighted) {
+        term = fmaxf(z, 0.f) - z * y + log1pf(expf(-fabsf(z)));
+        dz = 1.f / (1.f + expf(-z)) - y;
+    } else {
+        const float e = expf(-fabsf(z));
+        const float lw = 1.f + (pw - 1.f) * y;
+        term = w * ((1.f - y) * z + lw * (fmaxf(-z, 0.f) + log1pf(e)));
+        const float t = pw * y, s = (z >= 0.f ? 1.f : e) / (1.f + e);
+        dz = w * __fsub_rn(__fmul_rn((t + 1.f) - y, s), t);
+    }
+}
+
 // Every feature / weight / workspace pointer handed to this library is device GLOBAL memory.  Inside
 // out-of-line (noinline) device functions hipcc cannot infer that and would emit FLAT loads, whose
 // lgkmcnt accounting serialises them with the LDS reads; the hot loads therefore say so explicitly.

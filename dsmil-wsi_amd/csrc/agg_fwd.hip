@@ -2176,20 +2176,22 @@ extern "C" {
 static __global__ void k_loss_head(const float* __restrict__ classes, const float* __restrict__ pred,
                             const int64_t* __restrict__ idx, const float* __restrict__ label, int C,
                             float* __restrict__ loss, float* __restrict__ max_pred, float* __restrict__ g_pred,
-                            float* __restrict__ g_max) {
+                            float* __restrict__ g_max, const float* __restrict__ pos_weight,
+                            const float* __restrict__ weight) {
     const int c = threadIdx.x;
+    const bool weighted = pos_weight || weight;   // class weights (dsmil_agg_loss_head_w), [C] each or null = ones
     float l = 0.f;
     if (c < C) {
         const float y = label[c];
         const float zb = pred[c], zm = classes[idx[c] * (long long)C + c];
-        // BCEWithLogits(z, y) = max(z,0) - z y + log1p(exp(-|z|))  (torch's stable form)
-        const float lb = fmaxf(zb, 0.f) - zb * y + log1pf(expf(-fabsf(zb)));
-        const float lm = fmaxf(zm, 0.f) - zm * y + log1pf(expf(-fabsf(zm)));
+        const float pw = pos_weight ? pos_weight[c] : 1.f, w = weight ? weight[c] : 1.f;
+        float lb, lm, db, dm;   // BCEWithLogits(z, y) and its derivative in z (bce_logit, agg_common.h)
+        bce_logit(weighted, zb, y, pw, w, lb, db);
+        bce_logit(weighted, zm, y, pw, w, lm, dm);
         l = 0.5f * (lb + lm) / (float)C;
-        const float sb = 1.f / (1.f + expf(-zb)), sm = 1.f / (1.f + expf(-zm));
         if (max_pred) max_pred[c] = zm;
-        if (g_pred) g_pred[c] = 0.5f * (sb - y) / (float)C;
-        if (g_max) g_max[c] = 0.5f * (sm - y) / (float)C;
+        if (g_pred) g_pred[c] = 0.5f * db / (float)C;
+        if (g_max) g_max[c] = 0.5f * dm / (float)C;
     }
     l = wave_sum(l);   // C <= 64: one wave
     if (threadIdx.x == 0) *loss = l;
@@ -2197,10 +2199,19 @@ static __global__ void k_loss_head(const float* __restrict__ classes, const floa
 
 int dsmil_agg_loss_head(const float* classes, const float* pred, const int64_t* idx, const float* label,
                         int32_t C, float* loss, float* max_pred, float* g_pred, float* g_max, void* stream) {
+    return dsmil_agg_loss_head_w(classes, pred, idx, label, C, loss, max_pred, g_pred, g_max, nullptr, stream);
+}
+
+int dsmil_agg_loss_head_w(const float* classes, const float* pred, const int64_t* idx, const float* label, int32_t C,
+                          float* loss, float* max_pred, float* g_pred, float* g_max, const dsmil_bce_weights* bw,
+                          void* stream) {
     if (!classes || !pred || !idx || !label || !loss || C <= 0) return DSMIL_E_INVALID;
     if (C > 64) return DSMIL_E_UNSUPPORTED;
+    const float* pos_weight = bw ? bw->pos_weight : nullptr;
+    const float* weight = bw ? bw->weight : nullptr;
+    if (((uintptr_t)pos_weight | (uintptr_t)weight) % 4) return DSMIL_E_ALIGN;
     hipLaunchKernelGGL(k_loss_head, dim3(1), dim3(64), 0, (hipStream_t)stream, classes, pred, idx, label, C, loss,
-                       max_pred, g_pred, g_max);
+                       max_pred, g_pred, g_max, pos_weight, weight);
     return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 

@@ -260,7 +260,7 @@ class MILNet(nn.Module):
         run.graph = g
         return run
 
-    def bag_loss(self, feats, label, row_map=None):
+    def bag_loss(self, feats, label, row_map=None, pos_weight=None, weight=None):
         """The training objective of one bag, train_tcga.py:64-71 / train_mil.py, as ONE native forward + loss head
         (and one native backward under autograd):
             bag_feats = feats[row_map]                      (dropout_patches :78-83, folded into the row loads)
@@ -272,7 +272,9 @@ class MILNet(nn.Module):
         of the bf16 rows in front of the call; loss and predictions are the fp32 ones of the forward's fp32 logits);
         everything else — a passing_v model and rows that require a gradient included, whose forward and backward are
         native all the same (value projection + aggregator + the row-gradient kernels) — composes the same objective
-        around ``self(x)``."""
+        around ``self(x)``.  ``pos_weight`` / ``weight``: the class weights of BCEWithLogitsLoss(weight, pos_weight)
+        (train_mil.py:172-173), each None or a tensor of 1 or C elements; the fused path hands them to the weighted loss head
+        (dsmil_agg_loss_head_w / _bags_w) as fp32 [C] device vectors (ops.bce_class_weights)."""
         bc = self.b_classifier
         if (self._fused(feats) and self._loss_dtype(feats) and not bc.passing_v and not feats.requires_grad
                 and self.i_classifier.fc[0].out_features <= 64):   # dsmil_agg_loss_head: one wave of classes; more take the torch expression
@@ -284,13 +286,14 @@ class MILNet(nn.Module):
                 torch._assert_async((row_map.min() >= 0) & (row_map.max() < feats.shape[0]),
                                     "row_map index out of range")
             _, w = self._lin_weights()
-            return _BagLossFunction.apply(feats, label, row_map, None, *w.values(), bc.nonlinear)
+            cw = ops.bce_class_weights(pos_weight, weight, self.i_classifier.fc[0].out_features, feats.device)
+            return _BagLossFunction.apply(feats, label, row_map, None, *w.values(), bc.nonlinear, *cw)
         x = feats if row_map is None else feats.index_select(0, row_map)
         ins, bag, _, _ = self._forward(x, _f32_out=True)
         mx, _ = torch.max(ins, 0)
         y = label.view(1, -1).to(bag.dtype)
-        loss = 0.5 * F.binary_cross_entropy_with_logits(bag.view(1, -1), y) + \
-            0.5 * F.binary_cross_entropy_with_logits(mx.view(1, -1), y)
+        loss = 0.5 * F.binary_cross_entropy_with_logits(bag.view(1, -1), y, weight, pos_weight=pos_weight) + \
+            0.5 * F.binary_cross_entropy_with_logits(mx.view(1, -1), y, weight, pos_weight=pos_weight)
         return loss, bag, mx
 
     @torch.no_grad()
@@ -365,7 +368,7 @@ class MILNet(nn.Module):
             o += n
         return tuple(torch.cat([t[i] for t in outs], dim=0) for i in range(4))
 
-    def batch_loss(self, feats, lengths, labels, row_map=None, per_bag=False):
+    def batch_loss(self, feats, lengths, labels, row_map=None, per_bag=False, pos_weight=None, weight=None):
         """The training objective of a BATCH of bags: loss = mean_b loss_b with loss_b the objective of ``bag_loss``
         (train_tcga.py:64-71) for bag b — one optimiser step per batch is this project's addition, the reference steps once
         per bag.  ``lengths`` count LOGICAL rows; ``row_map`` (int64 [sum(lengths)]) maps a logical row to a row of feats
@@ -374,7 +377,7 @@ class MILNet(nn.Module):
         CUDA fp32 rows that need no gradient, v = Identity, C <= 64: one native batched forward + batched loss head, and one
         native batched backward with the sparse max-stream gradient.  bf16-stored rows (K % 8 == 0) likewise, through the
         bf16 forward and dsmil_agg_backward_bags_bf16; a row map is one index_select of the bf16 rows in front of the call.  Otherwise the same objective from torch ops around
-        ``forward_batch``."""
+        ``forward_batch``.  ``pos_weight`` / ``weight`` as in ``bag_loss``."""
         lengths = [int(n) for n in lengths]
         n = len(lengths)
         labels = labels.reshape(n, -1)
@@ -386,14 +389,15 @@ class MILNet(nn.Module):
             if row_map is not None and row_map.numel():
                 torch._assert_async((row_map.min() >= 0) & (row_map.max() < feats.shape[0]), "row_map index out of range")
             _, w = self._lin_weights()
-            loss, pred, mx, each = _BagLossFunction.apply(feats, labels, row_map, tuple(lengths), *w.values(), bc.nonlinear)
+            cw = ops.bce_class_weights(pos_weight, weight, self.i_classifier.fc[0].out_features, feats.device)
+            loss, pred, mx, each = _BagLossFunction.apply(feats, labels, row_map, tuple(lengths), *w.values(), bc.nonlinear, *cw)
             return (loss, pred, mx, each) if per_bag else (loss, pred, mx)
         x = feats if row_map is None else feats.index_select(0, row_map)
         ins, pred, _, _ = self._forward_batch(x, lengths, _f32_out=True)
         mx = torch.stack([t.max(0)[0] for t in torch.split(ins, lengths, dim=0)])
         y = labels.to(pred.dtype)
-        each = 0.5 * F.binary_cross_entropy_with_logits(pred, y, reduction="none").mean(1) + \
-            0.5 * F.binary_cross_entropy_with_logits(mx, y, reduction="none").mean(1)
+        each = 0.5 * F.binary_cross_entropy_with_logits(pred, y, weight, pos_weight=pos_weight, reduction="none").mean(1) + \
+            0.5 * F.binary_cross_entropy_with_logits(mx, y, weight, pos_weight=pos_weight, reduction="none").mean(1)
         loss = each.mean()
         return (loss, pred, mx, each.detach()) if per_bag else (loss, pred, mx)
 
@@ -457,19 +461,23 @@ class _BagLossFunction(torch.autograd.Function):
     dense [N,C] instance-logit gradient of train_tcga.py:64-72.  With ``lengths`` (a tuple) the same over a batch of bags
     stored back to back: the batched forward + dsmil_agg_loss_head_bags, loss = the mean of the bags' losses (each bag's own
     loss is a fourth output), backward = dsmil_agg_backward_bags.  bf16-stored rows (no row map): the bf16 forward, the same
-    loss head on its fp32 logits, backward = dsmil_agg_backward_bags_bf16; gradients in the parameters' dtype."""
+    loss head on its fp32 logits, backward = dsmil_agg_backward_bags_bf16; gradients in the parameters' dtype.
+    ``pos_weight`` / ``weight`` (fp32 [C] device vectors or None): the loss head is its class-weighted form
+    (dsmil_agg_loss_head_w / dsmil_agg_loss_head_bags_w); the backward is fed its g_pred / g_max as before."""
 
     @staticmethod
-    def forward(ctx, feats, label, row_map, lengths, fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, nonlinear):
+    def forward(ctx, feats, label, row_map, lengths, fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, nonlinear,
+                pos_weight=None, weight=None):
         w = _wdict(fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, detach=True)
         if lengths is None:
             N = int(row_map.numel()) if row_map is not None else feats.shape[0]
             classes, pred, A, B, idx = ops.agg_forward(feats.detach(), [N], w, nonlinear=nonlinear, row_map=row_map)
-            loss, max_pred, g_pred, g_max = ops.agg_loss_head(classes, pred, idx, label.detach())
+            loss, max_pred, g_pred, g_max = ops.agg_loss_head(classes, pred, idx, label.detach(), pos_weight, weight)
             out = (loss, pred, max_pred)
         else:
             classes, pred, A, B, idx = ops.agg_forward(feats.detach(), lengths, w, nonlinear=nonlinear, row_map=row_map)
-            each, max_pred, g_pred, g_max = ops.agg_loss_head_bags(classes, lengths, pred, idx, label.detach())
+            each, max_pred, g_pred, g_max = ops.agg_loss_head_bags(classes, lengths, pred, idx, label.detach(),
+                                                                   pos_weight=pos_weight, weight=weight)
             out = (each.mean(), pred, max_pred, each)
         ctx.nonlinear, ctx.lengths = nonlinear, lengths
         ctx.save_for_backward(feats, row_map, fc_w, q0_w, q0_b, q2_w, q2_b, fcc_w, A, B, idx, g_pred, g_max, fc_b, fcc_b)
@@ -491,7 +499,7 @@ class _BagLossFunction(torch.autograd.Function):
             scale = g_loss / len(ctx.lengths)
             g = ops.agg_backward_bags(feats, ctx.lengths, w, A, B, idx, g_pred * scale, g_max=g_max * scale, row_map=row_map,
                                       nonlinear=ctx.nonlinear)
-        return (None, None, None, None, *_param_grads(g, w), None)
+        return (None, None, None, None, *_param_grads(g, w), None, None, None)
 
 
 class _AggFunction(torch.autograd.Function):

@@ -610,9 +610,43 @@ def agg_shard_attend(feats, w, crit_rows, vals=None, nonlinear=True):
     return A, ml, B
 
 
-def agg_loss_head(classes, pred, idx, label):
+_bce_cache = _LRU()
+
+
+def bce_class_weights(pos_weight, weight, C, dev):
+    """The class-weight tensors of a BCEWithLogitsLoss (each None, or 1 or ``C`` elements on any device in any float type —
+    train_mil.py:172 builds a 0-dim one) as what the ``_w`` entries read: contiguous fp32 [C] tensors on ``dev`` (None stays
+    None).  Made once per version of the criterion's tensors (_cached)."""
+    if pos_weight is None and weight is None:
+        return None, None
+
+    def make():
+        return tuple(None if t is None else t.detach().to(device=dev, dtype=torch.float32).reshape(-1).expand(C).contiguous()
+                     for t in (pos_weight, weight))
+    key = (str(dev), int(C), _tkey(pos_weight), _tkey(weight))
+    return _cached(_bce_cache, key, dev, [pos_weight, weight], make)
+
+
+def _bce_weights(pos_weight, weight, C, dev):
+    """struct dsmil_bce_weights over the two class-weight vectors of BCEWithLogitsLoss (train_mil.py:52-55), each None or
+    [C] — or None when both are None (the caller then takes the unweighted entry).  Returns (struct, the tensors it points
+    into: hold them until the call is enqueued)."""
+    if pos_weight is None and weight is None:
+        return None, ()
+    keep = []
+    for name, t in (("pos_weight", pos_weight), ("weight", weight)):
+        if t is not None:
+            t = _f32c(t.reshape(-1), name)
+            if t.device != dev or t.numel() != C:
+                raise ValueError(f"{name} must hold {C} elements on {dev} (got {t.numel()} on {t.device})")
+        keep.append(t)
+    return _native.BceWeights(*[(t.data_ptr() if t is not None else 0) for t in keep]), keep
+
+
+def agg_loss_head(classes, pred, idx, label, pos_weight=None, weight=None):
     """dsmil_agg_loss_head: the training objective of one bag (train_tcga.py:67-71) and its logit gradients in one
-    launch.  Returns (loss [] , max_pred [C], g_pred [C], g_max [C])."""
+    launch.  Returns (loss [] , max_pred [C], g_pred [C], g_max [C]).  ``pos_weight`` / ``weight`` ([C] fp32 each, or None):
+    the class weights of BCEWithLogitsLoss(weight, pos_weight) (train_mil.py:52-55) — dsmil_agg_loss_head_w."""
     classes = _f32c(classes, "classes"); pred = _f32c(pred.reshape(-1), "pred")
     label = _f32c(label.reshape(-1).to(torch.float32), "label")
     idx = _i64c(idx.reshape(-1), "idx")
@@ -620,10 +654,18 @@ def agg_loss_head(classes, pred, idx, label):
     dev = classes.device
     out = torch.empty((1 + 3 * C,), dtype=torch.float32, device=dev)
     loss, max_pred, g_pred, g_max = out[0:1], out[1:1 + C], out[1 + C:1 + 2 * C], out[1 + 2 * C:]
+    bw, keep = _bce_weights(pos_weight, weight, C, dev)
     with torch.cuda.device(dev):
-        rc = _native.lib().dsmil_agg_loss_head(_ptr(classes), _ptr(pred), _ptr(idx), _ptr(label), C, _ptr(loss),
-                                               _ptr(max_pred), _ptr(g_pred), _ptr(g_max), _stream(dev))
-    _native.check(rc, "dsmil_agg_loss_head")
+        if bw is None:
+            entry = "dsmil_agg_loss_head"
+            rc = _native.lib().dsmil_agg_loss_head(_ptr(classes), _ptr(pred), _ptr(idx), _ptr(label), C, _ptr(loss),
+                                                   _ptr(max_pred), _ptr(g_pred), _ptr(g_max), _stream(dev))
+        else:
+            entry = "dsmil_agg_loss_head_w"
+            rc = _native.lib().dsmil_agg_loss_head_w(_ptr(classes), _ptr(pred), _ptr(idx), _ptr(label), C, _ptr(loss),
+                                                     _ptr(max_pred), _ptr(g_pred), _ptr(g_max), ctypes.byref(bw), _stream(dev))
+    _native.check(rc, entry)
+    del keep
     return loss.reshape(()), max_pred, g_pred, g_max
 
 
@@ -719,10 +761,11 @@ def agg_backward(feats, w, A, B, idx, g_pred, g_classes=None, g_A=None, g_B=None
                          row_map, want_g_feats)
 
 
-def agg_loss_head_bags(classes, lengths, pred, idx, labels, offsets=None):
+def agg_loss_head_bags(classes, lengths, pred, idx, labels, offsets=None, pos_weight=None, weight=None):
     """dsmil_agg_loss_head_bags: the objective of ``agg_loss_head`` for every bag of a batch stored back to back, one
     launch.  classes [total,C], pred / idx / labels [n_bags,C] (the batched forward's outputs; labels 0/1).  Returns
-    (loss [n_bags], max_pred [n_bags,C], g_pred [n_bags,C], g_max [n_bags,C]) — the gradients of each bag's OWN loss."""
+    (loss [n_bags], max_pred [n_bags,C], g_pred [n_bags,C], g_max [n_bags,C]) — the gradients of each bag's OWN loss.
+    ``pos_weight`` / ``weight`` as in ``agg_loss_head``: dsmil_agg_loss_head_bags_w."""
     classes = _f32c(classes, "classes")
     n, C = len(lengths), classes.shape[1]
     pred = _f32c(pred.reshape(n, C), "pred")
@@ -732,10 +775,19 @@ def agg_loss_head_bags(classes, lengths, pred, idx, labels, offsets=None):
     off = offsets if offsets is not None else offsets_tensor(lengths, dev)
     loss = torch.empty((n,), dtype=torch.float32, device=dev)
     max_pred, g_pred, g_max = (torch.empty((n, C), dtype=torch.float32, device=dev) for _ in range(3))
+    bw, keep = _bce_weights(pos_weight, weight, C, dev)
     with torch.cuda.device(dev):
-        rc = _native.lib().dsmil_agg_loss_head_bags(_ptr(classes), _ptr(off), _ptr(pred), _ptr(idx), _ptr(labels), n, C,
-                                                    _ptr(loss), _ptr(max_pred), _ptr(g_pred), _ptr(g_max), _stream(dev))
-    _native.check(rc, "dsmil_agg_loss_head_bags")
+        if bw is None:
+            entry = "dsmil_agg_loss_head_bags"
+            rc = _native.lib().dsmil_agg_loss_head_bags(_ptr(classes), _ptr(off), _ptr(pred), _ptr(idx), _ptr(labels), n, C,
+                                                        _ptr(loss), _ptr(max_pred), _ptr(g_pred), _ptr(g_max), _stream(dev))
+        else:
+            entry = "dsmil_agg_loss_head_bags_w"
+            rc = _native.lib().dsmil_agg_loss_head_bags_w(_ptr(classes), _ptr(off), _ptr(pred), _ptr(idx), _ptr(labels), n, C,
+                                                          _ptr(loss), _ptr(max_pred), _ptr(g_pred), _ptr(g_max),
+                                                          ctypes.byref(bw), _stream(dev))
+    _native.check(rc, entry)
+    del keep
     return loss, max_pred, g_pred, g_max
 
 
@@ -793,13 +845,14 @@ def agg_train_step(feats, label, params, exp_avg, exp_avg_sq, step, lr, betas, e
 
 
 def agg_train_step_bags(feats, lengths, labels, params, exp_avg, exp_avg_sq, step, lr, betas, eps, weight_decay,
-                        nonlinear=True, row_map=None, offsets=None):
+                        nonlinear=True, row_map=None, offsets=None, pos_weight=None, weight=None):
     """dsmil_agg_train_step_bags / dsmil_agg_train_step_bags_bf16 (by ``feats.dtype``): ONE optimiser step on a batch of
     bags stored back to back as ONE native call — batched forward, the mean over the bags of ``agg_train_step``'s objective,
     batched backward, Adam.  ``lengths``: the bags' LOGICAL row counts; labels [n_bags, C]; ``params`` / ``exp_avg`` /
     ``exp_avg_sq`` / ``step`` as in ``agg_train_step`` (updated IN PLACE).  ``row_map``: int64 [sum(lengths)] as in
     ``agg_forward``; the bf16 entry has none, so bf16 rows are gathered by one index_select in front of the call (as
-    MILNet.batch_loss does).  Returns (loss [1], loss_each [n_bags]) as device tensors (no host sync)."""
+    MILNet.batch_loss does).  ``pos_weight`` / ``weight`` as in ``agg_loss_head``: the ``_w`` form of the same entry (same
+    launches, same workspace).  Returns (loss [1], loss_each [n_bags]) as device tensors (no host sync)."""
     bf16 = feats.dtype == torch.bfloat16
     if not feats.is_cuda:
         raise RuntimeError("feats must be a CUDA(HIP) tensor for the native path")
@@ -828,11 +881,15 @@ def agg_train_step_bags(feats, lengths, labels, params, exp_avg, exp_avg_sq, ste
     entry = "dsmil_agg_train_step_bags_bf16" if bf16 else "dsmil_agg_train_step_bags"
     ws = _workspace(dev, getattr(L, entry + "_workspace_bytes")(n, total, K, C, 1 if nonlinear else 0))
     rmap = () if bf16 else (_ptr(row_map),)
+    bw, keep_w = _bce_weights(pos_weight, weight, C, dev)
+    tail = ()
+    if bw is not None:
+        entry, tail = entry + "_w", (ctypes.byref(bw),)
     with torch.cuda.device(dev):
         rc = getattr(L, entry)(_ptr(feats), _ptr(off), n, total, max(lengths), *rmap, _ptr(labels), ctypes.byref(p),
-                               ctypes.byref(st), _ptr(each), _ptr(loss), _ptr(ws), ws.numel(), _stream(dev))
+                               ctypes.byref(st), _ptr(each), _ptr(loss), _ptr(ws), ws.numel(), *tail, _stream(dev))
     _native.check(rc, entry)
-    del keep
+    del keep, keep_w
     return loss, each
 
 

@@ -9,6 +9,7 @@ being re-read from disk every iteration (train_tcga.py:62; 288 GB of HBM holds w
 sets), and ``dropout_patches`` with rate 0 skips the full-bag row permutation
 (train_tcga.py:65,78-83: the aggregator is permutation-invariant).
 """
+import collections
 import copy
 import datetime
 import glob
@@ -102,17 +103,34 @@ def dropout_patches(feats, p):
     return feats if idx is None else feats.index_select(0, idx)
 
 
-def _is_plain_bce(criterion):
-    return (isinstance(criterion, nn.BCEWithLogitsLoss) and criterion.reduction == "mean"
-            and criterion.weight is None and criterion.pos_weight is None)
+def _native_bce(criterion, C=None):
+    """Whether the native objective computes ``criterion``: None if not, else its (pos_weight, weight) — each None or the
+    criterion's own tensor.  Eligible: a BCEWithLogitsLoss (a subclass only while it keeps the stock ``forward``) with
+    reduction "mean" whose pos_weight and weight are each None or per class — 0-dim, [1], [C] or [1, C] (train_mil.py:172
+    builds a 0-dim pos_weight) — and, when ``C`` is given, hold 1 or C elements.  The model side broadcasts them to fp32
+    [C] device vectors (ops.bce_class_weights)."""
+    if not isinstance(criterion, nn.BCEWithLogitsLoss) or type(criterion).forward is not nn.BCEWithLogitsLoss.forward:
+        return None
+    if criterion.reduction != "mean":
+        return None
+    for t in (criterion.pos_weight, criterion.weight):
+        if t is None:
+            continue
+        if not (torch.is_tensor(t) and t.is_floating_point() and (t.dim() <= 1 or (t.dim() == 2 and t.shape[0] == 1))):
+            return None
+        if t.numel() < 1 or (C is not None and t.numel() not in (1, int(C))):
+            return None
+    return criterion.pos_weight, criterion.weight
 
 
 def bag_loss(milnet, criterion, bag_feats, bag_label, row_map=None):
     """train_tcga.py:64-71.  ``row_map``: dropout_patches as an index list (rows of bag_feats that enter the bag).
-    With the stock criterion and a MILNet(FCLayer, BClassifier) the whole objective is one native forward + loss
-    head (MILNet.bag_loss); otherwise the same expression from torch ops."""
-    if _is_plain_bce(criterion) and hasattr(milnet, "bag_loss"):
-        return milnet.bag_loss(bag_feats, bag_label, row_map)
+    With a criterion the native objective computes (_native_bce: the stock BCEWithLogitsLoss, or one with per-class
+    pos_weight / weight) and a MILNet(FCLayer, BClassifier) the whole objective is one native forward + loss head
+    (MILNet.bag_loss); otherwise the same expression from torch ops."""
+    bce = _native_bce(criterion, bag_label.numel()) if hasattr(milnet, "bag_loss") else None
+    if bce is not None:
+        return milnet.bag_loss(bag_feats, bag_label, row_map, *bce)
     if row_map is not None:
         bag_feats = bag_feats.index_select(0, row_map)
     ins_prediction, bag_prediction, _, _ = milnet(bag_feats)
@@ -124,10 +142,12 @@ def bag_loss(milnet, criterion, bag_feats, bag_label, row_map=None):
 
 def batch_loss(milnet, criterion, feats, lengths, labels, row_map=None):
     """The objective of a group of bags stored back to back (``bags_per_step`` > 1): mean over the bags of ``bag_loss``'s
-    objective.  Returns (loss, pred [n,C], max_pred [n,C], each bag's own loss [n], detached).  Stock criterion and a model
-    with ``batch_loss``: MILNet.batch_loss (native on the GPU); otherwise the same expression from torch ops, bag by bag."""
-    if _is_plain_bce(criterion) and hasattr(milnet, "batch_loss"):
-        return milnet.batch_loss(feats, lengths, labels, row_map, per_bag=True)
+    objective.  Returns (loss, pred [n,C], max_pred [n,C], each bag's own loss [n], detached).  A criterion of _native_bce
+    and a model with ``batch_loss``: MILNet.batch_loss (native on the GPU); otherwise the same expression from torch ops,
+    bag by bag."""
+    bce = _native_bce(criterion, labels.numel() // max(1, len(lengths))) if hasattr(milnet, "batch_loss") else None
+    if bce is not None:
+        return milnet.batch_loss(feats, lengths, labels, row_map, True, *bce)
     x = feats if row_map is None else feats.index_select(0, row_map)
     each, preds, maxes = [], [], []
     for bag, label in zip(torch.split(x, [int(n) for n in lengths], dim=0), labels.reshape(len(lengths), -1)):
@@ -147,13 +167,17 @@ class FusedTrainStep:
 
     Eligible (``FusedTrainStep.create`` returns None otherwise, and ``train`` keeps the generic autograd path):
     MILNet(FCLayer, BClassifier) with v = Identity on a GPU, every parameter trainable fp32, the stock
-    BCEWithLogitsLoss, and a plain torch.optim.Adam (one parameter group holding exactly the model's parameters; amsgrad,
+    BCEWithLogitsLoss or one with per-class pos_weight / weight (_native_bce; train_mil.py:172-173 — the weighted step
+    always goes through ``step_bags``, a lone bag as a batch of one: dsmil_agg_train_step_bags_w / _bf16_w),
+    and a plain torch.optim.Adam (one parameter group holding exactly the model's parameters; amsgrad,
     maximize, capturable, differentiable off).  The optimiser's own state tensors (exp_avg, exp_avg_sq) are updated in
     place, ``step`` is written back by ``sync()`` — so optimizer.state_dict(), LR schedulers and a later generic step see a
     consistent optimiser.  ``.grad`` is not populated (as after zero_grad(set_to_none=True))."""
 
-    def __init__(self, milnet, optimizer, params):
+    def __init__(self, milnet, optimizer, params, bce=(None, None)):
         self.net, self.opt, self.params = milnet, optimizer, params
+        self.bce = bce   # the criterion's own (pos_weight, weight) tensors, each None or 1 / C elements
+        self.weighted = any(t is not None for t in bce)
         self.group = optimizer.param_groups[0]
         self.m, self.v, steps = [], [], []
         for p in params:
@@ -178,7 +202,10 @@ class FusedTrainStep:
         from .modules import BClassifier, FCLayer
         try:
             ic, bc = milnet.i_classifier, milnet.b_classifier
-            if not (isinstance(ic, FCLayer) and isinstance(bc, BClassifier)) or bc.passing_v or not _is_plain_bce(criterion):
+            if not (isinstance(ic, FCLayer) and isinstance(bc, BClassifier)) or bc.passing_v:
+                return None
+            bce = _native_bce(criterion, ic.fc[0].out_features)
+            if bce is None:
                 return None
             if type(optimizer) is not torch.optim.Adam or len(optimizer.param_groups) != 1:
                 return None
@@ -195,7 +222,7 @@ class FusedTrainStep:
                 return None
             if lin.out_features > 64:
                 return None
-            return FusedTrainStep(milnet, optimizer, params)
+            return FusedTrainStep(milnet, optimizer, params, bce)
         except (AttributeError, KeyError):
             return None
 
@@ -215,18 +242,20 @@ class FusedTrainStep:
             # (as MILNet.batch_loss: an out-of-range index would be an out-of-bounds device read in the row loads)
             torch._assert_async((row_map.min() >= 0) & (row_map.max() < feats.shape[0]), "row_map index out of range")
         with torch.no_grad():
+            # (per version of the criterion's tensors: a pos_weight edited in place between steps is picked up)
+            pos_weight, weight = ops.bce_class_weights(*self.bce, self.params[0].shape[0], feats.device)
             loss, each = ops.agg_train_step_bags(feats, lengths, labels, [p.data if p is not None else None for p in self.params],
                                                  self.m, self.v, self.step + 1, g["lr"], g["betas"], g["eps"], g["weight_decay"],
-                                                 nonlinear=self.nonlinear, row_map=row_map)
+                                                 nonlinear=self.nonlinear, row_map=row_map, pos_weight=pos_weight, weight=weight)
         self.step += 1   # only once the native step was enqueued (see __call__)
         torch.autograd.graph.increment_version(self._live)
         return loss.reshape(()), each
 
     def __call__(self, bag_feats, bag_label, row_map=None):
         """One optimiser step on one bag; returns the loss (0-dim device tensor, detached).  fp32 bags: dsmil_agg_train_step;
-        bf16-stored bags: ``step_bags`` with one length."""
+        bf16-stored bags, and every bag under a class-weighted criterion: ``step_bags`` with one length."""
         from . import ops
-        if bag_feats.dtype == torch.bfloat16:
+        if bag_feats.dtype == torch.bfloat16 or self.weighted:
             n = int(row_map.numel()) if row_map is not None else bag_feats.shape[0]
             return self.step_bags(bag_feats, [n], bag_label.reshape(1, -1), row_map)[0]
         g = self.group
@@ -659,9 +688,68 @@ def group_bags(X, bag_ids, labels):
     return bags, np.asarray(ys, np.float32)
 
 
+# False: mil_epoch_train / mil_epoch_test keep the reference's loop on the GPU too (as training.train's args.fused_step)
+mil_fused_step = True
+_mil_resident = collections.OrderedDict()
+
+
+def _mil_device_bags(bags, ys, device):
+    """The data set of train_mil.py on the training device, uploaded ONCE per (bags, device) call site instead of once per
+    bag per step (train_mil.py:47,49): (rows [sum n_i, F] fp32 — bag i is rows starts[i]:starts[i+1] —, starts, labels
+    [n_bags] fp32).  A small cache (four data sets) that holds ``bags`` itself, so its id stays its own; None for bags the
+    native step does not take as they are (not 2-D fp32 of one width, or empty)."""
+    key = (id(bags), str(device))
+    ent = _mil_resident.get(key)
+    ys32 = np.asarray(ys, np.float32)
+    if ent is not None and len(ent[1]) == len(bags) and all(a is b for a, b in zip(ent[1], bags)) and np.array_equal(ent[2], ys32):
+        _mil_resident.move_to_end(key)
+        return ent[3]
+    ok = len(bags) > 0 and all(isinstance(b, np.ndarray) and b.dtype == np.float32 and b.ndim == 2 and len(b) > 0
+                               and b.shape[1] == bags[0].shape[1] for b in bags)
+    res = None
+    if ok:
+        starts = np.zeros(len(bags) + 1, np.int64)
+        np.cumsum([len(b) for b in bags], out=starts[1:])
+        res = (torch.from_numpy(np.concatenate(bags)).to(device), starts, torch.from_numpy(ys32.copy()).to(device))
+    _mil_resident[key] = (bags, list(bags), ys32.copy(), res)
+    while len(_mil_resident) > 4:
+        _mil_resident.popitem(last=False)
+    return res
+
+
+def _mil_native(milnet, criterion, device):
+    """Whether mil_epoch_train / mil_epoch_test take the native calls: a GPU run of a one-class MILNet whose criterion the
+    native objective computes (_native_bce: train_mil.py:172-173 builds BCEWithLogitsLoss(pos_weight) — positionally, so its
+    0-dim tensor is the criterion's ``weight``), not switched off."""
+    if not mil_fused_step or torch.device(device).type != "cuda" or not hasattr(milnet, "batch_loss"):
+        return False
+    try:
+        return milnet.i_classifier.fc[0].out_features == 1 and _native_bce(criterion, 1) is not None
+    except (AttributeError, IndexError, TypeError):
+        return False
+
+
 def mil_epoch_train(bags, ys, idx, milnet, criterion, optimizer, device):
-    """train_mil.py:42-59 (instances of a bag are shuffled, :46)."""
+    """train_mil.py:42-59 (instances of a bag are shuffled, :46).  On the GPU with the reference's model, criterion and
+    optimiser (FusedTrainStep.create) a bag's whole step is ONE native call (dsmil_agg_train_step_bags_w on a batch of one):
+    the bags are resident on the device (_mil_device_bags), the instance shuffle of :46 is the step's row map — the same
+    np.random.permutation calls in the same order, uploaded once per epoch —, Adam runs inside the call and the losses are
+    summed on the device and read once per epoch (the reference prints nothing per bag).  Otherwise the reference's lines."""
     milnet.train()
+    fused = FusedTrainStep.create(milnet, criterion, optimizer) if _mil_native(milnet, criterion, device) else None
+    data = _mil_device_bags(bags, ys, device) if fused is not None else None
+    if data is not None and len(idx):
+        rows, starts, labels = data
+        perms = [np.random.permutation(len(bags[i])) + starts[i] for i in idx]
+        cuts = np.cumsum([0] + [len(p) for p in perms])
+        maps = torch.from_numpy(np.concatenate(perms)).to(device)
+        losses = []
+        try:
+            for k, i in enumerate(idx):
+                losses.append(fused(rows, labels[i:i + 1].view(1, 1), maps[cuts[k]:cuts[k + 1]]))
+        finally:
+            fused.sync()   # the optimiser's own step count (LR schedulers, state_dict, a later generic step)
+        return float(torch.stack(losses).double().sum().item()) / len(idx)
     total = 0.0
     for i in idx:
         optimizer.zero_grad()
@@ -679,8 +767,18 @@ def mil_epoch_train(bags, ys, idx, milnet, criterion, optimizer, device):
 
 @torch.no_grad()
 def mil_epoch_test(bags, ys, idx, milnet, criterion, device):
-    """train_mil.py:61-80."""
+    """train_mil.py:61-80.  On the GPU with a criterion of the native objective (_mil_native): all bags of ``idx`` in ONE
+    batched forward + loss head (MILNet.batch_loss over the resident rows), sigmoid on the device, one transfer."""
     milnet.eval()
+    data = _mil_device_bags(bags, ys, device) if _mil_native(milnet, criterion, device) else None
+    if data is not None and len(idx):
+        rows, starts, labels = data
+        where = torch.from_numpy(np.asarray(idx, np.int64)).to(device)
+        row_map = torch.from_numpy(np.concatenate([np.arange(starts[i], starts[i + 1]) for i in idx])).to(device)
+        loss, pred, _ = milnet.batch_loss(rows, [len(bags[i]) for i in idx], labels.index_select(0, where).view(-1, 1), row_map,
+                                          False, *_native_bce(criterion, 1))
+        out = torch.cat([loss.reshape(1), torch.sigmoid(pred).reshape(-1)]).double().cpu().numpy()   # train_mil.py:77
+        return float(out[0]), out[1:]
     total, preds = 0.0, []
     for i in idx:
         x = torch.from_numpy(bags[i]).to(device)

@@ -217,6 +217,31 @@ int dsmil_agg_forward_ex(const float* feats, const float* vals, const int64_t* o
 int dsmil_agg_loss_head(const float* classes, const float* pred, const int64_t* idx, const float* label,
                         int32_t C, float* loss, float* max_pred, float* g_pred, float* g_max, void* stream);
 
+/* Class weights of the objective: the criterion train_mil.py:172-173 builds, BCEWithLogitsLoss(pos_weight), and torch's
+ * general BCEWithLogitsLoss(weight, pos_weight), as train_mil.py:52-55 applies it to the bag and the max-instance logits.
+ * Per logit z of class c with label y (torch's binary_cross_entropy_with_logits):
+ *     lw = 1 + (pos_weight[c] - 1) y
+ *     term = weight[c] ((1 - y) z + lw (max(-z, 0) + log1p(exp(-|z|))))
+ *     d term / dz = weight[c] ((1 - y) - lw sigma(-z))  =  weight[c] (((pos_weight[c] y + 1) - y) sigma(z) - pos_weight[c] y),
+ *     evaluated in the second form, torch's backward (sigma formed from exp(-|z|): nothing overflows for large |z|)
+ * in place of max(z,0) - z y + log1p(exp(-|z|)) and sigma(z) - y; the 0.5, the mean over the C classes and a batch's mean
+ * over its bags are unchanged.  Both members are DEVICE pointers, [C] fp32, and either may be NULL (= all ones).
+ * The four *_w entries below have the signature of their unweighted sibling plus `const dsmil_bce_weights*` in front of
+ * `stream`, and the sibling's contract otherwise: same launches, same workspace (the sibling's size query answers for
+ * both), same limits (C <= 64), same order of checks and error codes, all before any launch, so a refused call has changed
+ * nothing.  A NULL struct, or both members NULL, gives the sibling's bits (the sibling IS that call); all-ones vectors agree
+ * with it to rounding.  A weight pointer that is not 4-byte aligned -> DSMIL_E_ALIGN (with the sibling's other alignment
+ * checks; the loss heads have no other: behind their DSMIL_E_INVALID / DSMIL_E_UNSUPPORTED checks).
+ * Added without a change of DSMIL_ABI_VERSION (it stays 6, no existing signature moved): detected by SYMBOL. */
+typedef struct dsmil_bce_weights {
+    const float* pos_weight;   /* [C] or NULL */
+    const float* weight;       /* [C] or NULL */
+} dsmil_bce_weights;
+/* dsmil_agg_loss_head with class weights (train_mil.py:172-173, :52-55). */
+int dsmil_agg_loss_head_w(const float* classes, const float* pred, const int64_t* idx, const float* label, int32_t C,
+                          float* loss, float* max_pred, float* g_pred, float* g_max, const dsmil_bce_weights* bw,
+                          void* stream);
+
 /* FCLayer.forward alone (dsmil.py:10-12): classes[total_rows, C] = feats @ fc_w^T + fc_b. */
 int dsmil_fc_forward(const float* feats, int64_t total_rows, int32_t K, int32_t C,
                      const float* fc_w, const float* fc_b, float* classes, void* stream);
@@ -310,6 +335,11 @@ int dsmil_agg_backward_bags(const float* feats, const float* vals, const int64_t
 int dsmil_agg_loss_head_bags(const float* classes, const int64_t* offsets, const float* pred, const int64_t* idx,
                              const float* labels, int32_t n_bags, int32_t C, float* loss, float* max_pred,
                              float* g_pred, float* g_max, void* stream);
+/* dsmil_agg_loss_head_bags with class weights (train_mil.py:172-173, :52-55; see dsmil_bce_weights): the same [C] vectors
+ * for every bag of the batch. */
+int dsmil_agg_loss_head_bags_w(const float* classes, const int64_t* offsets, const float* pred, const int64_t* idx,
+                               const float* labels, int32_t n_bags, int32_t C, float* loss, float* max_pred,
+                               float* g_pred, float* g_max, const dsmil_bce_weights* bw, void* stream);
 
 /* ---- the batched aggregator backward on bf16-STORED rows (training on a bf16 feature cache) -----------------------------
  * Replaces what autograd derives for `loss.backward()` in train_tcga.py:60-73 when the bag's rows are stored in bfloat16
@@ -494,6 +524,18 @@ int dsmil_agg_train_step_bags_bf16(const void* feats_bf16, const int64_t* offset
                                    int64_t max_rows, const float* labels, const dsmil_agg_params* p,
                                    const dsmil_adam_state* opt, float* loss_each, float* loss, void* ws, size_t ws_bytes,
                                    void* stream);
+/* dsmil_agg_train_step_bags / _bf16 with class weights in the objective (train_mil.py:172-173, :52-55; see
+ * dsmil_bce_weights): the body of train_mil.py:42-59 for a batch of one — the same launch sequence, the weights enter the
+ * one launch of the objective.  ws: the sibling's size query.  The weight pointers are checked with the other 4-byte
+ * operands (DSMIL_E_ALIGN, behind DSMIL_E_INVALID and DSMIL_E_UNSUPPORTED). */
+int dsmil_agg_train_step_bags_w(const float* feats, const int64_t* offsets, int32_t n_bags, int64_t total_rows,
+                                int64_t max_rows, const int64_t* row_map, const float* labels, const dsmil_agg_params* p,
+                                const dsmil_adam_state* opt, float* loss_each, float* loss, void* ws, size_t ws_bytes,
+                                const dsmil_bce_weights* bw, void* stream);
+int dsmil_agg_train_step_bags_bf16_w(const void* feats_bf16, const int64_t* offsets, int32_t n_bags, int64_t total_rows,
+                                     int64_t max_rows, const float* labels, const dsmil_agg_params* p,
+                                     const dsmil_adam_state* opt, float* loss_each, float* loss, void* ws, size_t ws_bytes,
+                                     const dsmil_bce_weights* bw, void* stream);
 
 /* ---- patch embedder: ResNet-18 with InstanceNorm2d, fc = Identity --------------------------
  * Replaces the torchvision backbone that compute_feats.py:157,170 builds and dsmil.IClassifier
