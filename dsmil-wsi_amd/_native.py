@@ -270,6 +270,12 @@ SIGNATURES = {
                                        ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
                                        ctypes.POINTER(ctypes.c_int64), ctypes.c_int64, ctypes.c_double, ctypes.c_double,
                                        ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
+    # NT-Xent (SimCLR pre-training of the embedder)
+    "dsmil_ntxent_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
+    "dsmil_ntxent_forward": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_int, c_f32p,
+                                            c_f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "dsmil_ntxent_backward": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_int, c_f32p,
+                                             c_f32p, c_f32p, c_f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "dsmil_agg_forward": (ctypes.c_int, [c_f32p, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64,
                                          ctypes.c_int64, ctypes.POINTER(AggParams), c_f32p, c_f32p,
                                          c_f32p, c_f32p, c_f32p, c_i64p, ctypes.c_void_p,

@@ -1470,3 +1470,48 @@ def jpeg_decode(blobs, device, size=None, stats=None, out=None):
     ``out``: a uint8 device tensor with room for [n, H, W, 3] (a caller's staging buffer); the result is a view of it.
     (= jpeg_decode_begin + jpeg_decode_end, the two halves a pipelining caller uses.)"""
     return jpeg_decode_end(jpeg_decode_begin(blobs, device, size=size, out=out), stats=stats)[0]
+
+
+def _ntxent_operands(zis, zjs):
+    zis = _f32c(zis, "zis"); zjs = _f32c(zjs, "zjs")
+    if zis.dim() != 2 or zis.shape != zjs.shape or zis.device != zjs.device:
+        raise RuntimeError(f"zis and zjs must be [n, d] tensors of one shape on one device (got {tuple(zis.shape)}, "
+                           f"{tuple(zjs.shape)})")
+    n, d = zis.shape
+    nbytes = _native.lib().dsmil_ntxent_workspace_bytes(n, d)
+    if nbytes == 0:
+        raise RuntimeError(f"dsmil_ntxent: unsupported shape n = {n}, d = {d} (1 <= n <= 65536, 1 <= d <= 4096)")
+    return zis, zjs, n, d, nbytes
+
+
+def ntxent_forward(zis, zjs, temperature, cosine=True):
+    """dsmil_ntxent_forward: the NT-Xent loss of SimCLR (simclr/loss/nt_xent.py:47-65) for the projections ``zis``, ``zjs``
+    [n, d] fp32 of the two views.  Returns (loss [], lse [2n]); ``lse`` is what ntxent_backward reads.  No host sync."""
+    zis, zjs, n, d, nbytes = _ntxent_operands(zis, zjs)
+    dev = zis.device
+    out = torch.empty((1 + 2 * n,), dtype=torch.float32, device=dev)
+    loss, lse = out[0:1], out[1:]
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, nbytes)
+        rc = _native.lib().dsmil_ntxent_forward(_ptr(zis), _ptr(zjs), n, d, float(temperature), 1 if cosine else 0, _ptr(loss),
+                                                _ptr(lse), _ptr(ws), ws.numel(), _stream(dev))
+    _native.check(rc, "dsmil_ntxent_forward")
+    return loss.reshape(()), lse
+
+
+def ntxent_backward(zis, zjs, temperature, lse, g_loss, cosine=True):
+    """dsmil_ntxent_backward: (g_zis, g_zjs) [n, d] for the upstream gradient ``g_loss`` (a device scalar, read on the
+    device).  ``lse`` is ntxent_forward's; the workspace need not be the forward's."""
+    zis, zjs, n, d, nbytes = _ntxent_operands(zis, zjs)
+    dev = zis.device
+    lse = _f32c(lse.reshape(-1), "lse")
+    g_loss = _f32c(g_loss.reshape(-1), "g_loss")
+    if lse.numel() != 2 * n or g_loss.numel() != 1:
+        raise RuntimeError("lse must have 2n elements and g_loss one")
+    g = torch.empty((2, n, d), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, nbytes)
+        rc = _native.lib().dsmil_ntxent_backward(_ptr(zis), _ptr(zjs), n, d, float(temperature), 1 if cosine else 0, _ptr(lse),
+                                                 _ptr(g_loss), _ptr(g[0]), _ptr(g[1]), _ptr(ws), ws.numel(), _stream(dev))
+    _native.check(rc, "dsmil_ntxent_backward")
+    return g[0], g[1]

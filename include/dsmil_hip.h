@@ -875,6 +875,26 @@ typedef struct dsmil_agg_route {
 /* Fills *route for *call.  DSMIL_E_INVALID for null pointers or non-positive sizes, else DSMIL_OK.  HOST function. */
 int dsmil_agg_forward_route(const dsmil_agg_call* call, dsmil_agg_route* route);
 
+/* NT-Xent, the SimCLR pre-training loss of the embedder.  Replaces NTXentLoss.forward (simclr/loss/nt_xent.py:47-65: the
+ * concatenation, the [2n, 2n] similarity matrix of :40-45 (cosine) or :33-38 (dot), the positives / negatives gather of
+ * :53-60 and CrossEntropyLoss(reduction="sum") / 2n of :63-65) and its autograd, without ever forming the matrix:
+ *   zis, zjs     device [n, d] fp32 row-major (the two views' projections); R = cat([zjs, zis]) as nt_xent.py:48
+ *   temperature  > 0;  cosine != 0: cosine similarity with torch's eps = 1e-8 on the norms, 0: dot products
+ *   loss         device [1]:  (1/2n) sum_a [ logsumexp_{b != a}(S_ab / T) - S_{a, (a + n) mod 2n} / T ]
+ *   lse          device [2n]: the rows' log-sum-exp, which the backward reads
+ *   g_loss       device [1]:  the upstream gradient (read on the device: no host synchronisation)
+ *   g_zis, g_zjs device [n, d]: d loss / d zis, d loss / d zjs times g_loss[0]
+ *   ws           device, 256-byte aligned, dsmil_ntxent_workspace_bytes(n, d) bytes: O(n d).  The backward rebuilds what it
+ *                needs from zis / zjs / lse: it does not depend on what a forward left in ws.
+ * 2n <= 2^17 and d <= 4096 (any d: padded to the MFMA k-step), else DSMIL_E_UNSUPPORTED (the size function returns 0).
+ * Arithmetic: two fp16 planes of the (normalised) rows, three plane products per MAC on v_mfma_f32_16x16x32_f16, fp32
+ * accumulation; split partials combined in a fixed order — results are bit-identical from call to call. */
+size_t dsmil_ntxent_workspace_bytes(int64_t n, int d);
+int dsmil_ntxent_forward(const float* zis, const float* zjs, int64_t n, int d, float temperature, int cosine, float* loss,
+                         float* lse, void* ws, size_t ws_bytes, void* stream);
+int dsmil_ntxent_backward(const float* zis, const float* zjs, int64_t n, int d, float temperature, int cosine, const float* lse,
+                          const float* g_loss, float* g_zis, float* g_zjs, void* ws, size_t ws_bytes, void* stream);
+
 /* Measurement hooks (bench.py's roofline leg; no reference counterpart).  While enabled, every
  * launch of a dominant kernel is bracketed by hipEventRecord on its own launch stream (up to 4096
  * launches per channel: 0 = k_query_attend of the aggregator, 1 = k_conv of the embedder);
