@@ -276,6 +276,14 @@ SIGNATURES = {
                                             c_f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "dsmil_ntxent_backward": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_int, c_f32p,
                                              c_f32p, c_f32p, c_f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # SimCLR's two-view augmentation (records: struct dsmil_simclr_view, 12 x 4 bytes, passed by address)
+    "dsmil_simclr_views_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "dsmil_simclr_views": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                          ctypes.c_int64, ctypes.c_int, c_f32p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                          ctypes.c_void_p]),
+    "dsmil_simclr_views_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                               ctypes.c_int64, ctypes.c_int, c_f32p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_size_t]),
     "dsmil_agg_forward": (ctypes.c_int, [c_f32p, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64,
                                          ctypes.c_int64, ctypes.POINTER(AggParams), c_f32p, c_f32p,
                                          c_f32p, c_f32p, c_f32p, c_i64p, ctypes.c_void_p,

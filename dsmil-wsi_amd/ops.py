@@ -1515,3 +1515,74 @@ def ntxent_backward(zis, zjs, temperature, lse, g_loss, cosine=True):
                                                  _ptr(g_loss), _ptr(g[0]), _ptr(g[1]), _ptr(ws), ws.numel(), _stream(dev))
     _native.check(rc, "dsmil_ntxent_backward")
     return g[0], g[1]
+
+
+# ---------------------------------------------------------------------------------------------
+# SimCLR's two-view augmentation on decoded tiles (simclr/data_aug/dataset_wrapper.py:48-58, csrc/simclr_aug.hip)
+# ---------------------------------------------------------------------------------------------
+SIMCLR_FLIP, SIMCLR_JITTER, SIMCLR_GREY, SIMCLR_BLUR = 1, 2, 4, 8      # include/dsmil_hip.h
+# struct dsmil_simclr_view as columns of an int32 [n, 12] array; columns 8..11 hold fp32 bits
+SIMCLR_COLS = ("tile", "i", "j", "h", "w", "flags", "order", "hue", "brightness", "contrast", "saturation", "sigma")
+
+
+def _simclr_check_records(rec, n_tiles, H, W):
+    """Host validation of the records (numpy int32 [n, 12]): the kernel trusts none of this, but answers a bad record with an
+    all-zero view instead of an error."""
+    if rec.ndim != 2 or rec.shape[1] != 12 or rec.dtype != np.int32:
+        raise ValueError("view records must be int32 [n_views, 12] (struct dsmil_simclr_view)")
+    tile, i, j, h, w, flags, order, hue = (rec[:, k].astype(np.int64) for k in range(8))
+    fl = np.ascontiguousarray(rec[:, 8:12]).view(np.float32)
+    if ((tile < 0) | (tile >= n_tiles)).any():
+        raise ValueError(f"a view names a tile outside the batch of {n_tiles}")
+    if ((h < 1) | (w < 1) | (i < 0) | (j < 0) | (i + h > H) | (j + w > W)).any():
+        raise ValueError(f"a view's crop lies outside its {H} x {W} tile")
+    if ((flags < 0) | (flags > 15)).any() or ((hue < 0) | (hue > 255)).any():
+        raise ValueError("view flags must be a combination of SIMCLR_* and the hue byte within 0..255")
+    jit = (flags & SIMCLR_JITTER) != 0
+    ops4 = np.stack([(order >> (2 * k)) & 3 for k in range(4)], 1)
+    if ((order < 0) | (order > 255)).any() or (np.sort(ops4[jit], 1) != np.arange(4)).any():
+        raise ValueError("a jittered view's order must be a permutation of 0..3, two bits per position")
+    if not (np.isfinite(fl[jit, :3]).all() and (fl[jit, :3] >= 0).all()):
+        raise ValueError("jitter factors must be finite and non-negative")
+    blur = (flags & SIMCLR_BLUR) != 0
+    if not (np.isfinite(fl[blur, 3]).all() and (fl[blur, 3] > 0).all()):
+        raise ValueError("a blurred view's sigma must be finite and positive")
+
+
+def simclr_views(tiles_u8, params, size, out="float"):
+    """dsmil_simclr_views: SimCLR's augmentation chain (crop + Pillow-bilinear resize, flip, colour jitter, greyscale, Gaussian
+    blur) for one record per output view.  ``tiles_u8``: uint8 [n, H, W, 3] (what jpeg_decode returns); ``params``: a
+    simclr.ViewParams (or anything with ``.records``, CPU int32 [n_views, 12]); ``size`` = S.  Returns fp32 [n_views, 3, S, S]
+    (byte / 255, ``out="float"``) or the bytes as uint8 [n_views, S, S, 3] (``out="uint8"``).  Device tiles: one launch on the
+    current stream, no host synchronisation (the records go up in one copy, asynchronous when they are pinned).  CPU tiles take
+    dsmil_simclr_views_host, the same arithmetic compiled for the host."""
+    if out not in ("float", "uint8"):
+        raise ValueError('out must be "float" or "uint8"')
+    if tiles_u8.dtype != torch.uint8 or tiles_u8.dim() != 4 or tiles_u8.shape[3] != 3:
+        raise ValueError("tiles must be a uint8 tensor [n, H, W, 3]")
+    n_tiles, H, W, _ = tiles_u8.shape
+    S = int(size)
+    rec = params.records
+    if rec.is_cuda or rec.dtype != torch.int32 or not rec.is_contiguous():
+        raise ValueError("params.records must be a contiguous CPU int32 tensor")
+    n_views = rec.shape[0]
+    L = _native.lib()
+    if n_tiles < 1 or n_views < 1 or L.dsmil_simclr_views_workspace_bytes(n_views, H, W, S) == 0:
+        raise ValueError(f"simclr_views: unsupported shape: {n_tiles} tiles of {H} x {W}, {n_views} views of {S} (8 <= H, W <= 256; "
+                         f"17 <= S <= 256 with an odd blur kernel int(0.06 S), here {int(0.06 * S)})")
+    _simclr_check_records(rec.numpy(), n_tiles, H, W)
+    tiles = tiles_u8 if tiles_u8.is_contiguous() else tiles_u8.contiguous()
+    dev = tiles.device
+    shape, dtype = ((n_views, 3, S, S), torch.float32) if out == "float" else ((n_views, S, S, 3), torch.uint8)
+    res = torch.empty(shape, dtype=dtype, device=dev)
+    of, ou = (_ptr(res), _ptr(None)) if out == "float" else (_ptr(None), _ptr(res))
+    if dev.type != "cuda":
+        rc = L.dsmil_simclr_views_host(_ptr(tiles), n_tiles, H, W, _ptr(rec), n_views, S, of, ou, _ptr(None), 0)
+        _native.check(rc, "dsmil_simclr_views_host")
+        return res
+    with torch.cuda.device(dev):
+        d_rec = rec.to(dev, non_blocking=True)
+        ws = _workspace(dev, L.dsmil_simclr_views_workspace_bytes(n_views, H, W, S))
+        rc = L.dsmil_simclr_views(_ptr(tiles), n_tiles, H, W, _ptr(d_rec), n_views, S, of, ou, _ptr(ws), ws.numel(), _stream(dev))
+    _native.check(rc, "dsmil_simclr_views")
+    return res

@@ -86,3 +86,118 @@ class NTXentLoss(torch.nn.Module):
         if _native_ok(zis, zjs):
             return _NTXentNative.apply(zis, zjs, self.temperature, self.use_cosine_similarity)
         return ntxent_composite(zis, zjs, self.temperature, self.use_cosine_similarity)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the two-view augmentation (simclr/data_aug/dataset_wrapper.py:48-58, SimCLRDataTransform :80-87) on decoded tiles
+# ---------------------------------------------------------------------------------------------------------------------------
+class ViewParams:
+    """One record per output view (struct dsmil_simclr_view), held as ONE buffer: ``records`` int32 [n, 12], of which ``ints``
+    = columns 0..7 (tile, i, j, h, w, flags, order, hue byte) and ``floats`` = columns 8..11 seen as float32 (brightness,
+    contrast, saturation, sigma) are views.  Pinned when CUDA is available, so the upload is one asynchronous copy.
+
+    The constructor takes explicit values, each a scalar or a sequence of n: ``order`` is the jitter's order, [4] or [n, 4], a
+    permutation of 0 brightness, 1 contrast, 2 saturation, 3 hue; ``hue`` is the BYTE added to H, trunc(hue_factor * 255)
+    mod 256."""
+
+    def __init__(self, tile, i, j, h, w, flip=False, jitter=False, grey=False, blur=False, order=(0, 1, 2, 3), brightness=1.0,
+                 contrast=1.0, saturation=1.0, hue=0, sigma=1.0):
+        tile = torch.as_tensor(tile, dtype=torch.int64).reshape(-1)
+        n = tile.numel()
+        self.records = torch.empty((n, 12), dtype=torch.int32, pin_memory=torch.cuda.is_available())
+        self.ints = self.records[:, :8]
+        self.floats = self.records[:, 8:].view(torch.float32)
+
+        def col(x, dtype):
+            x = torch.as_tensor(x).to(dtype).reshape(-1)
+            return x.expand(n) if x.numel() == 1 else x.reshape(n)
+
+        flags = (col(flip, torch.bool).int() * ops.SIMCLR_FLIP + col(jitter, torch.bool).int() * ops.SIMCLR_JITTER +
+                 col(grey, torch.bool).int() * ops.SIMCLR_GREY + col(blur, torch.bool).int() * ops.SIMCLR_BLUR)
+        order = torch.as_tensor(order, dtype=torch.int64).reshape(-1, 4)
+        packed = (order << torch.tensor([0, 2, 4, 6])).sum(1).expand(n)
+        for k, x in enumerate((tile, i, j, h, w, flags, packed, hue)):
+            self.ints[:, k] = col(x, torch.int32)
+        for k, x in enumerate((brightness, contrast, saturation, sigma)):
+            self.floats[:, k] = col(x, torch.float32)
+
+    def __len__(self):
+        return self.records.shape[0]
+
+    def order(self):
+        """[n, 4]: the jitter operation at each position."""
+        return torch.stack([(self.ints[:, 6] >> (2 * k)) & 3 for k in range(4)], 1)
+
+
+def draw_view_params(n_tiles, H, W, size, s=1.0, generator=None):
+    """The random parameters of SimCLR's transform pipeline for 2 n_tiles views (records 2k and 2k + 1 are the two views of
+    tile k), drawn with torchvision's distributions: RandomResizedCrop.get_params (scale (0.08, 1), ratio (3/4, 4/3), ten
+    tries, then the centre crop clamped to the ratio range), flip p = 0.5, ColorJitter(0.8s, 0.8s, 0.8s, 0.2s) applied with
+    p = 0.8 in a uniformly random order, greyscale p = 0.2, blur p = 0.5 with sigma = U(0.1, 2.0).  ``generator``: a CPU
+    torch.Generator (default: the global one).  ``size`` does not enter the draw (nor does it in torchvision's get_params); it
+    is part of the signature because it belongs to the transform being drawn for.  The reference mixes torch's and numpy's global streams, so its stream is not
+    reproduced; the distributions are."""
+    import math
+    n = 2 * int(n_tiles)
+    H, W, s = int(H), int(W), float(s)
+
+    def U(*shape):
+        return torch.rand(*shape, generator=generator, dtype=torch.float64)
+
+    area = H * W * (0.08 + (1.0 - 0.08) * U(n, 10))
+    lo, hi = math.log(3.0 / 4.0), math.log(4.0 / 3.0)
+    ratio = torch.exp(lo + (hi - lo) * U(n, 10))
+    w_try = torch.round(torch.sqrt(area * ratio)).long()
+    h_try = torch.round(torch.sqrt(area / ratio)).long()
+    ok = (w_try > 0) & (w_try <= W) & (h_try > 0) & (h_try <= H)
+    first = torch.argmax(ok.int(), dim=1)                       # the first accepted try
+    any_ok = ok.any(dim=1)
+    rows = torch.arange(n)
+    w, h = w_try[rows, first], h_try[rows, first]
+    i = torch.floor(U(n) * (H - h + 1).clamp_min(1)).long().clamp(max=H - 1)
+    j = torch.floor(U(n) * (W - w + 1).clamp_min(1)).long().clamp(max=W - 1)
+    in_ratio = W / H                                            # the fallback: the whole tile, clamped to the ratio range
+    if in_ratio < 3.0 / 4.0:
+        fw, fh = W, int(round(W / (3.0 / 4.0)))
+    elif in_ratio > 4.0 / 3.0:
+        fh, fw = H, int(round(H * (4.0 / 3.0)))
+    else:
+        fw, fh = W, H
+    fw, fh = min(fw, W), min(fh, H)
+    w = torch.where(any_ok, w, torch.tensor(fw))
+    h = torch.where(any_ok, h, torch.tensor(fh))
+    i = torch.where(any_ok, torch.minimum(i, H - h), torch.tensor((H - fh) // 2))
+    j = torch.where(any_ok, torch.minimum(j, W - w), torch.tensor((W - fw) // 2))
+    flip = U(n) < 0.5
+    jitter = U(n) < 0.8
+    f_lo, f_hi = max(0.0, 1.0 - 0.8 * s), 1.0 + 0.8 * s
+    factors = f_lo + (f_hi - f_lo) * U(n, 3)
+    hue = (-0.2 * s + 0.4 * s * U(n))
+    hue_byte = torch.trunc(hue * 255).long() % 256
+    order = torch.argsort(U(n, 4), dim=1)
+    grey = U(n) < 0.2
+    blur = U(n) < 0.5
+    sigma = 0.1 + 1.9 * U(n)
+    return ViewParams(torch.arange(n) // 2, i, j, h, w, flip, jitter, grey, blur, order, factors[:, 0], factors[:, 1],
+                      factors[:, 2], hue_byte, sigma)
+
+
+class TwoViewAugment:
+    """SimCLRDataTransform over a batch of decoded tiles: ``aug(tiles_u8_nhwc) -> (xis, xjs)``, each [n, 3, S, S] fp32
+    (``out="float"``, what ToTensor gives) or [n, S, S, 3] uint8 (``out="uint8"``, what the repository's trunk ingests).  Draws
+    the parameters on the host (draw_view_params), launches ops.simclr_views once; xis / xjs are the even / odd views of that
+    one output, nothing is copied.  ``last_params`` holds the parameters of the last call."""
+
+    def __init__(self, size=224, s=1.0, generator=None, out="float"):
+        if int(0.06 * int(size)) % 2 != 1 or not 17 <= int(size) <= 256:
+            raise ValueError(f"size {size}: the blur kernel int(0.06 size) = {int(0.06 * int(size))} must be odd, 17 <= size <= 256")
+        if out not in ("float", "uint8"):
+            raise ValueError('out must be "float" or "uint8"')
+        self.size, self.s, self.generator, self.out = int(size), float(s), generator, out
+        self.last_params = None
+
+    def __call__(self, tiles_u8_nhwc):
+        n, H, W, _ = tiles_u8_nhwc.shape
+        self.last_params = draw_view_params(n, H, W, self.size, self.s, self.generator)
+        views = ops.simclr_views(tiles_u8_nhwc, self.last_params, self.size, out=self.out)
+        return views[0::2], views[1::2]

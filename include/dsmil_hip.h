@@ -895,6 +895,43 @@ int dsmil_ntxent_forward(const float* zis, const float* zjs, int64_t n, int d, f
 int dsmil_ntxent_backward(const float* zis, const float* zjs, int64_t n, int d, float temperature, int cosine, const float* lse,
                           const float* g_loss, float* g_zis, float* g_zjs, void* ws, size_t ws_bytes, void* stream);
 
+/* SimCLR's two-view augmentation (simclr/data_aug/dataset_wrapper.py:48-58, twice per patch) on decoded tiles: one record per
+ * OUTPUT view, the reference's chain on uint8 RGB stage by stage —
+ *   1. crop (i, j, h, w) of tile `tile`, resized to S x S as Pillow's Image.resize(BILINEAR) does it: the horizontal pass first,
+ *      rounded to uint8, then the vertical one; coefficients in double, normalised, 22-bit fixed point, accumulator from 1 << 21;
+ *      support max(1, w / S); a pass whose in and out sizes agree is skipped
+ *   2. horizontal flip                                                              (DSMIL_SIMCLR_FLIP)
+ *   3. colour jitter (DSMIL_SIMCLR_JITTER): the four operations in the order packed into `order` (operation k at bits 2k, 2k + 1:
+ *      0 brightness, 1 contrast, 2 saturation, 3 hue), each Pillow's ImageEnhance = Image.blend(degenerate, image, factor) in
+ *      fp32 with truncation (clipping for factors outside [0, 1]); hue = RGB -> HSV, H += hue (mod 256), HSV -> RGB with
+ *      Pillow's widths (Convert.c)
+ *   4. greyscale (DSMIL_SIMCLR_GREY): L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 in the three channels
+ *   5. Gaussian blur (DSMIL_SIMCLR_BLUR): separable, ksize = (int)(0.06 S) taps, weights exp(-(t - (ksize - 1) / 2)^2 / (2 sigma^2))
+ *      normalised, reflect-101 border, fp32 without rounding between the passes, rounded to nearest at the end.  The
+ *      real-arithmetic definition: cv2.GaussianBlur works in fixed point on 8-bit images and may differ by a level or two.
+ *   6. out_nchw (fp32 [n_views, 3, S, S], byte / 255.0f) and / or out_nhwc (uint8 [n_views, S, S, 3]); either may be NULL.
+ * 8 <= H, W <= 256;  17 <= S <= 256 with (int)(0.06 S) odd, else DSMIL_E_UNSUPPORTED (the size function returns 0).
+ * dsmil_simclr_views: every pointer a device pointer; asynchronous on `stream`, no host synchronisation, no allocation.  A record
+ * whose tile or crop lies outside the batch reads nothing and yields an all-zero view (the caller validates on the host).
+ * dsmil_simclr_views_host: HOST function, host pointers, the same per-pixel arithmetic compiled for the host; ws is unused (may
+ * be NULL); a bad record is DSMIL_E_INVALID.
+ * Added without a change of DSMIL_ABI_VERSION (it stays 6, no existing signature moved): a caller finds them by symbol. */
+enum { DSMIL_SIMCLR_FLIP = 1, DSMIL_SIMCLR_JITTER = 2, DSMIL_SIMCLR_GREY = 4, DSMIL_SIMCLR_BLUR = 8 };
+typedef struct dsmil_simclr_view {
+    int32_t tile;                 /* source tile of the batch */
+    int32_t i, j, h, w;           /* crop: top, left, height, width */
+    int32_t flags;                /* DSMIL_SIMCLR_* */
+    int32_t order;                /* the jitter's order, 2 bits per position */
+    int32_t hue;                  /* the byte added to H: trunc(hue_factor * 255) mod 256 */
+    float brightness, contrast, saturation;   /* blend factors */
+    float sigma;                  /* of the blur */
+} dsmil_simclr_view;
+size_t dsmil_simclr_views_workspace_bytes(int64_t n_views, int H, int W, int S);
+int dsmil_simclr_views(const uint8_t* tiles_nhwc, int64_t n_tiles, int H, int W, const dsmil_simclr_view* views, int64_t n_views,
+                       int S, float* out_nchw, uint8_t* out_nhwc, void* ws, size_t ws_bytes, void* stream);
+int dsmil_simclr_views_host(const uint8_t* tiles_nhwc, int64_t n_tiles, int H, int W, const dsmil_simclr_view* views,
+                            int64_t n_views, int S, float* out_nchw, uint8_t* out_nhwc, void* ws, size_t ws_bytes);
+
 /* Measurement hooks (bench.py's roofline leg; no reference counterpart).  While enabled, every
  * launch of a dominant kernel is bracketed by hipEventRecord on its own launch stream (up to 4096
  * launches per channel: 0 = k_query_attend of the aggregator, 1 = k_conv of the embedder);
