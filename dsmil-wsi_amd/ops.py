@@ -1321,6 +1321,96 @@ def trunk32_tail(kind, y2, stats, idn, down_stats=None):
 
 
 # ---------------------------------------------------------------------------------------------
+# conv backward for training the embedder (csrc/conv_bwd.hip behind dsmil_conv_bwd_*): the weight and the data gradient of one
+# conv in the fp32-class trunk's layout and arithmetic (fp32 NHWC maps, fp32 OIHW weights, two fp16 planes, three products).
+# A shape the kernels do not take raises NotImplementedError (DSMIL_E_UNSUPPORTED), every other refusal RuntimeError; nothing
+# is launched in either case.
+# ---------------------------------------------------------------------------------------------
+CONV_BWD_WHICH = {"weight": 0, "data": 1}
+_CONV_BWD_PLAN_FIELDS = ("which", "Ho", "Wo", "out_rows", "out_cols", "grid_x", "grid_y", "grid_z", "block", "chunk", "n_partials",
+                         "run_len", "cols_pad")
+
+
+def _cb_check(rc, what):
+    if rc == _native.DSMIL_E_UNSUPPORTED:
+        raise NotImplementedError(f"{what}: shape outside what the conv backward kernels implement")
+    _native.check(rc, what)
+
+
+def conv_backward_plan(Cin, Cout, ks, stride, pad, B, H, W, which="weight"):
+    """What the host decides for this gradient (no device needed): a dict of ``Ho, Wo`` (the map of dy), ``out_rows, out_cols``
+    (the output GEMM), ``grid_x, grid_y, grid_z, block``, and for the weight gradient ``chunk`` (positions per chunk),
+    ``n_partials`` (partials a dw element is summed from), ``run_len`` (the longest run of positions one accumulator sums)
+    and ``cols_pad``.  For the data gradient ``run_len`` = Cout ks^2 and ``n_partials`` = 1."""
+    out = (ctypes.c_int32 * 16)()
+    rc = _native.lib().dsmil_conv_bwd_plan(Cin, Cout, ks, stride, pad, B, H, W, CONV_BWD_WHICH[which], out)
+    _cb_check(rc, "dsmil_conv_bwd_plan")
+    d = dict(zip(_CONV_BWD_PLAN_FIELDS, list(out)))
+    d["which"] = which
+    return d
+
+
+def _cb_scratch(dev, need, ws):
+    if ws is None:
+        return _t16_scratch(dev, need)
+    if not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
+        raise RuntimeError(f"ws must be a contiguous uint8 CUDA(HIP) tensor of at least {need} bytes")
+    return ws
+
+
+def conv_backward_weight(x_nhwc, dy_nhwc, ks, stride, pad, in_stats=None, ws=None):
+    """dsmil_conv_bwd_weight: x fp32 NHWC [B,H,W,Cin], dy fp32 NHWC [B,Ho,Wo,Cout] -> dw fp32 OIHW [Cout,Cin,ks,ks].
+    ``in_stats`` = (mean, rstd) [B,Cin]: x is a raw conv output and the gradient is taken against relu((x - mean) rstd), the
+    operand trunk32_conv stages.  ``ws``: a caller's workspace (uint8, any contents); default a fresh one.  No host sync."""
+    x, dy = _f32c(x_nhwc, "x_nhwc"), _f32c(dy_nhwc, "dy_nhwc")
+    B, H, W, Cin = x.shape
+    Cout = dy.shape[3]
+    Ho, Wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
+    if tuple(dy.shape) != (B, Ho, Wo, Cout):
+        raise ValueError(f"dy is {tuple(dy.shape)}, this conv of x gives {(B, Ho, Wo, 'Cout')}")
+    im, ir = (_f32c(t, "in_stats") for t in in_stats) if in_stats is not None else (None, None)
+    L = _native.lib()
+    need = L.dsmil_conv_bwd_workspace_bytes(Cin, Cout, ks, stride, pad, B, H, W, 0)
+    if need == 0:
+        _cb_check(L.dsmil_conv_bwd_plan(Cin, Cout, ks, stride, pad, B, H, W, 0, (ctypes.c_int32 * 16)()), "dsmil_conv_bwd_weight")
+    ws = _cb_scratch(x.device, need, ws)
+    dw = torch.empty((Cout, Cin, ks, ks), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = L.dsmil_conv_bwd_weight(_ptr(x), _ptr(im), _ptr(ir), _ptr(dy), _ptr(dw), B, H, W, Cin, Cout, ks, stride, pad, _ptr(ws),
+                                     ws.numel(), _stream(x.device))
+    _cb_check(rc, "dsmil_conv_bwd_weight")
+    return dw
+
+
+def conv_backward_data(dy_nhwc, w, H, W, stride, pad, ws=None):
+    """dsmil_conv_bwd_data: dy fp32 NHWC [B,Ho,Wo,Cout], w fp32 OIHW [Cout,Cin,ks,ks] -> dx fp32 NHWC [B,H,W,Cin] for the H x W
+    input the conv read.  An input pixel no output reads gets an exact 0.  No host sync."""
+    dy, w = _f32c(dy_nhwc, "dy_nhwc"), _f32c(w, "w")
+    B, Ho, Wo, Cout = dy.shape
+    Cout_w, Cin, ks, _ = w.shape
+    if Cout_w != Cout:
+        raise ValueError(f"w gives {Cout_w} output channels, dy has {Cout}")
+    if (Ho, Wo) != ((H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1):
+        raise ValueError(f"dy is {Ho} x {Wo}, this conv of a {H} x {W} input gives another map")
+    L = _native.lib()
+    need = L.dsmil_conv_bwd_workspace_bytes(Cin, Cout, ks, stride, pad, B, H, W, 1)
+    if need == 0:
+        _cb_check(L.dsmil_conv_bwd_plan(Cin, Cout, ks, stride, pad, B, H, W, 1, (ctypes.c_int32 * 16)()), "dsmil_conv_bwd_data")
+    ws = _cb_scratch(dy.device, need, ws)
+    dx = torch.empty((B, H, W, Cin), dtype=torch.float32, device=dy.device)
+    with torch.cuda.device(dy.device):
+        rc = L.dsmil_conv_bwd_data(_ptr(dy), _ptr(w), _ptr(dx), B, H, W, Cin, Cout, ks, stride, pad, _ptr(ws), ws.numel(),
+                                   _stream(dy.device))
+    _cb_check(rc, "dsmil_conv_bwd_data")
+    return dx
+
+
+def conv_backward_supported(Cin, Cout, ks, stride, pad, B, H, W, which):
+    """True where dsmil_conv_bwd_weight (``which`` = "weight") / dsmil_conv_bwd_data ("data") take the shape.  No device."""
+    return _native.lib().dsmil_conv_bwd_workspace_bytes(Cin, Cout, ks, stride, pad, B, H, W, CONV_BWD_WHICH[which]) > 0
+
+
+# ---------------------------------------------------------------------------------------------
 # background filters of the tilers (deepzoom_tiler.py:56-61, test_crop_single.py:17-24)
 # ---------------------------------------------------------------------------------------------
 def tile_stats(tiles):

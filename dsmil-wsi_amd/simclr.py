@@ -201,3 +201,124 @@ class TwoViewAugment:
         self.last_params = draw_view_params(n, H, W, self.size, self.s, self.generator)
         views = ops.simclr_views(tiles_u8_nhwc, self.last_params, self.size, out=self.out)
         return views[0::2], views[1::2]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# training the embedder: the convs' backward on the native kernels (csrc/conv_bwd.hip).  OPT-IN: nothing here is called by
+# default, and the native inference route of IClassifier does not pass through these modules' forward.
+# ---------------------------------------------------------------------------------------------------------------------------
+def _same2(v):
+    """The int both entries of a conv's (a, a) geometry pair share, else None (strings such as padding="same" included)."""
+    if isinstance(v, int):
+        return v
+    if isinstance(v, (tuple, list)) and len(v) == 2 and all(isinstance(t, int) for t in v) and v[0] == v[1]:
+        return v[0]
+    return None
+
+
+def _conv_geometry(m):
+    """(ks, stride, pad) of a bias-free, ungrouped, undilated, zero-padded square conv, else None."""
+    ks, stride, pad, dil = _same2(m.kernel_size), _same2(m.stride), _same2(m.padding), _same2(m.dilation)
+    if m.bias is not None or m.groups != 1 or dil != 1 or m.padding_mode != "zeros" or None in (ks, stride, pad):
+        return None
+    return ks, stride, pad
+
+
+class _ConvNative(torch.autograd.Function):
+    """y = conv(x, w) on NHWC fp32 maps.  Forward: ops.trunk32_conv (the fp32-class trunk's kernels) where it takes the shape;
+    the stem (Cin = 3), which that entry leaves to the fused stem kernel, runs aten's conv.  Backward: ops.conv_backward_data /
+    conv_backward_weight, each only if its gradient is asked for."""
+
+    @staticmethod
+    def forward(ctx, x_nhwc, w, ks, stride, pad, fwd_native):
+        if fwd_native:
+            y = ops.trunk32_conv(x_nhwc, w, stride, pad)[0]
+        else:
+            y = torch.nn.functional.conv2d(x_nhwc.permute(0, 3, 1, 2), w, None, stride, pad).permute(0, 2, 3, 1).contiguous()
+        ctx.save_for_backward(x_nhwc, w)
+        ctx.geom = (ks, stride, pad)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        ks, stride, pad = ctx.geom
+        g = g.contiguous()
+        dx = ops.conv_backward_data(g, w, x.shape[1], x.shape[2], stride, pad) if ctx.needs_input_grad[0] else None
+        dw = ops.conv_backward_weight(x, g, ks, stride, pad) if ctx.needs_input_grad[1] else None
+        return dx, dw, None, None, None, None
+
+
+class NativeConv2d(torch.nn.Conv2d):
+    """nn.Conv2d (same parameters, same state-dict keys) whose backward runs the native weight- and data-gradient kernels.
+
+    On a 4-d fp32 CUDA input, with ``bias=None``, ``groups=1``, ``dilation=1``, zero padding and a geometry the entries take
+    for every gradient that will be asked for, the forward is ``_ConvNative``; the input is read as NHWC without a copy when it is
+    ``channels_last`` (``x.permute(0, 2, 3, 1)`` contiguous), else copied once, and the output is the NCHW view of the NHWC
+    result.  Everything else — the CPU, other dtypes, biased or grouped convs, a refused shape such as the stem when its input
+    requires grad — is ``nn.Conv2d.forward``."""
+
+    def _native_plan(self, x):
+        w = self.weight
+        if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and w.is_cuda and w.dtype == torch.float32 and
+                w.device == x.device and w.is_contiguous()):
+            return None
+        geom = _conv_geometry(self)
+        if geom is None:
+            return None
+        ks, stride, pad = geom
+        B, Cin, H, W = x.shape
+        Cout = w.shape[0]
+        if Cin != w.shape[1] or min(B, H, W) < 1:
+            return None
+        grad = torch.is_grad_enabled()
+        args = (Cin, Cout, ks, stride, pad, B, H, W)
+        if grad and x.requires_grad and not ops.conv_backward_supported(*args, "data"):
+            return None
+        if not ops.conv_backward_supported(*args, "weight"):         # also the geometry check of a call without gradients
+            return None
+        from . import _native
+        fwd_native = _native.lib().dsmil_trunk32_conv_workspace_bytes(*args, 0) > 0
+        if not fwd_native and Cin != 3:
+            return None
+        return ks, stride, pad, fwd_native
+
+    def forward(self, x):
+        plan = self._native_plan(x)
+        if plan is None:
+            return super().forward(x)
+        xp = x.permute(0, 2, 3, 1)
+        if not xp.is_contiguous():
+            xp = xp.contiguous()
+        return _ConvNative.apply(xp, self.weight, *plan).permute(0, 3, 1, 2)
+
+
+def native_conv_eligible(m):
+    """True for a plain nn.Conv2d whose geometry the conv backward entries take at some input size."""
+    if type(m) is not torch.nn.Conv2d:
+        return False
+    geom = _conv_geometry(m)
+    if geom is None:
+        return False
+    ks, stride, pad = geom
+    return (ks in (1, 3, 7) and stride in (1, 2) and pad <= ks // 2 and (m.in_channels % 16 == 0 or m.in_channels == 3) and
+            m.out_channels % 64 == 0)
+
+
+def use_native_convs(model):
+    """Swaps every eligible ``nn.Conv2d`` of ``model`` (in place) for a ``NativeConv2d`` holding the SAME Parameter object, and
+    returns how many it swapped.  state_dict() keys and values, optimizers holding the parameters and ``isinstance(m,
+    nn.Conv2d)`` checks (modules.resnet_convs_of, IClassifier's native inference route) are unaffected."""
+    swapped = 0
+    for parent in list(model.modules()):
+        for name, m in list(parent.named_children()):
+            if not native_conv_eligible(m):
+                continue
+            new = NativeConv2d(m.in_channels, m.out_channels, m.kernel_size, m.stride, m.padding, m.dilation, m.groups, False,
+                               m.padding_mode, device="meta")
+            new.weight = m.weight
+            new.train(m.training)
+            setattr(parent, name, new)
+            swapped += 1
+    return swapped

@@ -932,6 +932,56 @@ int dsmil_simclr_views(const uint8_t* tiles_nhwc, int64_t n_tiles, int H, int W,
 int dsmil_simclr_views_host(const uint8_t* tiles_nhwc, int64_t n_tiles, int H, int W, const dsmil_simclr_view* views,
                             int64_t n_views, int S, float* out_nchw, uint8_t* out_nhwc, void* ws, size_t ws_bytes);
 
+/* Convolution backward for training the embedder (csrc/conv_bwd.hip): the weight gradient and the data gradient of one conv
+ * of the ResNet trunks, in the layout and arithmetic class of dsmil_trunk32_conv — fp32 NHWC maps, fp32 OIHW weights, two
+ * round-to-nearest fp16 planes per operand, the products h0 w0 + h0 w1 + h1 w0 added smallest first, fp32 accumulation on
+ * v_mfma_f32_32x32x16_f16.  With Ho = (H + 2 pad - ks) / stride + 1 (Wo alike):
+ *   weight   dw[co][ci][ky][kx] = sum_{n,oy,ox} dy[n,oy,ox,co] v[n, oy stride - pad + ky, ox stride - pad + kx, ci]
+ *            v = x, or relu((x - in_mean[n,ci]) in_rstd[n,ci]) when in_mean / in_rstd [B,Cin] are given (both or neither): the
+ *            operand the forward's NORM form stages.  Taps outside the map contribute exact zeros.
+ *   data     dx[n,iy,ix,ci] = sum_{ky,kx,co} dy[n, (iy + pad - ky) / stride, (ix + pad - kx) / stride, co] w[co][ci][ky][kx]
+ *            over the taps whose division is exact and lands in the map (a gather: a pixel no output reads gets +0).
+ *   x, dx    device [B,H,W,Cin] fp32;   dy device [B,Ho,Wo,Cout] fp32;   w_oihw, dw_oihw device [Cout,Cin,ks,ks] fp32
+ *   ws       device, 256-byte aligned, dsmil_conv_bwd_workspace_bytes(..., which) bytes; which = DSMIL_CONV_BWD_WEIGHT / _DATA
+ * Scaling.  The weights carry the forward's 2^8.  dy has no natural range: every call takes max |dy| on the device (no host read)
+ * and multiplies dy by 2^s at staging, s = 14 - e for max |dy| = f 2^e, f in [0.5, 1) (s clamped to +-60, 0 for an all-zero
+ * dy): the largest element lands in [2^13, 2^14).  2^-s (and 2^-8) are taken out behind the accumulation; all of it is exact.
+ * Order.  The weight gradient deals the B Ho Wo positions to workgroups in chunks of plan[CHUNK]; each (chunk, tile) writes one
+ * fp32 partial and a finish kernel adds the n_partials partials of an element in chunk order.  No atomics anywhere: two calls on
+ * the same inputs are bit-identical.  A call never reads what another call left in ws.
+ * Limits, else DSMIL_E_UNSUPPORTED before any launch (the size function returns 0): Cin % 16 == 0 (or Cin == 3 for the weight
+ * gradient: the stem, its 147 columns padded with exact zeros), Cout % 64 == 0, ks in {1, 3, 7}, stride in {1, 2}, pad <= ks / 2,
+ * at least one output pixel, every element count below 2^31.  Null pointers are DSMIL_E_INVALID, x / dy / dx / statistics off 16
+ * bytes or ws off 256 DSMIL_E_ALIGN, a short workspace DSMIL_E_WORKSPACE.  Asynchronous on `stream`; nothing is allocated.
+ * dsmil_conv_bwd_plan is a HOST function: out[DSMIL_CONV_BWD_PLAN_*], the rest 0.
+ * Added without a change of DSMIL_ABI_VERSION (it stays 6, no existing signature moved): a caller finds them by symbol. */
+enum { DSMIL_CONV_BWD_WEIGHT = 0, DSMIL_CONV_BWD_DATA = 1 };
+enum {
+    DSMIL_CONV_BWD_PLAN_WHICH = 0,
+    DSMIL_CONV_BWD_PLAN_HO = 1,         /* the map of dy */
+    DSMIL_CONV_BWD_PLAN_WO = 2,
+    DSMIL_CONV_BWD_PLAN_OUT0 = 3,       /* rows of the output GEMM: Cout (weight), B H W (data) */
+    DSMIL_CONV_BWD_PLAN_OUT1 = 4,       /* its columns: Cin ks ks (weight), Cin (data) */
+    DSMIL_CONV_BWD_PLAN_GRID_X = 5,
+    DSMIL_CONV_BWD_PLAN_GRID_Y = 6,
+    DSMIL_CONV_BWD_PLAN_GRID_Z = 7,
+    DSMIL_CONV_BWD_PLAN_BLOCK = 8,
+    DSMIL_CONV_BWD_PLAN_CHUNK = 9,      /* weight: positions per chunk; data: 0 */
+    DSMIL_CONV_BWD_PLAN_PARTIALS = 10,  /* partials a dw element is summed from (data: 1) */
+    DSMIL_CONV_BWD_PLAN_RUN_LEN = 11,   /* the longest run of contraction indices one accumulator sums: positions (weight),
+                                           Cout ks ks (data) */
+    DSMIL_CONV_BWD_PLAN_COLS_PAD = 12   /* weight: the Cin ks ks columns padded to the tile; data: 0 */
+};
+int dsmil_conv_bwd_plan(int32_t Cin, int32_t Cout, int32_t ks, int32_t stride, int32_t pad, int32_t B, int32_t H, int32_t W,
+                        int32_t which, int32_t out[16]);
+size_t dsmil_conv_bwd_workspace_bytes(int32_t Cin, int32_t Cout, int32_t ks, int32_t stride, int32_t pad, int32_t B, int32_t H,
+                                      int32_t W, int32_t which);
+int dsmil_conv_bwd_weight(const float* x, const float* in_mean, const float* in_rstd, const float* dy, float* dw_oihw, int32_t B,
+                          int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t ks, int32_t stride, int32_t pad, void* ws,
+                          size_t ws_bytes, void* stream);
+int dsmil_conv_bwd_data(const float* dy, const float* w_oihw, float* dx, int32_t B, int32_t H, int32_t W, int32_t Cin,
+                        int32_t Cout, int32_t ks, int32_t stride, int32_t pad, void* ws, size_t ws_bytes, void* stream);
+
 /* Measurement hooks (bench.py's roofline leg; no reference counterpart).  While enabled, every
  * launch of a dominant kernel is bracketed by hipEventRecord on its own launch stream (up to 4096
  * launches per channel: 0 = k_query_attend of the aggregator, 1 = k_conv of the embedder);
