@@ -13,11 +13,14 @@
 //   g_Wf = g_c^T x, g_bf = colsum g_c
 // Every matrix product runs on bf16 MFMA over EXACT three-plane cuts of both fp32 operands, six plane products
 // (agg_split.h — the form the forward uses; round 3 had the backward on v_mfma_f32_32x32x2_f32, 1/16 of the rate).
-// Launch sequence (one stream, no host sync; 9 launches, round 3: 17):
-//   k_pack_agg_split x2  plane-cut W1 | W2 (skipped when the forward's packed image is handed in) and W2^T
-//   k_bwd_prep           gB, D, g_fcc_*                                  (block 0: head; the others: g_fcc_w)
-//   k_fc                 gA = V gB^T                                     (HBM stream, the forward's FCLayer kernel)
-//   k_bwd_qrow           q_c = q(x[idx_c])                               (skipped when the forward's q_max is handed in)
+// Launch sequence of one bag (agg_backward_impl; one stream, no host sync; 9 launches with the nonlinear query, round 3: 17):
+//   k_train_prologue     plane-cut W1 | W2 and W2^T into the workspace, the bag's {0, N} offsets — one launch; not launched
+//                        by dsmil_agg_train_step's backward, whose prologue ran before (or inside) the forward
+//   k_bwd_prep           gB, D, g_fcc_*                                  (block 0: head; the others: g_fcc_w; in the training
+//                        step also the loss head and, where C Kv floats fit its LDS, the gA rows as extra workgroups)
+//   k_fc                 gA = V gB^T                                     (HBM stream, the forward's FCLayer kernel; not launched
+//                        when k_bwd_prep carried it)
+//   k_bwd_qrow           q_c = q(x[idx_c])                               (not launched when the training step hands in the forward's q_max)
 //   k_bwd_rows           recompute H, Q per 32-row wave tile (the forward's MLP tile, H stored from the accumulators),
 //                        gs, gz2 -> workspace; per-tile partials of g_q = gs^T Q (register butterfly over the rows)
 //   k_bwd_critical       g_q = sum of the partials; gz2[idx_c] += g_q[c] (1 - Q[idx_c]^2)
@@ -37,6 +40,9 @@
 // dsmil_agg_backward_bags (agg_bwd_bags.h, included below) is this backward over a BATCH of bags stored back to back: the
 // row kernels above run over all rows of the batch, the per-bag steps get a batched form (k_bwd_rows / k_bwd_rows_hs with
 // BAGS = true walk a grid of tile slots, slot_owner).
+// Host code (behind the kernels): the two launch sequences are two functions; the workspace layout (bwd_layout), its carve
+// (BwdBufs), the call description (BwdCall), the common refusals and the row-only launch steps are written once and used by
+// both, and the step entries share param_sizes / carve_tensors / adam_fuse / adam_scalars.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -1196,17 +1202,24 @@ inline unsigned long long* tn_trace_buffer() {
     }();
     return buf;
 }
+#else
+inline unsigned long long* tn_trace_buffer() { return nullptr; }
 #endif
+// ---- host code: what the one-bag sequence and the batched one (agg_bwd_bags.h) share, then the one-bag sequence ----
+// Workspace of the backward.  n_bags == 0: ONE bag of N rows (dsmil_agg_backward*).  n_bags >= 1: a batch of n_bags bags
+// stored back to back, N rows in all (agg_bwd_bags.h): one gB / D / q_max / g_q set per bag, gqp over the tile slots of
+// the batch (its real tiles plus the idle ones) and the row -> bag table behind everything else.  A batch of ONE bag is
+// therefore not the one-bag layout.  R, S of k_tn_split and k_tn_small's row ranges come from N alone.
 struct BwdWs {
-    size_t gB, Dv, zero, qmax, gq, gA, gs, gz2, Hb, Qb, gH, gqp, wsplit, w2t, part0, part1, pb0, pb1, part, part_b, off, total;
-    int splits, rows;   // k_tn_small (dense instance-logit gradient)
+    size_t gB, Dv, zero, qmax, gq, gA, gs, gz2, Hb, Qb, gH, gqp, wsplit, w2t, part0, part1, pb0, pb1, part, part_b, off, rowbag, total;
+    int splits;         // k_tn_small (dense instance-logit gradient)
     int S, R, nx;       // k_tn_split
-    long long T32;
+    long long T32;      // the 32-row tiles of N rows (k_bwd_critical of the one bag)
 };
-BwdWs bwd_layout(long long N, int K, int Kv, int C, int nonlinear) {
+BwdWs bwd_layout(int n_bags, long long N, int K, int Kv, int C, int nonlinear) {
     BwdWs w;
-    w.rows = tn_rows(N);
-    w.splits = (int)((N + w.rows - 1) / w.rows);
+    const int rows = tn_rows(N);
+    w.splits = (int)((N + rows - 1) / rows);
     w.nx = (K + 63) / 64;
     const int nslab = w.nx + (nonlinear ? 2 : 0);
     long long st = TN_WGS / nslab;
@@ -1217,20 +1230,22 @@ BwdWs bwd_layout(long long N, int K, int Kv, int C, int nonlinear) {
     w.R = (int)R;
     w.S = (int)((N + R - 1) / R);
     w.T32 = (N + 31) / 32;
+    const size_t sets = n_bags ? (size_t)n_bags : 1;                           // gB, D, q_max, g_q: one set per bag
+    const long long qtiles = n_bags ? N / 32 + n_bags + 1 : w.T32;             // gqp: one [C,128] partial per 32-row tile (slot)
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t p = o; o = al(o + bytes); return p; };
-    w.gB = take((size_t)C * Kv * 4);
-    w.Dv = take((size_t)C * 4);
+    w.gB = take(sets * C * Kv * 4);
+    w.Dv = take(sets * C * 4);
     w.zero = take(QD * 4);
-    w.qmax = take((size_t)C * QD * 4);
-    w.gq = take((size_t)C * QD * 4);
+    w.qmax = take(sets * C * QD * 4);
+    w.gq = take(sets * C * QD * 4);
     w.gA = take((size_t)N * C * 4);
     w.gs = take((size_t)N * C * 4);
     w.gz2 = take((size_t)N * QD * 4);
     w.Hb = take((size_t)N * QD * 4);
     w.Qb = take((size_t)N * QD * 4);
     w.gH = take((size_t)N * QD * 4);
-    w.gqp = take((size_t)w.T32 * C * QD * 4);
+    w.gqp = take((size_t)qtiles * C * QD * 4);
     w.wsplit = take((size_t)(2 * ((K + 31) / 32) + 8) * S3_CHUNK_F4 * 16);
     w.w2t = take((size_t)8 * S3_CHUNK_F4 * 16);
     w.part0 = take((size_t)w.S * QD * K * 4);
@@ -1239,9 +1254,57 @@ BwdWs bwd_layout(long long N, int K, int Kv, int C, int nonlinear) {
     w.pb1 = take((size_t)w.S * QD * 4);
     w.part = take((size_t)w.splits * (C > 4 ? C : 4) * (K > QD ? K : QD) * 4);   // k_tn_small: [splits][C][K]
     w.part_b = take((size_t)w.splits * QD * 4);
-    w.off = take(2 * sizeof(int64_t));
+    w.off = take(2 * sizeof(int64_t));                                         // {0, N}: the rows as one run (k_bwd_gh)
+    w.rowbag = take(n_bags ? (size_t)N * 4 : 0);                               // (the one bag has none)
     w.total = o;
     return w;
+}
+
+// the regions of a workspace as typed pointers
+struct BwdBufs {
+    float *gB, *Dv, *zero, *qmax, *gq, *gA, *gs, *gz2, *Hb, *Qb, *gH, *gqp;
+    bf16_t *wsplit, *w2t;
+    float *part0, *part1, *pb0, *pb1, *part, *part_b;
+    int64_t* off;
+    int* rowbag;
+};
+BwdBufs bwd_carve(void* ws, const BwdWs& L) {
+    char* w8 = (char*)ws;
+    auto f = [&](size_t o) { return (float*)(w8 + o); };
+    return BwdBufs{f(L.gB), f(L.Dv), f(L.zero), f(L.qmax), f(L.gq), f(L.gA), f(L.gs), f(L.gz2), f(L.Hb), f(L.Qb), f(L.gH), f(L.gqp),
+                   (bf16_t*)(w8 + L.wsplit), (bf16_t*)(w8 + L.w2t),
+                   f(L.part0), f(L.part1), f(L.pb0), f(L.pb1), f(L.part), f(L.part_b), (int64_t*)(w8 + L.off), (int*)(w8 + L.rowbag)};
+}
+
+// One backward call: the arguments of the C entries (include/dsmil_hip.h has their meaning).  An entry sets what its
+// signature has and leaves the rest null.  N: the rows of the bag, or of the whole batch.  XT: the rows' storage type.
+template <typename XT>
+struct BwdCall {
+    const XT* feats; const XT* vals; int64_t N; const dsmil_agg_params* p;
+    const float* A; const float* Bm; const int64_t* idx;
+    const float* g_classes; const float* g_max; const float* g_pred; const float* g_A; const float* g_B;
+    const dsmil_agg_grads* g; float* g_vals; const int64_t* rowmap;
+    void* ws; size_t ws_bytes; void* stream;
+    float* g_feats;
+};
+
+// The refusals both sequences share: DSMIL_E_INVALID for a missing operand or a bad size, else DSMIL_E_ALIGN, else 0.
+// Each sequence adds its own DSMIL_E_INVALID checks (all of that class: their order among these cannot show) and ranks
+// the alignment refusal as its entry always has.
+template <typename XT>
+int bwd_common_refusal(const BwdCall<XT>& c) {
+    const dsmil_agg_params* p = c.p;
+    const dsmil_agg_grads* g = c.g;
+    if (!c.feats || !p || !c.A || !c.Bm || !c.idx || !g || !c.ws) return DSMIL_E_INVALID;
+    if (c.g_max && (!g->fc_w || !g->fc_b)) return DSMIL_E_INVALID;
+    if (c.N <= 0 || p->K <= 0 || p->Kv <= 0 || p->C <= 0) return DSMIL_E_INVALID;
+    if (!p->q0_w || !p->q0_b || !p->fcc_w || (p->nonlinear && (!p->q2_w || !p->q2_b))) return DSMIL_E_INVALID;
+    if (!g->q0_w || !g->q0_b || !g->fcc_w || !g->fcc_b || (p->nonlinear && (!g->q2_w || !g->q2_b))) return DSMIL_E_INVALID;
+    if (c.g_classes && (!g->fc_w || !g->fc_b)) return DSMIL_E_INVALID;
+    if (c.g_feats && (c.g_classes || c.g_max) && !p->fc_w) return DSMIL_E_INVALID;   // the instance stream's share of g_x reads Wf
+    if ((!c.vals || c.vals == c.feats) && p->Kv != p->K) return DSMIL_E_INVALID;      // v = Identity
+    if (((uintptr_t)c.ws % 256) || ((uintptr_t)p->q0_b % 16) || (p->nonlinear && ((uintptr_t)p->q2_b % 16))) return DSMIL_E_ALIGN;
+    return DSMIL_OK;
 }
 
 template <typename KernelT, typename ArgT>
@@ -1252,6 +1315,43 @@ int launch_tile_kernel(KernelT kern, const ArgT& arg, int nw, bool dma, long lon
     if (!dsmil_lds::allow((const void*)kern, (int)lds)) return DSMIL_E_LAUNCH;
     // (slots: the tile slots of a batch of bags, agg_bwd_bags.h; else the tiles of N rows)
     hipLaunchKernelGGL(kern, dim3((unsigned)(slots ? slots : (N + BM - 1) / BM)), dim3(nw * 64), lds, st, arg);
+    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
+}
+
+// hidden-split tile (agg_hs.h): HS_THREADS threads per HS_BM rows
+template <typename KernelT, typename ArgT>
+int launch_hs(KernelT kern, const ArgT& arg, long long blocks, hipStream_t st) {
+    if (!dsmil_lds::allow((const void*)kern, HS_LDS_BYTES)) return DSMIL_E_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(HS_THREADS), HS_LDS_BYTES, st, arg);
+    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
+}
+
+// step 6 (nonlinear query): gH = (gz2 W2) [H > 0] over N rows as one run (b.off = {0, N}); nw: the tile regime of step 4
+int launch_gh(const BwdBufs& b, long long N, int C, int nw, hipStream_t st) {
+    GhArgs gh{};
+    gh.at = AttendArgs{b.gz2, b.gz2, b.w2t, b.off, nullptr, b.zero, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                       QD, QD, C, 0, 0, 0, nullptr};
+    gh.Hbuf = b.Hb; gh.gH = b.gH;
+    return (nw == 4) ? launch_tile_kernel(k_bwd_gh<4>, gh, 4, true, N, st) : launch_hs(k_bwd_gh_hs, gh, (N + HS_BM - 1) / HS_BM, st);
+}
+
+// step 7: g_W1 and g_W2 partials, the contraction over N instance rows in one launch (`trace`: trace builds only)
+template <typename XT>
+int launch_tn_split(const XT* feats, const int64_t* rowmap, long long N, int K, int nonlinear, const BwdWs& L, const BwdBufs& b,
+                    bool v4, unsigned long long* trace, hipStream_t st) {
+    TnArgs tn{};
+    tn.X = feats; tn.rowmap = rowmap; tn.N = N; tn.K = K; tn.R = L.R; tn.nx = L.nx;
+    tn.nslab = L.nx + (nonlinear ? 2 : 0); tn.S = L.S;
+    tn.part0 = b.part0; tn.part1 = b.part1; tn.pb0 = b.pb0; tn.pb1 = b.pb1;
+    if (nonlinear) { tn.A0 = b.gH; tn.A1 = b.gz2; tn.Hb = b.Hb; }
+    else { tn.A0 = b.gz2; tn.A1 = nullptr; tn.Hb = nullptr; }
+    tn.trace = trace;
+    const dim3 gtn((unsigned)(tn.nslab * ((L.S + 7) / 8 * 8)));
+    if constexpr (sizeof(XT) == 2) hipLaunchKernelGGL((k_tn_split<true, false, XT>), gtn, dim3(256), 0, st, tn);   // bf16 rows: v4 holds, no map
+    else if (v4 && rowmap) hipLaunchKernelGGL((k_tn_split<true, true>), gtn, dim3(256), 0, st, tn);
+    else if (v4) hipLaunchKernelGGL((k_tn_split<true, false>), gtn, dim3(256), 0, st, tn);
+    else if (rowmap) hipLaunchKernelGGL((k_tn_split<false, true>), gtn, dim3(256), 0, st, tn);
+    else hipLaunchKernelGGL((k_tn_split<false, false>), gtn, dim3(256), 0, st, tn);
     return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 
@@ -1268,177 +1368,184 @@ int tn_small(const float* a, const XT* bm, long long N, int M, int Kc, float* pa
     return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 
-// packed_split: the forward's plane-cut W1 | W2 image (dsmil_agg_pack_split layout) or null; qmax_in: the forward's
-// q_max [C,128] or null — both are recomputed here when absent
-int agg_backward_impl(const float* feats, const float* vals, int64_t N, const dsmil_agg_params* p,
-                      const float* A, const float* Bm, const int64_t* idx, const float* g_classes,
-                      const float* g_max, const float* g_pred, const float* g_A, const float* g_B,
-                      const dsmil_agg_grads* g, float* g_vals, const int64_t* rowmap, void* ws, size_t ws_bytes,
-                      void* stream, const void* packed_split, const float* qmax_in, bool prepared = false,
-                      const LossHeadArgs* lhp = nullptr, const AdamFuse* adam = nullptr, bool own_fc_launch = false,
-                      float* g_feats = nullptr) {
-    if (adam && (!g_max || g_classes)) return DSMIL_E_INVALID;   // the fused optimizer step is the training loop's
-    if (!feats || !p || !A || !Bm || !idx || (!g_pred && !lhp) || !g || !ws) return DSMIL_E_INVALID;
-    if (g_max && (!g->fc_w || !g->fc_b)) return DSMIL_E_INVALID;
-    if (N <= 0 || p->K <= 0 || p->Kv <= 0 || p->C <= 0) return DSMIL_E_INVALID;
-    if (!p->q0_w || !p->q0_b || !p->fcc_w || (p->nonlinear && (!p->q2_w || !p->q2_b))) return DSMIL_E_INVALID;
-    if (!g->q0_w || !g->q0_b || !g->fcc_w || !g->fcc_b || (p->nonlinear && (!g->q2_w || !g->q2_b))) return DSMIL_E_INVALID;
-    if (g_classes && (!g->fc_w || !g->fc_b)) return DSMIL_E_INVALID;
-    if (g_feats && (g_classes || g_max) && !p->fc_w) return DSMIL_E_INVALID;   // the instance stream's share of g_x reads Wf
-    if (!vals) vals = feats;
-    if (vals == feats && p->Kv != p->K) return DSMIL_E_INVALID;
-    if (((uintptr_t)ws % 256) || ((uintptr_t)p->q0_b % 16) || (p->nonlinear && ((uintptr_t)p->q2_b % 16))) return DSMIL_E_ALIGN;
-    if (packed_split && ((uintptr_t)packed_split % 16)) return DSMIL_E_ALIGN;
+// k_bwd_reduce's arguments for the query stream (g_W1, g_b1, g_W2, g_b2 from the row-range partials); the one-bag
+// sequence adds its sparse FCLayer term and the fcc tensors of its fused Adam
+template <typename XT>
+ReduceArgs reduce_args(const BwdCall<XT>& c, const BwdWs& L, const BwdBufs& b) {
+    ReduceArgs ra{};
+    ra.part0 = b.part0; ra.part1 = b.part1; ra.pb0 = b.pb0; ra.pb1 = b.pb1;
+    ra.g_w0 = c.g->q0_w; ra.g_b0 = c.g->q0_b; ra.g_w1 = c.g->q2_w; ra.g_b1 = c.g->q2_b;
+    ra.S = L.S; ra.K = c.p->K; ra.nonlinear = c.p->nonlinear; ra.C = c.p->C;
+    return ra;
+}
+
+// k_bwd_gx's arguments (step 10, g_feats); the batch adds its row -> bag table and offsets
+template <typename XT>
+GxArgs gx_args(const BwdCall<XT>& c, const BwdBufs& b) {
+    const dsmil_agg_params* p = c.p;
+    const bool identity_v = !c.vals || c.vals == c.feats;
+    GxArgs gx{};
+    gx.L = p->nonlinear ? b.gH : b.gz2; gx.W = p->q0_w; gx.out = c.g_feats; gx.N = c.N; gx.J = QD; gx.K = p->K; gx.lvec = 1;
+    gx.gc = c.g_classes; gx.Wf = p->fc_w; gx.A = identity_v ? c.A : nullptr; gx.gB = b.gB; gx.idx = c.idx; gx.gmax = c.g_max;
+    gx.C = (c.g_classes || c.g_max || identity_v) ? p->C : 0;
+    return gx;
+}
+
+// What only dsmil_agg_train_step hands the one-bag backward
+struct BwdStepExtras {
+    const float* qmax_in;      // the forward's q_max [C,128]: k_bwd_qrow is not launched
+    bool prepared;             // the step's prologue (its own launch or carried by the forward) has filled wsplit, w2t, off of THIS workspace
+    const LossHeadArgs* lh;    // k_bwd_prep forms the objective and g_pred / g_max itself
+    const AdamFuse* adam;      // optimizer.step() in k_bwd_reduce, or null
+    bool own_fc_launch;        // experiment builds: gA as its own launch even where it could ride in k_bwd_prep
+};
+
+int agg_backward_impl(const BwdCall<float>& c, const BwdStepExtras* sx = nullptr) {
+    const LossHeadArgs* lhp = sx ? sx->lh : nullptr;
+    const AdamFuse* adam = sx ? sx->adam : nullptr;
+    if (adam && (!c.g_max || c.g_classes)) return DSMIL_E_INVALID;   // the fused optimizer step is the training loop's
+    if (!c.g_pred && !lhp) return DSMIL_E_INVALID;
+    int rc = bwd_common_refusal(c);
+    if (rc) return rc;
+    const dsmil_agg_params* p = c.p;
+    const dsmil_agg_grads* g = c.g;
+    const float* feats = c.feats;
+    const float* vals = c.vals ? c.vals : feats;
+    const int64_t N = c.N;
+    const int64_t* rowmap = c.rowmap;
     const int K = p->K, Kv = p->Kv, C = p->C;
-    const BwdWs L = bwd_layout(N, K, Kv, C, p->nonlinear);
-    if (ws_bytes < L.total) return DSMIL_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    char* w8 = (char*)ws;
-    float* gB = (float*)(w8 + L.gB); float* Dv = (float*)(w8 + L.Dv); float* zero = (float*)(w8 + L.zero);
-    float* qmax = (float*)(w8 + L.qmax); float* gq = (float*)(w8 + L.gq);
-    float* gA = (float*)(w8 + L.gA); float* gs = (float*)(w8 + L.gs); float* gz2 = (float*)(w8 + L.gz2);
-    float* Hb = (float*)(w8 + L.Hb); float* Qb = (float*)(w8 + L.Qb); float* gH = (float*)(w8 + L.gH);
-    float* gqp = (float*)(w8 + L.gqp);
-    bf16_t* wsplit = (bf16_t*)(w8 + L.wsplit); bf16_t* w2t = (bf16_t*)(w8 + L.w2t);
-    float* part0 = (float*)(w8 + L.part0); float* part1 = (float*)(w8 + L.part1);
-    float* pb0 = (float*)(w8 + L.pb0); float* pb1 = (float*)(w8 + L.pb1);
-    float* part = (float*)(w8 + L.part); float* part_b = (float*)(w8 + L.part_b);
-    int64_t* off = (int64_t*)(w8 + L.off);
+    const BwdWs L = bwd_layout(0, N, K, Kv, C, p->nonlinear);
+    if (c.ws_bytes < L.total) return DSMIL_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)c.stream;
+    const BwdBufs b = bwd_carve(c.ws, L);
     // the DMA tile needs 16-B aligned rows; K % 4 != 0 (MUSK: 166) takes the register-staged tile
     const bool v4 = (K % 4 == 0) && (((uintptr_t)feats) % 16 == 0);
     const bool w4 = (K % 4 == 0) && (((uintptr_t)feats | (uintptr_t)p->q0_w) % 16 == 0);
     const bool v4v = (Kv % 4 == 0) && ((uintptr_t)vals % 16 == 0);
-    int rc;
-    // 0. plane-cut weights: W1 | W2 unless the forward's image was handed in; W2^T for the gH pipeline
-    // (`prepared`: dsmil_agg_train_step's prologue already filled wsplit, w2t and off of THIS workspace)
-    const int nks = 2 * ((K + 31) / 32);
-    if (prepared) packed_split = wsplit;
-    else if (!packed_split || p->nonlinear) {   // (a nonlinear query needs W2^T from here anyway: the caller's image is then not used)
-        hipLaunchKernelGGL(k_train_prologue, dim3(240), dim3(256), 0, st, p->q0_w, p->nonlinear ? p->q2_w : nullptr, wsplit, w2t, K, nks,
-                           off, off, (long long)N);
-        packed_split = wsplit;
-    } else {
-        hipLaunchKernelGGL(k_set_offsets, dim3(1), dim3(1), 0, st, off, (long long)N);
+    // 0. plane-cut weights W1 | W2 and W2^T, the {0, N} offsets — unless dsmil_agg_train_step's prologue has filled them
+    if (!(sx && sx->prepared)) {
+        hipLaunchKernelGGL(k_train_prologue, dim3(240), dim3(256), 0, st, p->q0_w, p->nonlinear ? p->q2_w : nullptr, b.wsplit, b.w2t, K,
+                           2 * ((K + 31) / 32), b.off, b.off, (long long)N);
     }
     // 1. head: gB, D, g_fcc_*
     const long long nfcc = (long long)C * C * Kv;
     const int prep_blocks = (int)(1 + (nfcc + 1023) / 1024);
-    FcRole fr{vals, rowmap, gA, 0, prep_blocks};
-    if (lhp && !own_fc_launch && (Kv % 4 == 0) && ((uintptr_t)vals % 16 == 0) && (long long)C * Kv <= FC_ROLE_MAX) {   // the training step: one launch less
+    FcRole fr{vals, rowmap, b.gA, 0, prep_blocks};
+    if (lhp && !sx->own_fc_launch && (Kv % 4 == 0) && ((uintptr_t)vals % 16 == 0) && (long long)C * Kv <= FC_ROLE_MAX) {   // the training step: one launch less
         long long fb = ((long long)N + 3) / 4;
         fr.blocks = (int)(fb > 4096 ? 4096 : fb);
     }
-    hipLaunchKernelGGL(k_bwd_prep, dim3((unsigned)(prep_blocks + fr.blocks)), dim3(256), 0, st, p->fcc_w, Bm, g_pred, g_B, A, g_A,
-                       gB, Dv, g->fcc_w, g->fcc_b, zero, (long long)N, Kv, C, lhp ? *lhp : LossHeadArgs{}, fr);
+    hipLaunchKernelGGL(k_bwd_prep, dim3((unsigned)(prep_blocks + fr.blocks)), dim3(256), 0, st, p->fcc_w, c.Bm, c.g_pred, c.g_B, c.A, c.g_A,
+                       b.gB, b.Dv, g->fcc_w, g->fcc_b, b.zero, (long long)N, Kv, C, lhp ? *lhp : LossHeadArgs{}, fr);
     if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
     // 2. gA = V gB^T  (the forward's FCLayer kernel with W := gB, b := 0)
     if (!fr.blocks) {
-        rc = dsmil_fc_forward_rows(vals, N, Kv, C, gB, zero, gA, rowmap, stream);
+        rc = dsmil_fc_forward_rows(vals, N, Kv, C, b.gB, b.zero, b.gA, rowmap, c.stream);
         if (rc) return rc;
     }
-    // 3. critical queries
-    if (qmax_in) qmax = const_cast<float*>(qmax_in);
-    else {
-        if (w4) hipLaunchKernelGGL(k_bwd_qrow<4>, dim3((unsigned)C), dim3(256), 0, st, feats, idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, K, p->nonlinear, rowmap);
-        else hipLaunchKernelGGL(k_bwd_qrow<1>, dim3((unsigned)C), dim3(256), 0, st, feats, idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, K, p->nonlinear, rowmap);
+    // 3. critical queries (the training step hands in the forward's)
+    const float* qmax = sx ? sx->qmax_in : nullptr;
+    if (!qmax) {
+        if (w4) hipLaunchKernelGGL(k_bwd_qrow<4>, dim3((unsigned)C), dim3(256), 0, st, feats, c.idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, b.qmax, K, p->nonlinear, rowmap);
+        else hipLaunchKernelGGL(k_bwd_qrow<1>, dim3((unsigned)C), dim3(256), 0, st, feats, c.idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, b.qmax, K, p->nonlinear, rowmap);
         if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+        qmax = b.qmax;
     }
-    // 4. per-row part on MFMA
+    // 4. per-row part on MFMA.  Four-wave regime: the LDS-DMA tile, or <4,1> on rows that are not 16-B aligned
     const int nw = (N / 128 >= 512) ? 4 : 1;
     BwdRowsArgs br{};
-    br.at = AttendArgs{feats, feats, (const bf16_t*)packed_split, off, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, nullptr, nullptr, nullptr,
+    br.at = AttendArgs{feats, feats, b.wsplit, b.off, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, nullptr, nullptr, nullptr,
                        K, K, C, p->nonlinear, 0, 0, rowmap};
-    br.A = A; br.gA = gA; br.g_A = g_A; br.Dv = Dv; br.gs = gs; br.gz2 = gz2; br.Hbuf = Hb; br.Qbuf = Qb; br.gqp = gqp;
-    auto launch_hs = [&](auto kern, const auto& arg) {   // hidden-split tile: 256 threads per 64 rows
-        if (!dsmil_lds::allow((const void*)kern, HS_LDS_BYTES)) return (int)DSMIL_E_LAUNCH;
-        hipLaunchKernelGGL(kern, dim3((unsigned)((N + HS_BM - 1) / HS_BM)), dim3(HS_THREADS), HS_LDS_BYTES, st, arg);
-        return hipGetLastError() == hipSuccess ? (int)DSMIL_OK : (int)DSMIL_E_LAUNCH;
-    };
+    br.A = c.A; br.gA = b.gA; br.g_A = c.g_A; br.Dv = b.Dv; br.gs = b.gs; br.gz2 = b.gz2; br.Hbuf = b.Hb; br.Qbuf = b.Qb; br.gqp = b.gqp;
     if (nw == 4) rc = v4 ? launch_tile_kernel(k_bwd_rows<4, 4>, br, 4, true, N, st) : launch_tile_kernel(k_bwd_rows<4, 1>, br, 4, false, N, st);
-    else if (v4) rc = launch_hs(k_bwd_rows_hs<false>, br);
+    else if (v4) rc = launch_hs(k_bwd_rows_hs<false>, br, (N + HS_BM - 1) / HS_BM, st);
     else rc = launch_tile_kernel(k_bwd_rows<1, 1>, br, 1, false, N, st);
     if (rc) return rc;
     // 5. gradient of the critical queries joins their rows
-    hipLaunchKernelGGL(k_bwd_critical, dim3(1), dim3(1024), 0, st, idx, gqp, Qb, gz2, gq, L.T32, C, p->nonlinear);
+    hipLaunchKernelGGL(k_bwd_critical, dim3(1), dim3(1024), 0, st, c.idx, b.gqp, b.Qb, b.gz2, b.gq, L.T32, C, p->nonlinear);
     if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
-    TnArgs tn{};
-    tn.X = feats; tn.rowmap = rowmap; tn.N = N; tn.K = K; tn.R = L.R; tn.nx = L.nx;
-    tn.nslab = L.nx + (p->nonlinear ? 2 : 0); tn.S = L.S;
-    tn.part0 = part0; tn.part1 = part1; tn.pb0 = pb0; tn.pb1 = pb1;
-    if (p->nonlinear) {
-        // 6. gH = (gz2 W2) [H > 0]
-        GhArgs gh{};
-        gh.at = AttendArgs{gz2, gz2, w2t, off, nullptr, zero, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           QD, QD, C, 0, 0, 0, nullptr};
-        gh.Hbuf = Hb; gh.gH = gH;
-        rc = (nw == 4) ? launch_tile_kernel(k_bwd_gh<4>, gh, 4, true, N, st) : launch_hs(k_bwd_gh_hs, gh);
-        if (rc) return rc;
-        tn.A0 = gH; tn.A1 = gz2; tn.Hb = Hb;
-    } else {
-        tn.A0 = gz2; tn.A1 = nullptr; tn.Hb = nullptr;
-    }
+    // 6. gH = (gz2 W2) [H > 0]
+    if (p->nonlinear && (rc = launch_gh(b, N, C, nw, st))) return rc;
     // 7. weight gradients: contractions over instances, then the fixed-order reduction (+ the sparse FCLayer gradient)
-#ifdef DSMIL_TRACE
-    tn.trace = tn_trace_buffer();
-#endif
-    {
-        const dim3 gtn((unsigned)(tn.nslab * ((L.S + 7) / 8 * 8)));
-        if (v4 && rowmap) hipLaunchKernelGGL((k_tn_split<true, true>), gtn, dim3(256), 0, st, tn);
-        else if (v4) hipLaunchKernelGGL((k_tn_split<true, false>), gtn, dim3(256), 0, st, tn);
-        else if (rowmap) hipLaunchKernelGGL((k_tn_split<false, true>), gtn, dim3(256), 0, st, tn);
-        else hipLaunchKernelGGL((k_tn_split<false, false>), gtn, dim3(256), 0, st, tn);
-    }
-    if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    if ((rc = launch_tn_split(feats, rowmap, N, K, p->nonlinear, L, b, v4, tn_trace_buffer(), st))) return rc;
     // 8. dense instance stream (FCLayer): only when the caller has a dense upstream gradient on the instance logits
-    if (g_classes) {
-        rc = tn_small(g_classes, feats, N, C, K, part, part_b, g->fc_w, g->fc_b, L.splits, w4, st, rowmap);
-        if (rc) return rc;
-    }
-    ReduceArgs ra{};
-    ra.part0 = part0; ra.part1 = part1; ra.pb0 = pb0; ra.pb1 = pb1;
-    ra.g_w0 = g->q0_w; ra.g_b0 = g->q0_b; ra.g_w1 = g->q2_w; ra.g_b1 = g->q2_b;
-    ra.S = L.S; ra.K = K; ra.nonlinear = p->nonlinear;
-    ra.feats = feats; ra.idx = idx; ra.g_max = g_max; ra.rowmap = rowmap; ra.g_fc_w = g->fc_w; ra.g_fc_b = g->fc_b;
-    ra.C = C; ra.accumulate = g_classes ? 1 : 0;
+    if (c.g_classes && (rc = tn_small(c.g_classes, feats, N, C, K, b.part, b.part_b, g->fc_w, g->fc_b, L.splits, w4, st, rowmap))) return rc;
+    ReduceArgs ra = reduce_args(c, L, b);
+    ra.feats = feats; ra.idx = c.idx; ra.g_max = c.g_max; ra.rowmap = rowmap; ra.g_fc_w = g->fc_w; ra.g_fc_b = g->fc_b;
+    ra.accumulate = c.g_classes ? 1 : 0;
     if (adam) {
         ra.af = *adam;
         ra.af.g_fcc_w = g->fcc_w; ra.af.g_fcc_b = g->fcc_b; ra.af.n_fcc_w = (long long)C * C * Kv; ra.af.n_fcc_b = C;
     }
-    const long long nred = (long long)QD * K + (p->nonlinear ? QD * QD + 2 * QD : QD) + (g_max ? (long long)C * K + C : 0) +
+    const long long nred = (long long)QD * K + (p->nonlinear ? QD * QD + 2 * QD : QD) + (c.g_max ? (long long)C * K + C : 0) +
                            (adam ? (long long)C * C * Kv + C : 0);
     hipLaunchKernelGGL(k_bwd_reduce, dim3((unsigned)((nred + 255) / 256)), dim3(256), 0, st, ra);
     if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
     // 9. gradient of the value rows (only when v is a trainable layer of the caller)
-    if (g_vals) {
+    if (c.g_vals) {
         const long long n4 = (long long)N * ((Kv + 3) / 4);
-        if (v4v && (uintptr_t)g_vals % 16 == 0)
-            hipLaunchKernelGGL(k_bwd_gvals<4>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, A, gB, g_vals, (long long)N, Kv, C);
+        if (v4v && (uintptr_t)c.g_vals % 16 == 0)
+            hipLaunchKernelGGL(k_bwd_gvals<4>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, c.A, b.gB, c.g_vals, (long long)N, Kv, C);
         else
-            hipLaunchKernelGGL(k_bwd_gvals<1>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, A, gB, g_vals, (long long)N, Kv, C);
+            hipLaunchKernelGGL(k_bwd_gvals<1>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, c.A, b.gB, c.g_vals, (long long)N, Kv, C);
         if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
     }
     // 10. gradient of the input rows (only on request): gH / gz2, gB are still in the workspace
-    if (g_feats) {
-        GxArgs gx{};
-        gx.L = p->nonlinear ? gH : gz2; gx.W = p->q0_w; gx.out = g_feats; gx.N = N; gx.J = QD; gx.K = K; gx.lvec = 1;
-        gx.gc = g_classes; gx.Wf = p->fc_w; gx.A = vals == feats ? A : nullptr; gx.gB = gB; gx.idx = idx; gx.gmax = g_max;
-        gx.C = (g_classes || g_max || vals == feats) ? C : 0;
-        if (!gx_launch<false>(gx, st)) return DSMIL_E_UNSUPPORTED;
+    if (c.g_feats) {
+        if (!gx_launch<false>(gx_args(c, b), st)) return DSMIL_E_UNSUPPORTED;
         if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
     }
     return DSMIL_OK;
+}
+
+// ---- the step entries' common setup --------------------------------------------------------------------------------
+// the eight parameter tensors in parameter order (ops.W_KEYS): fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b (v = Identity)
+struct ParamSizes { long long n[8]; long long total; };
+ParamSizes param_sizes(int K, int C, int nonlinear) {
+    ParamSizes s{{(long long)C * K, C, (long long)QD * K, QD, nonlinear ? QD * QD : 0, nonlinear ? QD : 0, (long long)C * C * K, C}, 0};
+    for (int i = 0; i < 8; ++i) s.total += s.n[i];
+    return s;
+}
+// eight tensors of a step's workspace from `base` on, each 256-B aligned (the gradients; the rounded set of the bf16 step),
+// and the same pointers as a dsmil_agg_grads
+struct StepTensors { float* t[8]; dsmil_agg_grads g; size_t bytes; };
+StepTensors carve_tensors(char* base, const ParamSizes& sz, int nonlinear) {
+    StepTensors s{};
+    for (int i = 0; i < 8; ++i) { s.t[i] = (float*)(base + s.bytes); s.bytes = al(s.bytes + (size_t)sz.n[i] * 4); }
+    s.g.fc_w = s.t[0]; s.g.fc_b = s.t[1]; s.g.q0_w = s.t[2]; s.g.q0_b = s.t[3]; s.g.q2_w = nonlinear ? s.t[4] : nullptr;
+    s.g.q2_b = nonlinear ? s.t[5] : nullptr; s.g.fcc_w = s.t[6]; s.g.fcc_b = s.t[7];
+    return s;
+}
+// Adam's scalars, formed in double as torch forms them from Python floats, then handed to the kernels as fp32
+AdamScalars adam_scalars(int64_t step, double lr, double beta1, double beta2, double eps, double weight_decay) {
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    return AdamScalars{(float)(lr / bc1), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay,
+                       (float)sqrt(bc2)};
+}
+// optimizer.step() on the tensors of *p, applied where the gradient elements are formed (AdamFuse; af.p: the eight
+// tensors in parameter order); false: step <= 0 or a moment tensor is missing
+bool adam_fuse(const dsmil_agg_params* p, const ParamSizes& sz, const dsmil_adam_state* opt, AdamFuse& af) {
+    if (opt->step <= 0 || !opt->exp_avg || !opt->exp_avg_sq) return false;
+    const float* params[8] = {p->fc_w, p->fc_b, p->q0_w, p->q0_b, p->q2_w, p->q2_b, p->fcc_w, p->fcc_b};
+    af = AdamFuse{};
+    af.on = 1;
+    for (int i = 0; i < 8; ++i) {
+        if (sz.n[i] && (!opt->exp_avg[i] || !opt->exp_avg_sq[i])) return false;
+        af.p[i] = const_cast<float*>(params[i]); af.m[i] = opt->exp_avg[i]; af.v[i] = opt->exp_avg_sq[i];
+    }
+    af.h = adam_scalars(opt->step, opt->lr, opt->beta1, opt->beta2, opt->eps, opt->weight_decay);
+    return true;
 }
 
 // workspace of dsmil_agg_train_step: the forward's, the backward's, and the step's own tensors
 struct StepWs {
     size_t fwd, bwd, classes, A, B, pred, idx, mx, gpred, gmax, off, grads, total;
     size_t fwd_bytes, bwd_bytes;
-    long long gelems;
 };
 StepWs step_layout(long long N, int K, int C, int nonlinear) {
     StepWs s;
     s.fwd_bytes = dsmil_agg_workspace_bytes(1, N, K, K, C);
-    s.bwd_bytes = bwd_layout(N, K, K, C, nonlinear).total;
+    s.bwd_bytes = bwd_layout(0, N, K, K, C, nonlinear).total;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t p = o; o = al(o + bytes); return p; };
     s.fwd = take(s.fwd_bytes);
@@ -1452,12 +1559,9 @@ StepWs step_layout(long long N, int K, int C, int nonlinear) {
     s.gpred = take((size_t)C * 4);
     s.gmax = take((size_t)C * 4);
     s.off = take(2 * sizeof(int64_t));
-    // gradients in parameter order: fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b (each 256-B aligned)
-    s.grads = o;
-    const long long sizes[8] = {(long long)C * K, C, (long long)QD * K, QD, nonlinear ? QD * QD : 0, nonlinear ? QD : 0,
-                                (long long)C * C * K, C};
-    s.gelems = 0;
-    for (int i = 0; i < 8; ++i) { take((size_t)sizes[i] * 4); s.gelems += sizes[i]; }
+    s.grads = o;   // carve_tensors
+    const ParamSizes sz = param_sizes(K, C, nonlinear);
+    for (int i = 0; i < 8; ++i) take((size_t)sz.n[i] * 4);
     s.total = o;
     return s;
 }
@@ -1470,15 +1574,15 @@ extern "C" {
 
 size_t dsmil_agg_backward_workspace_bytes(int64_t N, int32_t K, int32_t Kv, int32_t C) {
     if (N <= 0 || K <= 0 || Kv <= 0 || C <= 0) return 0;
-    return bwd_layout(N, K, Kv, C, 1).total;   // the nonlinear layout is the larger one
+    return bwd_layout(0, N, K, Kv, C, 1).total;   // the nonlinear layout is the larger one
 }
 
 int dsmil_agg_backward(const float* feats, const float* vals, int64_t N, const dsmil_agg_params* p,
                        const float* A, const float* Bm, const int64_t* idx, const float* g_classes,
                        const float* g_pred, const float* g_A, const float* g_B, const dsmil_agg_grads* g,
                        float* g_vals, void* ws, size_t ws_bytes, void* stream) {
-    return agg_backward_impl(feats, vals, N, p, A, Bm, idx, g_classes, nullptr, g_pred, g_A, g_B, g, g_vals, nullptr,
-                             ws, ws_bytes, stream, nullptr, nullptr);
+    return dsmil_agg_backward_rows(feats, vals, N, p, A, Bm, idx, g_classes, /*g_max*/ nullptr, g_pred, g_A, g_B, g, g_vals,
+                                   /*rowmap*/ nullptr, ws, ws_bytes, stream, /*g_feats*/ nullptr);
 }
 
 int dsmil_agg_backward_ex(const float* feats, const float* vals, int64_t N, const dsmil_agg_params* p,
@@ -1486,8 +1590,8 @@ int dsmil_agg_backward_ex(const float* feats, const float* vals, int64_t N, cons
                           const float* g_max, const float* g_pred, const float* g_A, const float* g_B,
                           const dsmil_agg_grads* g, float* g_vals, const int64_t* rowmap, void* ws, size_t ws_bytes,
                           void* stream) {
-    return agg_backward_impl(feats, vals, N, p, A, Bm, idx, g_classes, g_max, g_pred, g_A, g_B, g, g_vals, rowmap,
-                             ws, ws_bytes, stream, nullptr, nullptr);
+    return dsmil_agg_backward_rows(feats, vals, N, p, A, Bm, idx, g_classes, g_max, g_pred, g_A, g_B, g, g_vals, rowmap, ws, ws_bytes,
+                                   stream, /*g_feats*/ nullptr);
 }
 
 size_t dsmil_agg_backward_rows_workspace_bytes(int64_t N, int32_t K, int32_t Kv, int32_t C) {
@@ -1499,13 +1603,16 @@ int dsmil_agg_backward_rows(const float* feats, const float* vals, int64_t N, co
                             const float* g_max, const float* g_pred, const float* g_A, const float* g_B,
                             const dsmil_agg_grads* g, float* g_vals, const int64_t* rowmap, void* ws, size_t ws_bytes,
                             void* stream, float* g_feats) {
-    return agg_backward_impl(feats, vals, N, p, A, Bm, idx, g_classes, g_max, g_pred, g_A, g_B, g, g_vals, rowmap,
-                             ws, ws_bytes, stream, nullptr, nullptr, false, nullptr, nullptr, false, g_feats);
+    BwdCall<float> c{};
+    c.feats = feats; c.vals = vals; c.N = N; c.p = p; c.A = A; c.Bm = Bm; c.idx = idx; c.g_classes = g_classes; c.g_max = g_max;
+    c.g_pred = g_pred; c.g_A = g_A; c.g_B = g_B; c.g = g; c.g_vals = g_vals; c.rowmap = rowmap; c.ws = ws; c.ws_bytes = ws_bytes;
+    c.stream = stream; c.g_feats = g_feats;
+    return agg_backward_impl(c);
 }
 
 size_t dsmil_agg_backward_bags_workspace_bytes(int32_t n_bags, int64_t total_rows, int32_t K, int32_t Kv, int32_t C) {
     if (n_bags <= 0 || total_rows <= 0 || K <= 0 || Kv <= 0 || C <= 0) return 0;
-    return bags_layout(n_bags, total_rows, K, Kv, C, 1).total;   // the nonlinear layout is the larger one
+    return bwd_layout(n_bags, total_rows, K, Kv, C, 1).total;   // the nonlinear layout is the larger one
 }
 
 int dsmil_agg_backward_bags(const float* feats, const float* vals, const int64_t* offsets, int32_t n_bags,
@@ -1513,8 +1620,11 @@ int dsmil_agg_backward_bags(const float* feats, const float* vals, const int64_t
                             const float* Bm, const int64_t* idx, const float* g_classes, const float* g_max,
                             const float* g_pred, const float* g_A, const float* g_B, const dsmil_agg_grads* g,
                             float* g_vals, const int64_t* rowmap, void* ws, size_t ws_bytes, void* stream, float* g_feats) {
-    return agg_backward_bags_impl(feats, vals, offsets, n_bags, total_rows, max_rows, p, A, Bm, idx, g_classes, g_max, g_pred,
-                                  g_A, g_B, g, g_vals, rowmap, ws, ws_bytes, stream, g_feats);
+    BwdCall<float> c{};
+    c.feats = feats; c.vals = vals; c.N = total_rows; c.p = p; c.A = A; c.Bm = Bm; c.idx = idx; c.g_classes = g_classes; c.g_max = g_max;
+    c.g_pred = g_pred; c.g_A = g_A; c.g_B = g_B; c.g = g; c.g_vals = g_vals; c.rowmap = rowmap; c.ws = ws; c.ws_bytes = ws_bytes;
+    c.stream = stream; c.g_feats = g_feats;
+    return agg_backward_bags_impl(c, offsets, n_bags, max_rows);
 }
 
 size_t dsmil_agg_backward_bags_bf16_workspace_bytes(int32_t n_bags, int64_t total_rows, int32_t K, int32_t Kv, int32_t C) {
@@ -1526,9 +1636,11 @@ int dsmil_agg_backward_bags_bf16(const void* feats_bf16, const void* vals_bf16, 
                                  const float* Bm, const int64_t* idx, const float* g_classes, const float* g_max,
                                  const float* g_pred, const float* g_A, const float* g_B, const dsmil_agg_grads* g,
                                  float* g_vals, void* ws, size_t ws_bytes, void* stream) {
-    return agg_backward_bags_impl((const bf16_t*)feats_bf16, (const bf16_t*)vals_bf16, offsets, n_bags, total_rows, max_rows,
-                                  p, A, Bm, idx, g_classes, g_max, g_pred, g_A, g_B, g, g_vals, nullptr, ws, ws_bytes, stream,
-                                  nullptr);
+    BwdCall<bf16_t> c{};
+    c.feats = (const bf16_t*)feats_bf16; c.vals = (const bf16_t*)vals_bf16; c.N = total_rows; c.p = p; c.A = A; c.Bm = Bm; c.idx = idx;
+    c.g_classes = g_classes; c.g_max = g_max; c.g_pred = g_pred; c.g_A = g_A; c.g_B = g_B; c.g = g; c.g_vals = g_vals; c.ws = ws;
+    c.ws_bytes = ws_bytes; c.stream = stream;
+    return agg_backward_bags_impl(c, offsets, n_bags, max_rows);
 }
 
 int dsmil_agg_loss_head_bags(const float* classes, const int64_t* offsets, const float* pred, const int64_t* idx,
@@ -1570,10 +1682,9 @@ int dsmil_adam_step(int32_t n_tensors, float* const* params, const float* const*
     if (n == 0) return DSMIL_OK;
     t.n = n;
     for (int i = n; i < DSMIL_ADAM_MAX_TENSORS; ++i) t.end[i] = tot;
-    // scalars formed in double, as torch forms them from Python floats, then handed to the kernel as fp32
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    hipLaunchKernelGGL(k_adam, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t, (float)(lr / bc1),
-                       (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)sqrt(bc2));
+    const AdamScalars h = adam_scalars(step, lr, beta1, beta2, eps, weight_decay);
+    hipLaunchKernelGGL(k_adam, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t, h.step_size, h.w1, h.beta2,
+                       h.w2, h.eps, h.wd, h.bc2_sqrt);
     return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 
@@ -1599,21 +1710,15 @@ int dsmil_agg_train_step(const float* feats, int64_t N, const int64_t* row_map, 
     float* classes = (float*)(w8 + L.classes); float* A = (float*)(w8 + L.A); float* Bm = (float*)(w8 + L.B);
     float* pred = (float*)(w8 + L.pred); int64_t* idx = (int64_t*)(w8 + L.idx); float* mx = (float*)(w8 + L.mx);
     float* gpred = (float*)(w8 + L.gpred); float* gmax = (float*)(w8 + L.gmax); int64_t* off = (int64_t*)(w8 + L.off);
-    // gradient tensors in parameter order
-    const long long sizes[8] = {(long long)C * K, C, (long long)QD * K, QD, p->nonlinear ? QD * QD : 0, p->nonlinear ? QD : 0,
-                                (long long)C * C * K, C};
-    float* gr[8];
-    {
-        size_t o = L.grads;
-        for (int i = 0; i < 8; ++i) { gr[i] = (float*)(w8 + o); o = al(o + (size_t)sizes[i] * 4); }
-    }
+    const ParamSizes sz = param_sizes(K, C, p->nonlinear);
+    const StepTensors gr = carve_tensors(w8 + L.grads, sz, p->nonlinear);   // the gradients
 #ifdef DSMIL_EXPERIMENTS   // DSMIL_TRAIN_UNFUSE: 1 = Adam as its own launch, 2 = gA as its own launch, 4 = k_pred and the prologue as their own launches
     static const int unfuse = getenv("DSMIL_TRAIN_UNFUSE") ? atoi(getenv("DSMIL_TRAIN_UNFUSE")) : 0;
 #else
     constexpr int unfuse = 0;
 #endif
     // prologue: plane-cut W1 | W2 and W2^T + the bag's offsets for the forward and the backward, one launch
-    const BwdWs LB = bwd_layout(N, K, K, C, p->nonlinear);
+    const BwdWs LB = bwd_layout(0, N, K, K, C, p->nonlinear);
     char* bw8 = w8 + L.bwd;
     const bool planes = dsmil_agg_mlp_form() == NP_BWD;   // (experiment builds may run the forward in another MFMA form)
     // (as 240 extra workgroups of the forward's first launch when that is k_logits_stream, else as its own launch)
@@ -1636,40 +1741,26 @@ int dsmil_agg_train_step(const float* feats, int64_t N, const int64_t* row_map, 
     if (rc) return rc;
     // backward (train_tcga.py:72); its first kernel also forms loss = 0.5 BCE(bag) + 0.5 BCE(max instance) and both
     // upstream gradients (train_tcga.py:68-71)
-    dsmil_agg_grads g{};
-    g.fc_w = gr[0]; g.fc_b = gr[1]; g.q0_w = gr[2]; g.q0_b = gr[3]; g.q2_w = p->nonlinear ? gr[4] : nullptr;
-    g.q2_b = p->nonlinear ? gr[5] : nullptr; g.fcc_w = gr[6]; g.fcc_b = gr[7];
     const float* qmax = nullptr;
     const float* pred_part = nullptr;
     int pred_blocks = 0;
     dsmil_agg_forward_leftovers(w8 + L.fwd, 1, N, K, K, C, &qmax, &pred_part, &pred_blocks);
     const LossHeadArgs lh{label, classes, (unfuse & 4) ? pred : nullptr, idx, loss, mx, gpred, gmax, pred_part, p->fcc_b, pred, pred_blocks};
     // optimizer.step() (train_tcga.py:73): Adam over the eight tensors, applied by the backward's last launch (k_bwd_reduce)
-    // to the gradient elements it has just formed; scalars formed in double as in dsmil_adam_step
-    float* params[8] = {const_cast<float*>(p->fc_w), const_cast<float*>(p->fc_b), const_cast<float*>(p->q0_w),
-                        const_cast<float*>(p->q0_b), const_cast<float*>(p->q2_w), const_cast<float*>(p->q2_b),
-                        const_cast<float*>(p->fcc_w), const_cast<float*>(p->fcc_b)};
-    if (opt->step <= 0) return DSMIL_E_INVALID;
-    AdamFuse af{};
-    af.on = 1;
-    for (int i = 0; i < 8; ++i) {
-        if (sizes[i] && (!opt->exp_avg[i] || !opt->exp_avg_sq[i])) return DSMIL_E_INVALID;
-        af.p[i] = params[i]; af.m[i] = opt->exp_avg[i]; af.v[i] = opt->exp_avg_sq[i];
-    }
-    const double bc1 = 1.0 - pow(opt->beta1, (double)opt->step), bc2 = 1.0 - pow(opt->beta2, (double)opt->step);
-    af.h = AdamScalars{(float)(opt->lr / bc1), (float)(1.0 - opt->beta1), (float)opt->beta2, (float)(1.0 - opt->beta2),
-                       (float)opt->eps, (float)opt->weight_decay, (float)sqrt(bc2)};
-    if (unfuse & 1) {
-        rc = agg_backward_impl(feats, nullptr, N, p, A, Bm, idx, nullptr, gmax, gpred, nullptr, nullptr, &g, nullptr, row_map,
-                               bw8, L.bwd_bytes, stream, nullptr, qmax, true, &lh, nullptr, (unfuse & 2) != 0);
-        if (rc) return rc;
-        int64_t numel[8];
-        for (int i = 0; i < 8; ++i) numel[i] = sizes[i];
-        return dsmil_adam_step(8, params, (const float* const*)gr, opt->exp_avg, opt->exp_avg_sq, numel, opt->step, opt->lr,
-                               opt->beta1, opt->beta2, opt->eps, opt->weight_decay, stream);
-    }
-    return agg_backward_impl(feats, nullptr, N, p, A, Bm, idx, nullptr, gmax, gpred, nullptr, nullptr, &g, nullptr, row_map,
-                             bw8, L.bwd_bytes, stream, nullptr, qmax, true, &lh, &af, (unfuse & 2) != 0);
+    // to the gradient elements it has just formed
+    AdamFuse af;
+    if (!adam_fuse(p, sz, opt, af)) return DSMIL_E_INVALID;
+    BwdCall<float> c{};
+    c.feats = feats; c.N = N; c.p = p; c.A = A; c.Bm = Bm; c.idx = idx; c.g_max = gmax; c.g_pred = gpred; c.g = &gr.g;
+    c.rowmap = row_map; c.ws = bw8; c.ws_bytes = L.bwd_bytes; c.stream = stream;
+    BwdStepExtras sx{};
+    sx.qmax_in = qmax; sx.prepared = true; sx.lh = &lh; sx.adam = (unfuse & 1) ? nullptr : &af; sx.own_fc_launch = (unfuse & 2) != 0;
+    rc = agg_backward_impl(c, &sx);
+    if (rc || !(unfuse & 1)) return rc;
+    int64_t numel[8];
+    for (int i = 0; i < 8; ++i) numel[i] = sz.n[i];
+    return dsmil_adam_step(8, af.p, (const float* const*)gr.t, opt->exp_avg, opt->exp_avg_sq, numel, opt->step, opt->lr,
+                           opt->beta1, opt->beta2, opt->eps, opt->weight_decay, stream);
 }
 
 // ---- one optimiser step on a BATCH of bags per call (agg_bwd_bags.h: agg_train_step_bags_impl) ----

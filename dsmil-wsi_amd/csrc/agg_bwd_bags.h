@@ -27,6 +27,12 @@
 // 128-row tile (k_bwd_rows<4,*>, k_bwd_gh<4>); fewer rows -> the hidden-split 64-row tile (k_bwd_rows_hs, k_bwd_gh_hs), or
 // the one-wave register-staged tile when the rows are not 16-B aligned (K % 4 != 0).  n_bags only adds idle slots.
 //
+// Host code: agg_backward_bags_impl is the batched launch sequence, written out in full here.  It takes the call as a
+// BwdCall (agg_bwd.hip) plus offsets / n_bags / max_rows, sizes its workspace with bwd_layout(n_bags, ..) — the one-bag
+// layout is the same function at n_bags == 0 — and calls the steps that only know rows (launch_gh, launch_tn_split,
+// tn_small, reduce_args, gx_args) where the one-bag sequence calls them.  Step 4 stays its own: over slots there is
+// no <4,1> form, so unaligned rows in the four-wave regime take the one-wave tile.
+//
 // dsmil_agg_train_step_bags / dsmil_agg_train_step_bags_bf16 (the end of this file) chain the batched forward, the mean
 // objective (k_loss_head_bags_mean) and this backward with Adam applied by its last two launches (k_bwd_reduce's AdamFuse,
 // the same hook in k_bags_head): one C call per minibatch step; on bf16 rows k_round_bf16 rebuilds the rounded weight set.
@@ -286,171 +292,81 @@ __global__ __launch_bounds__(256) void k_round_bf16(RoundTensors t) {
     t.dst[k][o] = bf2f(f2bf(t.src[k][o]));
 }
 
-// workspace: the one-bag layout over total_rows with one gB / D / q_max / g_q set per bag, the idle tile slots in gqp,
-// and the row -> bag table
-struct BagsWs {
-    size_t gB, Dv, zero, qmax, gq, gA, gs, gz2, Hb, Qb, gH, gqp, wsplit, w2t, part0, part1, pb0, pb1, part, part_b, off, rowbag, total;
-    int splits, S, R, nx;
-};
-BagsWs bags_layout(int n_bags, long long T, int K, int Kv, int C, int nonlinear) {
-    const BwdWs one = bwd_layout(T, K, Kv, C, nonlinear);   // R, S of k_tn_split and k_tn_small's row ranges: from total_rows
-    BagsWs w;
-    w.splits = one.splits; w.S = one.S; w.R = one.R; w.nx = one.nx;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t p = o; o = al(o + bytes); return p; };
-    w.gB = take((size_t)n_bags * C * Kv * 4);
-    w.Dv = take((size_t)n_bags * C * 4);
-    w.zero = take(QD * 4);
-    w.qmax = take((size_t)n_bags * C * QD * 4);
-    w.gq = take((size_t)n_bags * C * QD * 4);
-    w.gA = take((size_t)T * C * 4);
-    w.gs = take((size_t)T * C * 4);
-    w.gz2 = take((size_t)T * QD * 4);
-    w.Hb = take((size_t)T * QD * 4);
-    w.Qb = take((size_t)T * QD * 4);
-    w.gH = take((size_t)T * QD * 4);
-    w.gqp = take((size_t)(T / 32 + n_bags + 1) * C * QD * 4);
-    w.wsplit = take((size_t)(2 * ((K + 31) / 32) + 8) * S3_CHUNK_F4 * 16);
-    w.w2t = take((size_t)8 * S3_CHUNK_F4 * 16);
-    w.part0 = take((size_t)w.S * QD * K * 4);
-    w.part1 = take((size_t)w.S * QD * QD * 4);
-    w.pb0 = take((size_t)w.S * QD * 4);
-    w.pb1 = take((size_t)w.S * QD * 4);
-    w.part = take((size_t)w.splits * (C > 4 ? C : 4) * (K > QD ? K : QD) * 4);
-    w.part_b = take((size_t)w.splits * QD * 4);
-    w.off = take(2 * sizeof(int64_t));
-    w.rowbag = take((size_t)T * 4);
-    w.total = o;
-    return w;
-}
-
+// The batched launch sequence.  Workspace: bwd_layout(n_bags, total_rows, ..) (agg_bwd.hip).  c.N = total_rows; g_pred,
+// g_max, idx are [n_bags, C], B and g_B [n_bags, C, Kv].
 // XT = float: dsmil_agg_backward_bags.  XT = bf16_t: dsmil_agg_backward_bags_bf16 — the same launches on the same workspace
 // layout with the rows fetched as bf16 (exact MFMA operands: their plane cut is (x, 0, 0)); no row map, no g_feats, and the
 // register-staged / hidden-split tiles only (the LDS-DMA tile stages fp32 bytes as they are).
 template <typename XT>
-int agg_backward_bags_impl(const XT* feats, const XT* vals, const int64_t* offsets, int32_t n_bags, int64_t T,
-                           int64_t max_rows, const dsmil_agg_params* p, const float* A, const float* Bm, const int64_t* idx,
-                           const float* g_classes, const float* g_max, const float* g_pred, const float* g_A,
-                           const float* g_B, const dsmil_agg_grads* g, float* g_vals, const int64_t* rowmap, void* ws,
-                           size_t ws_bytes, void* stream, float* g_feats, const AdamFuse* adam = nullptr) {
-    // the checks of agg_backward_impl, in its order
-    if (adam && (!g_max || g_classes || g_vals || g_feats)) return DSMIL_E_INVALID;   // the fused optimizer step is the training loop's
-    if (!feats || !offsets || !p || !A || !Bm || !idx || !g_pred || !g || !ws) return DSMIL_E_INVALID;
-    if (g_max && (!g->fc_w || !g->fc_b)) return DSMIL_E_INVALID;
-    if (n_bags < 1 || T < n_bags || max_rows < 1 || max_rows > T || p->K <= 0 || p->Kv <= 0 || p->C <= 0) return DSMIL_E_INVALID;
-    if (!p->q0_w || !p->q0_b || !p->fcc_w || (p->nonlinear && (!p->q2_w || !p->q2_b))) return DSMIL_E_INVALID;
-    if (!g->q0_w || !g->q0_b || !g->fcc_w || !g->fcc_b || (p->nonlinear && (!g->q2_w || !g->q2_b))) return DSMIL_E_INVALID;
-    if (g_classes && (!g->fc_w || !g->fc_b)) return DSMIL_E_INVALID;
-    if (g_feats && (g_classes || g_max) && !p->fc_w) return DSMIL_E_INVALID;
-    if (!vals) vals = feats;
-    if (vals == feats && p->Kv != p->K) return DSMIL_E_INVALID;
+int agg_backward_bags_impl(const BwdCall<XT>& c, const int64_t* offsets, int32_t n_bags, int64_t max_rows,
+                           const AdamFuse* adam = nullptr) {
+    const int64_t T = c.N;
+    if (adam && (!c.g_max || c.g_classes || c.g_vals || c.g_feats)) return DSMIL_E_INVALID;   // the fused optimizer step is the training loop's
+    if (!offsets || !c.g_pred || n_bags < 1 || T < n_bags || max_rows < 1 || max_rows > T) return DSMIL_E_INVALID;
+    int rc = bwd_common_refusal(c);
+    if (rc == DSMIL_E_INVALID) return rc;
+    const dsmil_agg_params* p = c.p;
+    const dsmil_agg_grads* g = c.g;
+    const XT* feats = c.feats;
+    const XT* vals = c.vals ? c.vals : feats;
+    const int64_t* rowmap = c.rowmap;
     if (T > BAGS_MAX_ROWS) return DSMIL_E_UNSUPPORTED;
     constexpr bool B16 = sizeof(XT) == 2;
-    if (B16 && (rowmap || g_feats)) return DSMIL_E_INVALID;
+    if (B16 && (rowmap || c.g_feats)) return DSMIL_E_INVALID;
     if (B16 && (p->K % 8 || p->Kv % 4)) return DSMIL_E_UNSUPPORTED;          // the bf16 forward's condition
     if (B16 && (((uintptr_t)feats | (uintptr_t)vals) % 16)) return DSMIL_E_ALIGN;
-    if (((uintptr_t)ws % 256) || ((uintptr_t)p->q0_b % 16) || (p->nonlinear && ((uintptr_t)p->q2_b % 16))) return DSMIL_E_ALIGN;
+    if (rc) return rc;   // the common alignment refusal ranks behind the batch's own limits
     const int K = p->K, Kv = p->Kv, C = p->C;
-    const BagsWs L = bags_layout(n_bags, T, K, Kv, C, p->nonlinear);
-    if (ws_bytes < L.total) return DSMIL_E_WORKSPACE;
+    const BwdWs L = bwd_layout(n_bags, T, K, Kv, C, p->nonlinear);
+    if (c.ws_bytes < L.total) return DSMIL_E_WORKSPACE;
     const long long n4 = (long long)T * ((Kv + 3) / 4);
     if ((n4 + 255) / 256 > 0x7fffffffLL || (long long)C * n_bags > 0x7fffffffLL) return DSMIL_E_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    char* w8 = (char*)ws;
-    float* gB = (float*)(w8 + L.gB); float* Dv = (float*)(w8 + L.Dv); float* zero = (float*)(w8 + L.zero);
-    float* qmax = (float*)(w8 + L.qmax); float* gq = (float*)(w8 + L.gq);
-    float* gA = (float*)(w8 + L.gA); float* gs = (float*)(w8 + L.gs); float* gz2 = (float*)(w8 + L.gz2);
-    float* Hb = (float*)(w8 + L.Hb); float* Qb = (float*)(w8 + L.Qb); float* gH = (float*)(w8 + L.gH);
-    float* gqp = (float*)(w8 + L.gqp);
-    bf16_t* wsplit = (bf16_t*)(w8 + L.wsplit); bf16_t* w2t = (bf16_t*)(w8 + L.w2t);
-    float* part0 = (float*)(w8 + L.part0); float* part1 = (float*)(w8 + L.part1);
-    float* pb0 = (float*)(w8 + L.pb0); float* pb1 = (float*)(w8 + L.pb1);
-    float* part = (float*)(w8 + L.part); float* part_b = (float*)(w8 + L.part_b);
-    int64_t* off1 = (int64_t*)(w8 + L.off);      // {0, total_rows}: the batch as one run of rows (k_bwd_gh)
-    int* rowbag = (int*)(w8 + L.rowbag);
+    hipStream_t st = (hipStream_t)c.stream;
+    const BwdBufs b = bwd_carve(c.ws, L);
     const bool v4 = (K % 4 == 0) && (((uintptr_t)feats) % 16 == 0);
     const bool w4 = (K % 4 == 0) && (((uintptr_t)feats | (uintptr_t)p->q0_w) % 16 == 0);
     const bool v4v = (Kv % 4 == 0) && ((uintptr_t)vals % 16 == 0);
-    int rc;
     // 0. plane-cut weights W1 | W2 and W2^T, the {0, total_rows} offsets; the row -> bag table
-    const int nks = 2 * ((K + 31) / 32);
-    hipLaunchKernelGGL(k_train_prologue, dim3(240), dim3(256), 0, st, p->q0_w, p->nonlinear ? p->q2_w : nullptr, wsplit, w2t, K, nks,
-                       off1, off1, (long long)T);
-    hipLaunchKernelGGL(k_bags_rowbag, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, offsets, n_bags, (long long)T, rowbag);
+    hipLaunchKernelGGL(k_train_prologue, dim3(240), dim3(256), 0, st, p->q0_w, p->nonlinear ? p->q2_w : nullptr, b.wsplit, b.w2t, K,
+                       2 * ((K + 31) / 32), b.off, b.off, (long long)T);
+    hipLaunchKernelGGL(k_bags_rowbag, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, offsets, n_bags, (long long)T, b.rowbag);
     // 1. heads: gB, D per bag
-    hipLaunchKernelGGL(k_bags_prep, dim3((unsigned)n_bags), dim3(256), 0, st, p->fcc_w, Bm, g_pred, g_B, A, g_A, offsets, gB, Dv, zero, Kv, C);
+    hipLaunchKernelGGL(k_bags_prep, dim3((unsigned)n_bags), dim3(256), 0, st, p->fcc_w, c.Bm, c.g_pred, c.g_B, c.A, c.g_A, offsets, b.gB,
+                       b.Dv, b.zero, Kv, C);
     if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
     // 2. gA = V gB[bag]^T
     {
         long long blocks = ((long long)T + 3) / 4;
         if (blocks > 4096) blocks = 4096;
-        if (v4v) hipLaunchKernelGGL((k_bags_ga<4, XT>), dim3((unsigned)blocks), dim3(256), 0, st, vals, gB, rowbag, gA, (long long)T, Kv, C, rowmap);
-        else hipLaunchKernelGGL((k_bags_ga<1, XT>), dim3((unsigned)blocks), dim3(256), 0, st, vals, gB, rowbag, gA, (long long)T, Kv, C, rowmap);
+        if (v4v) hipLaunchKernelGGL((k_bags_ga<4, XT>), dim3((unsigned)blocks), dim3(256), 0, st, vals, b.gB, b.rowbag, b.gA, (long long)T, Kv, C, rowmap);
+        else hipLaunchKernelGGL((k_bags_ga<1, XT>), dim3((unsigned)blocks), dim3(256), 0, st, vals, b.gB, b.rowbag, b.gA, (long long)T, Kv, C, rowmap);
     }
     // 3. critical queries
-    if (w4) hipLaunchKernelGGL((k_bags_qrow<4, XT>), dim3((unsigned)(C * n_bags)), dim3(256), 0, st, feats, offsets, idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, K, C, p->nonlinear, rowmap);
-    else hipLaunchKernelGGL((k_bags_qrow<1, XT>), dim3((unsigned)(C * n_bags)), dim3(256), 0, st, feats, offsets, idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, K, C, p->nonlinear, rowmap);
+    if (w4) hipLaunchKernelGGL((k_bags_qrow<4, XT>), dim3((unsigned)(C * n_bags)), dim3(256), 0, st, feats, offsets, c.idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, b.qmax, K, C, p->nonlinear, rowmap);
+    else hipLaunchKernelGGL((k_bags_qrow<1, XT>), dim3((unsigned)(C * n_bags)), dim3(256), 0, st, feats, offsets, c.idx, p->q0_w, p->q0_b, p->q2_w, p->q2_b, b.qmax, K, C, p->nonlinear, rowmap);
     if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
-    // 4. per-row part on MFMA, a 1-D grid of tile slots
+    // 4. per-row part on MFMA, a 1-D grid of tile slots.  Four-wave regime: the LDS-DMA tile over 128-row slots, or the one-wave
+    // register-staged tile over 32-row slots on rows that are not 16-B aligned (no <4,1> form over slots)
     const int nw = (T / 128 >= 512) ? 4 : 1;
     BwdRowsArgs br{};
-    br.at = AttendArgs{feats, feats, wsplit, offsets, p->q0_w, p->q0_b, p->q2_w, p->q2_b, qmax, nullptr, nullptr, nullptr,
+    br.at = AttendArgs{feats, feats, b.wsplit, offsets, p->q0_w, p->q0_b, p->q2_w, p->q2_b, b.qmax, nullptr, nullptr, nullptr,
                        K, K, C, p->nonlinear, 0, 0, rowmap};
-    br.A = A; br.gA = gA; br.g_A = g_A; br.Dv = Dv; br.gs = gs; br.gz2 = gz2; br.Hbuf = Hb; br.Qbuf = Qb; br.gqp = gqp;
+    br.A = c.A; br.gA = b.gA; br.g_A = c.g_A; br.Dv = b.Dv; br.gs = b.gs; br.gz2 = b.gz2; br.Hbuf = b.Hb; br.Qbuf = b.Qb; br.gqp = b.gqp;
     br.n_bags = n_bags;
-    auto launch_hs = [&](auto kern, const auto& arg, long long blocks) {
-        if (!dsmil_lds::allow((const void*)kern, HS_LDS_BYTES)) return (int)DSMIL_E_LAUNCH;
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(HS_THREADS), HS_LDS_BYTES, st, arg);
-        return hipGetLastError() == hipSuccess ? (int)DSMIL_OK : (int)DSMIL_E_LAUNCH;
-    };
-    if (nw == 4) {
-        const long long slots = T / 128 + n_bags;
-        rc = v4 ? launch_tile_kernel(k_bwd_rows<4, 4, true, XT>, br, 4, !B16, T, st, slots)
-                : launch_tile_kernel(k_bwd_rows<1, 1, true, XT>, br, 1, false, T, st, T / 32 + n_bags);
-    } else if (v4) rc = launch_hs(k_bwd_rows_hs<true, XT>, br, T / HS_BM + n_bags);
+    if (nw == 4 && v4) rc = launch_tile_kernel(k_bwd_rows<4, 4, true, XT>, br, 4, !B16, T, st, T / 128 + n_bags);
+    else if (nw == 1 && v4) rc = launch_hs(k_bwd_rows_hs<true, XT>, br, T / HS_BM + n_bags, st);
     else rc = launch_tile_kernel(k_bwd_rows<1, 1, true, XT>, br, 1, false, T, st, T / 32 + n_bags);
     if (rc) return rc;
     // 5. gradient of the critical queries joins their rows, bag by bag
-    hipLaunchKernelGGL(k_bags_critical, dim3((unsigned)n_bags), dim3(1024), 0, st, offsets, idx, gqp, Qb, gz2, gq, C, p->nonlinear);
+    hipLaunchKernelGGL(k_bags_critical, dim3((unsigned)n_bags), dim3(1024), 0, st, offsets, c.idx, b.gqp, b.Qb, b.gz2, b.gq, C, p->nonlinear);
     if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
-    TnArgs tn{};
-    tn.X = feats; tn.rowmap = rowmap; tn.N = T; tn.K = K; tn.R = L.R; tn.nx = L.nx;
-    tn.nslab = L.nx + (p->nonlinear ? 2 : 0); tn.S = L.S;
-    tn.part0 = part0; tn.part1 = part1; tn.pb0 = pb0; tn.pb1 = pb1;
-    if (p->nonlinear) {
-        // 6. gH = (gz2 W2) [H > 0] over the rows of the batch
-        GhArgs gh{};
-        gh.at = AttendArgs{gz2, gz2, w2t, off1, nullptr, zero, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           QD, QD, C, 0, 0, 0, nullptr};
-        gh.Hbuf = Hb; gh.gH = gH;
-        rc = (nw == 4) ? launch_tile_kernel(k_bwd_gh<4>, gh, 4, true, T, st) : launch_hs(k_bwd_gh_hs, gh, (T + HS_BM - 1) / HS_BM);
-        if (rc) return rc;
-        tn.A0 = gH; tn.A1 = gz2; tn.Hb = Hb;
-    } else {
-        tn.A0 = gz2; tn.A1 = nullptr; tn.Hb = nullptr;
-    }
+    // 6. gH = (gz2 W2) [H > 0] over the rows of the batch
+    if (p->nonlinear && (rc = launch_gh(b, T, C, nw, st))) return rc;
     // 7. weight gradients: the contraction over ALL instance rows of the batch, then the fixed-order reduction
-#ifdef DSMIL_TRACE
-    tn.trace = nullptr;
-#endif
-    {
-        const dim3 gtn((unsigned)(tn.nslab * ((L.S + 7) / 8 * 8)));
-        if constexpr (B16) hipLaunchKernelGGL((k_tn_split<true, false, XT>), gtn, dim3(256), 0, st, tn);   // (v4 holds, no map)
-        else if (v4 && rowmap) hipLaunchKernelGGL((k_tn_split<true, true>), gtn, dim3(256), 0, st, tn);
-        else if (v4) hipLaunchKernelGGL((k_tn_split<true, false>), gtn, dim3(256), 0, st, tn);
-        else if (rowmap) hipLaunchKernelGGL((k_tn_split<false, true>), gtn, dim3(256), 0, st, tn);
-        else hipLaunchKernelGGL((k_tn_split<false, false>), gtn, dim3(256), 0, st, tn);
-    }
-    if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    if ((rc = launch_tn_split(feats, rowmap, T, K, p->nonlinear, L, b, v4, nullptr, st))) return rc;
     // 8. dense instance stream
-    if (g_classes) {
-        rc = tn_small(g_classes, feats, T, C, K, part, part_b, g->fc_w, g->fc_b, L.splits, w4, st, rowmap);
-        if (rc) return rc;
-    }
-    ReduceArgs ra{};
-    ra.part0 = part0; ra.part1 = part1; ra.pb0 = pb0; ra.pb1 = pb1;
-    ra.g_w0 = g->q0_w; ra.g_b0 = g->q0_b; ra.g_w1 = g->q2_w; ra.g_b1 = g->q2_b;
-    ra.S = L.S; ra.K = K; ra.nonlinear = p->nonlinear; ra.C = C;
+    if (c.g_classes && (rc = tn_small(c.g_classes, feats, T, C, K, b.part, b.part_b, g->fc_w, g->fc_b, L.splits, w4, st, rowmap))) return rc;
+    ReduceArgs ra = reduce_args(c, L, b);
     // `adam` (dsmil_agg_train_step_bags): optimizer.step() where the gradient elements are formed, every thread on its own
     // element.  Each parameter tensor's LAST READER is an earlier launch than its updater:
     //   q0_w, q2_w   forward (their cut image), k_train_prologue, k_bags_qrow            -> updated by k_bwd_reduce
@@ -465,27 +381,24 @@ int agg_backward_bags_impl(const XT* feats, const XT* vals, const int64_t* offse
     const long long nred = (long long)QD * K + (p->nonlinear ? QD * QD + 2 * QD : QD);
     hipLaunchKernelGGL(k_bwd_reduce, dim3((unsigned)((nred + 255) / 256)), dim3(256), 0, st, ra);
     // the sums over the bags: bag head and the sparse FCLayer term
-    BagsHeadArgs ha{feats, offsets, idx, g_max, rowmap, g->fc_w, g->fc_b, g_pred, Bm, g->fcc_w, g->fcc_b, n_bags, K, Kv, C,
-                    g_classes ? 1 : 0, AdamFuse{}};
+    BagsHeadArgs ha{feats, offsets, c.idx, c.g_max, rowmap, g->fc_w, g->fc_b, c.g_pred, c.Bm, g->fcc_w, g->fcc_b, n_bags, K, Kv, C,
+                    c.g_classes ? 1 : 0, AdamFuse{}};
     if (adam) ha.af = *adam;
-    const long long nhead = (g_max ? (long long)C * K + C : 0) + (long long)C * C * Kv + C;
+    const long long nhead = (c.g_max ? (long long)C * K + C : 0) + (long long)C * C * Kv + C;
     hipLaunchKernelGGL(k_bags_head<XT>, dim3((unsigned)((nhead + 255) / 256)), dim3(256), 0, st, ha);
     if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
     // 9. gradient of the value rows
-    if (g_vals) {
-        if (v4v && (uintptr_t)g_vals % 16 == 0)
-            hipLaunchKernelGGL(k_bags_gvals<4>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, A, gB, rowbag, g_vals, (long long)T, Kv, C);
+    if (c.g_vals) {
+        if (v4v && (uintptr_t)c.g_vals % 16 == 0)
+            hipLaunchKernelGGL(k_bags_gvals<4>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, c.A, b.gB, b.rowbag, c.g_vals, (long long)T, Kv, C);
         else
-            hipLaunchKernelGGL(k_bags_gvals<1>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, A, gB, rowbag, g_vals, (long long)T, Kv, C);
+            hipLaunchKernelGGL(k_bags_gvals<1>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, c.A, b.gB, b.rowbag, c.g_vals, (long long)T, Kv, C);
         if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
     }
     // 10. gradient of the input rows
-    if (g_feats) {
-        GxArgs gx{};
-        gx.L = p->nonlinear ? gH : gz2; gx.W = p->q0_w; gx.out = g_feats; gx.N = T; gx.J = QD; gx.K = K; gx.lvec = 1;
-        gx.gc = g_classes; gx.Wf = p->fc_w; gx.A = vals == feats ? A : nullptr; gx.gB = gB; gx.idx = idx; gx.gmax = g_max;
-        gx.C = (g_classes || g_max || vals == feats) ? C : 0;
-        gx.rowbag = rowbag; gx.offsets = offsets;
+    if (c.g_feats) {
+        GxArgs gx = gx_args(c, b);
+        gx.rowbag = b.rowbag; gx.offsets = offsets;
         if (!gx_launch<false, true>(gx, st)) return DSMIL_E_UNSUPPORTED;
         if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
     }
@@ -493,21 +406,16 @@ int agg_backward_bags_impl(const XT* feats, const XT* vals, const int64_t* offse
 }
 
 // ---- dsmil_agg_train_step_bags / _bf16: one optimiser step on a batch of bags per C call ----------------------------
-// workspace: the batched forward's, bags_layout, the step's own tensors, the eight gradient tensors and, for bf16 rows,
-// the rounded parameter set with its packed MFMA image
+// workspace: the batched forward's, the batched backward's, the step's own tensors, the eight gradient tensors and, for
+// bf16 rows, the rounded parameter set with its packed MFMA image
 struct BagsStepWs {
     size_t fwd, bwd, classes, A, B, pred, idx, gpred, gmax, grads, rounded, image, total;
     size_t fwd_bytes, bwd_bytes;
 };
-inline void step_bags_sizes(int K, int C, int nonlinear, long long (&sizes)[8]) {   // parameter order (ops.W_KEYS)
-    const long long s[8] = {(long long)C * K, C, (long long)QD * K, QD, nonlinear ? QD * QD : 0, nonlinear ? QD : 0,
-                            (long long)C * C * K, C};
-    for (int i = 0; i < 8; ++i) sizes[i] = s[i];
-}
 BagsStepWs step_bags_layout(int n_bags, long long T, int K, int C, int nonlinear, bool b16) {
     BagsStepWs s;
     s.fwd_bytes = dsmil_agg_workspace_bytes(n_bags, T, K, K, C);
-    s.bwd_bytes = bags_layout(n_bags, T, K, K, C, nonlinear).total;
+    s.bwd_bytes = bwd_layout(n_bags, T, K, K, C, nonlinear).total;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t p = o; o = al(o + bytes); return p; };
     s.fwd = take(s.fwd_bytes);
@@ -519,13 +427,12 @@ BagsStepWs step_bags_layout(int n_bags, long long T, int K, int C, int nonlinear
     s.idx = take((size_t)n_bags * C * 8);
     s.gpred = take((size_t)n_bags * C * 4);
     s.gmax = take((size_t)n_bags * C * 4);
-    long long sizes[8];
-    step_bags_sizes(K, C, nonlinear, sizes);
-    s.grads = o;
-    for (int i = 0; i < 8; ++i) take((size_t)sizes[i] * 4);       // each tensor 256-B aligned
+    const ParamSizes sz = param_sizes(K, C, nonlinear);
+    s.grads = o;   // carve_tensors
+    for (int i = 0; i < 8; ++i) take((size_t)sz.n[i] * 4);
     s.rounded = o;
     if (b16)
-        for (int i = 0; i < 8; ++i) take((size_t)sizes[i] * 4);
+        for (int i = 0; i < 8; ++i) take((size_t)sz.n[i] * 4);
     s.image = take(b16 ? dsmil_agg_packed_bf16_bytes(K) : 0);
     s.total = o;
     return s;
@@ -551,12 +458,10 @@ int agg_train_step_bags_impl(const XT* feats, const int64_t* offsets, int32_t n_
     if (p->K <= 0 || p->C <= 0 || p->Kv != p->K) return DSMIL_E_INVALID;
     if (!p->fc_w || !p->fc_b || !p->q0_w || !p->q0_b || !p->fcc_w || !p->fcc_b || (p->nonlinear && (!p->q2_w || !p->q2_b)))
         return DSMIL_E_INVALID;
-    if (opt->step <= 0 || !opt->exp_avg || !opt->exp_avg_sq) return DSMIL_E_INVALID;
     const int K = p->K, C = p->C;
-    long long sizes[8];
-    step_bags_sizes(K, C, p->nonlinear, sizes);
-    for (int i = 0; i < 8; ++i)
-        if (sizes[i] && (!opt->exp_avg[i] || !opt->exp_avg_sq[i])) return DSMIL_E_INVALID;
+    const ParamSizes sz = param_sizes(K, C, p->nonlinear);
+    AdamFuse af;   // optimizer.step() on the masters (af.p), applied by the backward's last two launches
+    if (!adam_fuse(p, sz, opt, af)) return DSMIL_E_INVALID;
     // 2. DSMIL_E_UNSUPPORTED: the limits of the calls the step chains
     if (C > 64 || n_bags > 65535 || T > BAGS_MAX_ROWS) return DSMIL_E_UNSUPPORTED;
     if (B16 && K % 8) return DSMIL_E_UNSUPPORTED;
@@ -575,29 +480,19 @@ int agg_train_step_bags_impl(const XT* feats, const int64_t* offsets, int32_t n_
     float* classes = (float*)(w8 + L.classes); float* A = (float*)(w8 + L.A); float* Bm = (float*)(w8 + L.B);
     float* pred = (float*)(w8 + L.pred); int64_t* idx = (int64_t*)(w8 + L.idx);
     float* gpred = (float*)(w8 + L.gpred); float* gmax = (float*)(w8 + L.gmax);
-    float* masters[8] = {const_cast<float*>(p->fc_w), const_cast<float*>(p->fc_b), const_cast<float*>(p->q0_w),
-                         const_cast<float*>(p->q0_b), const_cast<float*>(p->q2_w), const_cast<float*>(p->q2_b),
-                         const_cast<float*>(p->fcc_w), const_cast<float*>(p->fcc_b)};
-    float* gr[8];
-    float* rnd[8];
-    {
-        size_t o = L.grads, r = L.rounded;
-        for (int i = 0; i < 8; ++i) {
-            gr[i] = (float*)(w8 + o); o = al(o + (size_t)sizes[i] * 4);
-            rnd[i] = (float*)(w8 + r); r = al(r + (size_t)sizes[i] * 4);
-        }
-    }
+    const StepTensors gr = carve_tensors(w8 + L.grads, sz, p->nonlinear);   // the gradients
     int rc;
     dsmil_agg_params pr = *p;   // what the forward and the backward read: the masters, or (bf16 rows) the rounded set
     if constexpr (B16) {
         // straight-through (dsmil_agg_backward_bags_bf16): forward and backward at the rounded weights, Adam on the masters
+        const StepTensors rnd = carve_tensors(w8 + L.rounded, sz, p->nonlinear);   // the rounded set
         RoundTensors rt{};
         long long tot = 0;
-        for (int i = 0; i < 8; ++i) { rt.src[i] = masters[i]; rt.dst[i] = rnd[i]; tot += sizes[i]; rt.end[i] = tot; }
+        for (int i = 0; i < 8; ++i) { rt.src[i] = af.p[i]; rt.dst[i] = rnd.t[i]; tot += sz.n[i]; rt.end[i] = tot; }
         hipLaunchKernelGGL(k_round_bf16, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, rt);
         if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
-        pr.fc_w = rnd[0]; pr.fc_b = rnd[1]; pr.q0_w = rnd[2]; pr.q0_b = rnd[3];
-        pr.q2_w = p->nonlinear ? rnd[4] : nullptr; pr.q2_b = p->nonlinear ? rnd[5] : nullptr; pr.fcc_w = rnd[6]; pr.fcc_b = rnd[7];
+        pr.fc_w = rnd.g.fc_w; pr.fc_b = rnd.g.fc_b; pr.q0_w = rnd.g.q0_w; pr.q0_b = rnd.g.q0_b;
+        pr.q2_w = rnd.g.q2_w; pr.q2_b = rnd.g.q2_b; pr.fcc_w = rnd.g.fcc_w; pr.fcc_b = rnd.g.fcc_b;
         rc = dsmil_agg_pack_bf16(pr.q0_w, pr.q2_w, K, w8 + L.image, stream);
         if (rc) return rc;
         rc = dsmil_agg_forward_bf16(feats, nullptr, offsets, n_bags, T, max_rows, &pr, w8 + L.image, nullptr, classes, A, Bm, pred,
@@ -613,18 +508,11 @@ int agg_train_step_bags_impl(const XT* feats, const int64_t* offsets, int32_t n_
     hipLaunchKernelGGL(k_loss_head_bags_mean, dim3(1), dim3(1024), 0, st, classes, offsets, pred, idx, labels, (int)n_bags, C,
                        1.0f / (float)n_bags, loss_each, loss, gpred, gmax, pos_weight, weight);
     if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
-    // backward + optimizer.step(): scalars formed in double as in dsmil_agg_train_step / dsmil_adam_step
-    dsmil_agg_grads g{};
-    g.fc_w = gr[0]; g.fc_b = gr[1]; g.q0_w = gr[2]; g.q0_b = gr[3]; g.q2_w = p->nonlinear ? gr[4] : nullptr;
-    g.q2_b = p->nonlinear ? gr[5] : nullptr; g.fcc_w = gr[6]; g.fcc_b = gr[7];
-    AdamFuse af{};
-    af.on = 1;
-    for (int i = 0; i < 8; ++i) { af.p[i] = masters[i]; af.m[i] = opt->exp_avg[i]; af.v[i] = opt->exp_avg_sq[i]; }
-    const double bc1 = 1.0 - pow(opt->beta1, (double)opt->step), bc2 = 1.0 - pow(opt->beta2, (double)opt->step);
-    af.h = AdamScalars{(float)(opt->lr / bc1), (float)(1.0 - opt->beta1), (float)opt->beta2, (float)(1.0 - opt->beta2),
-                       (float)opt->eps, (float)opt->weight_decay, (float)sqrt(bc2)};
-    return agg_backward_bags_impl<XT>(feats, nullptr, offsets, n_bags, T, max_rows, &pr, A, Bm, idx, nullptr, gmax, gpred, nullptr,
-                                      nullptr, &g, nullptr, row_map, w8 + L.bwd, L.bwd_bytes, stream, nullptr, &af);
+    // backward + optimizer.step()
+    BwdCall<XT> c{};
+    c.feats = feats; c.N = T; c.p = &pr; c.A = A; c.Bm = Bm; c.idx = idx; c.g_max = gmax; c.g_pred = gpred; c.g = &gr.g;
+    c.rowmap = row_map; c.ws = w8 + L.bwd; c.ws_bytes = L.bwd_bytes; c.stream = stream;
+    return agg_backward_bags_impl(c, offsets, n_bags, max_rows, &af);
 }
 
 }  // namespace
