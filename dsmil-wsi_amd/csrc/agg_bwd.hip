@@ -51,11 +51,11 @@
 #include "agg_split.h"
 #include "agg_hs.h"
 #include "lds_attr.h"
-#define DSMIL_VALUE_BWD
-#include "agg_value.h"
 #include "agg_gx.h"
 
 namespace {
+
+__global__ __launch_bounds__(256, 2) void k_bwd_gx(GxArgs a) { gx_tile<false>(a); }   // (agg_gx.h: step 10, g_feats)
 
 constexpr int NP_BWD = 6;   // plane products per fp32 MAC (the forward's default form)
 
@@ -1805,88 +1805,6 @@ int dsmil_agg_train_step_bags_bf16_w(const void* feats_bf16, const int64_t* offs
                                      const dsmil_bce_weights* bw, void* stream) {
     return agg_train_step_bags_impl<bf16_t>((const bf16_t*)feats_bf16, offsets, n_bags, total_rows, max_rows, nullptr, labels, p,
                                             opt, loss_each, loss, ws, ws_bytes, bw, stream);
-}
-
-// ---- the value stream's parameter gradients (agg_value.h): what autograd derives for dsmil.py:39 behind g_vals ----
-size_t dsmil_value_workspace_bytes(int64_t rows, int32_t K, int32_t Kv) {
-    if (rows <= 0 || K <= 0 || Kv <= 0) return 0;
-    return vp_ws_layout(rows, K, Kv).total;
-}
-
-int dsmil_value_backward(const float* feats, const float* V, const float* g_vals, int64_t rows, int32_t K, int32_t Kv,
-                         const int64_t* row_map, float* g_v_w, float* g_v_b, void* ws, size_t ws_bytes, void* stream) {
-    if (!feats || !V || !g_vals || !g_v_w || !g_v_b || !ws || rows <= 0 || K <= 0 || Kv <= 0) return DSMIL_E_INVALID;
-    if ((uintptr_t)ws % 256) return DSMIL_E_ALIGN;
-    const VpWs L = vp_ws_layout(rows, K, Kv);
-    if (ws_bytes < L.total) return DSMIL_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    VtnArgs a{};
-    a.G = g_vals; a.V = V; a.X = feats; a.rowmap = row_map;
-    a.part = (float*)((char*)ws + L.part); a.pb = (float*)((char*)ws + L.pb);
-    a.N = rows; a.K = K; a.Kv = Kv;
-    vtn_plan(rows, K, Kv, a.S, a.R);
-    a.nsk = (K + 63) / 64; a.nsu = (Kv + 127) / 128;
-    const long long wgs = (long long)a.nsk * a.nsu * a.S;
-    if (wgs > 0x7fffffffLL) return DSMIL_E_UNSUPPORTED;
-    hipLaunchKernelGGL(k_value_tn, dim3((unsigned)wgs), dim3(256), 0, st, a);
-    if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
-    const long long n = (long long)Kv * K + Kv;
-    hipLaunchKernelGGL(k_value_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.part, a.pb, g_v_w, g_v_b, K, Kv, a.S);
-    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
-}
-
-// bf16-stored rows (k_value_tn_b16): the same partial layout and reduce; no weight image in front of the partials
-struct VtnB16Ws { size_t part, pb, total; };
-static VtnB16Ws vtn_b16_ws_layout(long long rows, int K, int Kv) {
-    VtnB16Ws L;
-    int S, R;
-    vtn_plan(rows, K, Kv, S, R);
-    L.part = 0;
-    L.pb = vp_al((size_t)S * Kv * K * 4);
-    L.total = L.pb + vp_al((size_t)S * Kv * 4);
-    return L;
-}
-
-size_t dsmil_value_backward_bf16_workspace_bytes(int64_t rows, int32_t K, int32_t Kv) {
-    if (rows <= 0 || K <= 0 || Kv <= 0) return 0;
-    return vtn_b16_ws_layout(rows, K, Kv).total;
-}
-
-int dsmil_value_backward_bf16(const void* feats_bf16, const void* V_bf16, const float* g_vals, int64_t rows, int32_t K,
-                              int32_t Kv, float* g_v_w, float* g_v_b, void* ws, size_t ws_bytes, void* stream) {
-    if (!feats_bf16 || !V_bf16 || !g_vals || !g_v_w || !g_v_b || !ws || rows <= 0 || K <= 0 || Kv <= 0) return DSMIL_E_INVALID;
-    if (K % 8 || Kv % 4) return DSMIL_E_UNSUPPORTED;
-    VtnB16Args a{};
-    vtn_plan(rows, K, Kv, a.S, a.R);
-    a.nsk = (K + 63) / 64; a.nsu = (Kv + 127) / 128;
-    const long long wgs = (long long)a.nsk * a.nsu * a.S;
-    if (wgs > 0x7fffffffLL) return DSMIL_E_UNSUPPORTED;
-    if ((uintptr_t)feats_bf16 % 16 || (uintptr_t)V_bf16 % 8 || (uintptr_t)g_vals % 16 || (uintptr_t)ws % 256) return DSMIL_E_ALIGN;
-    const VtnB16Ws L = vtn_b16_ws_layout(rows, K, Kv);
-    if (ws_bytes < L.total) return DSMIL_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    a.G = g_vals; a.V = (const bf16_t*)V_bf16; a.X = (const bf16_t*)feats_bf16;
-    a.part = (float*)((char*)ws + L.part); a.pb = (float*)((char*)ws + L.pb);
-    a.N = rows; a.K = K; a.Kv = Kv;
-    hipLaunchKernelGGL(k_value_tn_b16, dim3((unsigned)wgs), dim3(256), 0, st, a);
-    if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
-    const long long n = (long long)Kv * K + Kv;
-    hipLaunchKernelGGL(k_value_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.part, a.pb, g_v_w, g_v_b, K, Kv, a.S);
-    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
-}
-
-int dsmil_value_backward_rows(const float* feats, const float* V, const float* g_vals, int64_t rows, int32_t K, int32_t Kv,
-                              const float* v_w, const void* packed, int32_t accumulate, float* g_feats, void* ws,
-                              size_t ws_bytes, void* stream) {
-    (void)feats; (void)packed; (void)ws_bytes;   // the product reads neither the rows nor the forward's image (agg_gx.h)
-    if (!V || !g_vals || !v_w || !g_feats || rows <= 0 || K <= 0 || Kv <= 0) return DSMIL_E_INVALID;
-    if (ws && ((uintptr_t)ws % 256)) return DSMIL_E_ALIGN;
-    GxArgs gx{};
-    gx.L = g_vals; gx.V = V; gx.W = v_w; gx.out = g_feats; gx.N = rows; gx.J = Kv; gx.K = K;
-    gx.accumulate = accumulate ? 1 : 0;
-    gx.lvec = (Kv % 4 == 0) && (((uintptr_t)g_vals | (uintptr_t)V) % 16 == 0);
-    if (!gx_launch<true>(gx, (hipStream_t)stream)) return DSMIL_E_UNSUPPORTED;
-    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 
 #ifdef DSMIL_TRACE

@@ -206,6 +206,9 @@ __global__ void k_bags_gvals(const float* __restrict__ A, const float* __restric
     }
 }
 
+// g_feats of a batch: agg_gx.h's tile body with the row's own gB / idx / g_max in the tail
+__global__ __launch_bounds__(256, 2) void k_bags_gx(GxArgs a) { gx_tile<false, true>(a); }
+
 // the training objective of every bag of a batch: k_loss_head (agg_fwd.hip), one wave per bag
 __global__ __launch_bounds__(64) void k_loss_head_bags(const float* __restrict__ classes, const int64_t* __restrict__ offsets,
                                                        const float* __restrict__ pred, const int64_t* __restrict__ idx,

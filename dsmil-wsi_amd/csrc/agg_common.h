@@ -42,7 +42,6 @@ constexpr int W_TILE = QD * LDK; // floats per staged weight chunk
 constexpr int R0 = 128;          // rows per workgroup of k_logits_argmax
 
 inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }   // workspace regions start on 256-B boundaries
-__global__ void k_set_offsets(int64_t* off, long long N) { off[0] = 0; off[1] = N; }   // the {0, N} offsets of a lone bag
 
 // Wave-wide sum / max, every lane gets the result.  On DPP: row_ror 8, 4, 2, 1 inside the four 16-lane rows (every lane of a
 // row then holds the row's value), then the four rows through v_readlane and three scalar-operand VALU ops — ~11 instructions,

@@ -716,67 +716,6 @@ __host__ __device__ constexpr long long f3_frag_slot(int chunk, int ub, int plan
     const int m = lane & 15, g = lane >> 4;
     return (long long)(2 * chunk + (g >> 1)) * F2_CHUNK_F4 + ((ub >> 1) * 2 + plane) * 64 + 32 * (g & 1) + (f3_unit(ub, m) & 31);
 }
-
-// fp32 query weights -> two fp16 planes (round to nearest) of the power-of-two scaled values, MFMA-fragment order:
-//   chunk s < nks (GEMM 1):  [t][p][lane (l31,hi)][e] = plane_p(a1 W1[32t + l31][16s + 8hi + e])   (0 past K)
-//   chunk nks + 2t + sx:     [t2][p][lane][e] = plane_p(a2 W2[32t2 + l31][32t + 16sx + (e&3) + 8(e>>2) + 4hi])
-//   trailer (behind chunk nks + 8): {1 / a1, 1 / a2, max_j ||W1[j]||_1}
-// a1 / a2 from max |W1| / max |W2| (f2_scale), computed by every workgroup for itself (same values everywhere).
-__global__ __launch_bounds__(256) void k_pack_agg_f2(const float* __restrict__ q0_w, const float* __restrict__ q2_w,
-                                                     _Float16* __restrict__ out, int K, int nks) {
-    __shared__ float s_m[2][4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float m1 = 0.f, m2 = 0.f;
-    for (long long i = tid; i < (long long)QD * K; i += 256) m1 = fmaxf(m1, fabsf(q0_w[i]));
-    if (q2_w)
-        for (int i = tid; i < QD * QD; i += 256) m2 = fmaxf(m2, fabsf(q2_w[i]));
-    m1 = wave_max(m1);
-    m2 = wave_max(m2);
-    if (lane == 0) { s_m[0][wave] = m1; s_m[1][wave] = m2; }
-    __syncthreads();
-    m1 = fmaxf(fmaxf(s_m[0][0], s_m[0][1]), fmaxf(s_m[0][2], s_m[0][3]));
-    m2 = fmaxf(fmaxf(s_m[1][0], s_m[1][1]), fmaxf(s_m[1][2], s_m[1][3]));
-    float i1, i2;
-    const float a1 = f2_scale(m1, i1), a2 = f2_scale(m2, i2);
-    const long long per = (long long)F2_CHUNK_F4 * 8;   // fp16 per chunk
-    const long long total = (long long)(nks + (q2_w ? 8 : 0)) * per;
-    for (long long i = (long long)blockIdx.x * 256 + tid; i < total; i += (long long)gridDim.x * 256) {
-        const int s = (int)(i / per);
-        int r = (int)(i - s * per);
-        const int e = r & 7; r >>= 3;
-        const int ln = r & 63; r >>= 6;
-        const int p = r & 1, t = r >> 1;
-        const int l31 = ln & 31, hi = ln >> 5;
-        float v;
-        if (s < nks) {
-            const int k = 16 * s + 8 * hi + e;
-            v = k < K ? q0_w[(long long)(32 * t + l31) * K + k] * a1 : 0.f;
-        } else {
-            const int st = s - nks, tt = st >> 1, sx = st & 1;
-            v = q2_w[(32 * t + l31) * QD + 32 * tt + 16 * sx + (e & 3) + 8 * (e >> 2) + 4 * hi] * a2;
-        }
-        const _Float16 h = (_Float16)v;
-        out[i] = p == 0 ? h : (_Float16)(v - (float)h);
-    }
-    if (blockIdx.x == 0) {
-        // trailer[2] = max_j sum_k |W1[j][k]|: with a row's max |x| it bounds the hidden layer of that row (k_attend_f3 scales its
-        // hidden planes by that bound instead of exchanging the row's maximum between the waves)
-        __shared__ float s_n1[4];
-        float n1 = 0.f;
-        for (int j = wave; j < QD; j += 4) {
-            float sum = 0.f;
-            for (int k = lane; k < K; k += 64) sum += fabsf(q0_w[(long long)j * K + k]);
-            n1 = fmaxf(n1, wave_sum(sum));
-        }
-        if (lane == 0) s_n1[wave] = n1;
-        __syncthreads();
-        if (tid == 0) {
-            float* tr = reinterpret_cast<float*>(out + (long long)(nks + 8) * per);
-            tr[0] = i1;
-            tr[1] = i2;
-            tr[2] = fmaxf(fmaxf(s_n1[0], s_n1[1]), fmaxf(s_n1[2], s_n1[3]));
-        }
-    }
-}
+// (the pack kernel of the image, k_pack_agg_f2, is defined in agg_fwd.hip, the one unit that launches it)
 
 }  // namespace

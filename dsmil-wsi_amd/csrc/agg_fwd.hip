@@ -45,11 +45,81 @@
 #include "agg_f2.h"
 #include "agg_f3.h"
 #include "agg_res.h"
-#define DSMIL_VALUE_FWD
-#include "agg_value.h"
 #include "lds_attr.h"
 
 namespace {
+
+// ---- kernels of the shared headers that only this unit launches, defined here so that one object emits them ----
+__global__ void k_set_offsets(int64_t* off, long long N) { off[0] = 0; off[1] = N; }   // the {0, N} offsets of a lone bag
+
+// the image of pack_agg_split_range (agg_split.h) over the whole grid
+__global__ void k_pack_agg_split(const float* __restrict__ q0_w, const float* __restrict__ q2_w,
+                                 bf16_t* __restrict__ out, int K, int nks, int tr = 0) {
+    pack_agg_split_range(q0_w, q2_w, out, K, nks, tr, (long long)blockIdx.x * blockDim.x + threadIdx.x,
+                         (long long)gridDim.x * blockDim.x);
+}
+
+// fp32 query weights -> two fp16 planes (round to nearest) of the power-of-two scaled values, MFMA-fragment order:
+//   chunk s < nks (GEMM 1):  [t][p][lane (l31,hi)][e] = plane_p(a1 W1[32t + l31][16s + 8hi + e])   (0 past K)
+//   chunk nks + 2t + sx:     [t2][p][lane][e] = plane_p(a2 W2[32t2 + l31][32t + 16sx + (e&3) + 8(e>>2) + 4hi])
+//   trailer (behind chunk nks + 8): {1 / a1, 1 / a2, max_j ||W1[j]||_1}
+// a1 / a2 from max |W1| / max |W2| (f2_scale), computed by every workgroup for itself (same values everywhere).
+__global__ __launch_bounds__(256) void k_pack_agg_f2(const float* __restrict__ q0_w, const float* __restrict__ q2_w,
+                                                     _Float16* __restrict__ out, int K, int nks) {
+    __shared__ float s_m[2][4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float m1 = 0.f, m2 = 0.f;
+    for (long long i = tid; i < (long long)QD * K; i += 256) m1 = fmaxf(m1, fabsf(q0_w[i]));
+    if (q2_w)
+        for (int i = tid; i < QD * QD; i += 256) m2 = fmaxf(m2, fabsf(q2_w[i]));
+    m1 = wave_max(m1);
+    m2 = wave_max(m2);
+    if (lane == 0) { s_m[0][wave] = m1; s_m[1][wave] = m2; }
+    __syncthreads();
+    m1 = fmaxf(fmaxf(s_m[0][0], s_m[0][1]), fmaxf(s_m[0][2], s_m[0][3]));
+    m2 = fmaxf(fmaxf(s_m[1][0], s_m[1][1]), fmaxf(s_m[1][2], s_m[1][3]));
+    float i1, i2;
+    const float a1 = f2_scale(m1, i1), a2 = f2_scale(m2, i2);
+    const long long per = (long long)F2_CHUNK_F4 * 8;   // fp16 per chunk
+    const long long total = (long long)(nks + (q2_w ? 8 : 0)) * per;
+    for (long long i = (long long)blockIdx.x * 256 + tid; i < total; i += (long long)gridDim.x * 256) {
+        const int s = (int)(i / per);
+        int r = (int)(i - s * per);
+        const int e = r & 7; r >>= 3;
+        const int ln = r & 63; r >>= 6;
+        const int p = r & 1, t = r >> 1;
+        const int l31 = ln & 31, hi = ln >> 5;
+        float v;
+        if (s < nks) {
+            const int k = 16 * s + 8 * hi + e;
+            v = k < K ? q0_w[(long long)(32 * t + l31) * K + k] * a1 : 0.f;
+        } else {
+            const int st = s - nks, tt = st >> 1, sx = st & 1;
+            v = q2_w[(32 * t + l31) * QD + 32 * tt + 16 * sx + (e & 3) + 8 * (e >> 2) + 4 * hi] * a2;
+        }
+        const _Float16 h = (_Float16)v;
+        out[i] = p == 0 ? h : (_Float16)(v - (float)h);
+    }
+    if (blockIdx.x == 0) {
+        // trailer[2] = max_j sum_k |W1[j][k]|: with a row's max |x| it bounds the hidden layer of that row (k_attend_f3 scales its
+        // hidden planes by that bound instead of exchanging the row's maximum between the waves)
+        __shared__ float s_n1[4];
+        float n1 = 0.f;
+        for (int j = wave; j < QD; j += 4) {
+            float sum = 0.f;
+            for (int k = lane; k < K; k += 64) sum += fabsf(q0_w[(long long)j * K + k]);
+            n1 = fmaxf(n1, wave_sum(sum));
+        }
+        if (lane == 0) s_n1[wave] = n1;
+        __syncthreads();
+        if (tid == 0) {
+            float* tr = reinterpret_cast<float*>(out + (long long)(nks + 8) * per);
+            tr[0] = i1;
+            tr[1] = i2;
+            tr[2] = fmaxf(fmaxf(s_n1[0], s_n1[1]), fmaxf(s_n1[2], s_n1[3]));
+        }
+    }
+}
 
 // --------------------------------------------------------------------------------------------
 // k_logits_argmax: c = x W_i^T + b_i (dsmil.py:11) and per-tile arg-max partials (dsmil.py:52).
@@ -2028,105 +2098,6 @@ int dsmil_agg_pack_f2(const float* q0_w, const float* q2_w, int32_t K, void* pac
     if ((uintptr_t)packed % 16) return DSMIL_E_ALIGN;
     hipLaunchKernelGGL(k_pack_agg_f2, dim3(64), dim3(256), 0, (hipStream_t)stream, q0_w, q2_w, (_Float16*)packed, K,
                        2 * ((K + 31) / 32));
-    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
-}
-
-// ---- the value stream of BClassifier(passing_v=True): V = ReLU(Linear(K, K)(feats)), dsmil.py:35-39,48 (agg_value.h) ----
-size_t dsmil_value_packed_bytes(int32_t K, int32_t Kv) { return (K <= 0 || Kv <= 0) ? 0 : vp_image_bytes(K, Kv); }
-
-int dsmil_value_pack(const float* v_w, int32_t K, int32_t Kv, void* packed, void* stream) {
-    if (!v_w || !packed || K <= 0 || Kv <= 0) return DSMIL_E_INVALID;
-    if ((uintptr_t)packed % 16) return DSMIL_E_ALIGN;
-    hipLaunchKernelGGL(k_pack_value, dim3(256), dim3(256), 0, (hipStream_t)stream, v_w, (_Float16*)packed, K, Kv, vp_nks(K),
-                       vp_ntp(Kv));
-    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
-}
-
-int dsmil_value_forward(const float* feats, int64_t rows, int32_t K, int32_t Kv, const float* v_w, const float* v_b,
-                        const void* packed, const int64_t* row_map, float* V_out, void* ws, size_t ws_bytes, void* stream) {
-    if (!feats || !v_w || !v_b || !V_out || rows <= 0 || K <= 0 || Kv <= 0) return DSMIL_E_INVALID;
-    if (rows * (int64_t)Kv / 256 + 1 > 0x7fffffffLL) return DSMIL_E_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    if (K > VP_MAX_K) {
-        hipLaunchKernelGGL(k_value_proj_valu, dim3((unsigned)((rows * Kv + 255) / 256)), dim3(256), 0, st, feats, row_map, v_w,
-                           v_b, V_out, (long long)rows, K, Kv);
-        return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
-    }
-    if (!packed) {   // cut Wv into the workspace first (a caller with fixed weights packs once: dsmil_value_pack)
-        if (!ws) return DSMIL_E_INVALID;
-        if ((uintptr_t)ws % 256) return DSMIL_E_ALIGN;
-        if (ws_bytes < vp_image_bytes(K, Kv)) return DSMIL_E_WORKSPACE;
-        const int rc = dsmil_value_pack(v_w, K, Kv, ws, stream);
-        if (rc) return rc;
-        packed = ws;
-    }
-    if ((uintptr_t)packed % 16) return DSMIL_E_ALIGN;
-    const int nks = vp_nks(K);
-    const int RG = K <= 512 ? 2 : 1;
-    const int lds = nks * 4 * (32 * RG) * 16 + 32 * RG * 4;
-    const int vec = (K % 4 == 0) && ((uintptr_t)feats % 16 == 0);
-    const bool full = vec && K % 32 == 0;
-    void (*fn)(const float*, const int64_t*, const f32x4*, const float*, float*, long long, int, int, int) =
-        RG == 2 ? (full ? (nks == 32 ? k_value_proj<2, 32, true> : k_value_proj<2, 0, true>) : k_value_proj<2, 0, false>)
-                : (full ? k_value_proj<1, 0, true> : k_value_proj<1, 0, false>);
-    if (!dsmil_lds::allow((const void*)fn, lds)) return DSMIL_E_LAUNCH;
-    const long long tiles = (rows + 32 * RG - 1) / (32 * RG);
-    hipLaunchKernelGGL(fn, dim3((unsigned)tiles), dim3(VP_THREADS), lds, st, feats, row_map, (const f32x4*)packed, v_b, V_out,
-                       (long long)rows, K, Kv, vec);
-    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
-}
-
-// ---- the same layer on bf16-stored rows (k_pack_value_b16, k_value_proj_b16, k_value_proj_b16_valu: agg_value.h) ----
-size_t dsmil_value_packed_bf16_bytes(int32_t K, int32_t Kv) { return (K <= 0 || Kv <= 0) ? 0 : vb_image_bytes(K, Kv); }
-
-int dsmil_value_pack_bf16(const float* v_w, int32_t K, int32_t Kv, void* packed, void* stream) {
-    if (!v_w || !packed || K <= 0 || Kv <= 0) return DSMIL_E_INVALID;
-    if ((uintptr_t)packed % 16) return DSMIL_E_ALIGN;
-    hipLaunchKernelGGL(k_pack_value_b16, dim3(256), dim3(256), 0, (hipStream_t)stream, v_w, (bf16_t*)packed, K, Kv, vp_nks(K),
-                       vp_ntp(Kv));
-    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
-}
-
-size_t dsmil_value_workspace_bf16_bytes(int64_t rows, int32_t K, int32_t Kv) {
-    if (rows <= 0 || K <= 0 || Kv <= 0 || K > VB_MAX_K) return 0;   // (the plain kernel of wider rows reads v_w itself)
-    return vp_al(vb_image_bytes(K, Kv));
-}
-
-int dsmil_value_forward_bf16(const void* feats_bf16, int64_t rows, int32_t K, int32_t Kv, const float* v_w, const float* v_b,
-                             const void* packed, void* V_out_bf16, void* ws, size_t ws_bytes, void* stream) {
-    if (!feats_bf16 || !v_w || !v_b || !V_out_bf16 || rows <= 0 || K <= 0 || Kv <= 0) return DSMIL_E_INVALID;
-    if ((K % 8) || (Kv % 4)) return DSMIL_E_UNSUPPORTED;
-    if (((uintptr_t)feats_bf16 % 16) || ((uintptr_t)V_out_bf16 % 4)) return DSMIL_E_ALIGN;
-    if (rows * (int64_t)Kv / 256 + 1 > 0x7fffffffLL) return DSMIL_E_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    const bf16_t* x = (const bf16_t*)feats_bf16;
-    bf16_t* V = (bf16_t*)V_out_bf16;
-    if (K > VB_MAX_K) {
-        hipLaunchKernelGGL(k_value_proj_b16_valu, dim3((unsigned)((rows * Kv + 255) / 256)), dim3(256), 0, st, x, v_w, v_b, V,
-                           (long long)rows, K, Kv);
-        return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
-    }
-    const bool cut = !packed;   // round Wv into the workspace first (a caller with fixed weights packs once: dsmil_value_pack_bf16)
-    if (cut) {
-        if (!ws) return DSMIL_E_INVALID;
-        if ((uintptr_t)ws % 256) return DSMIL_E_ALIGN;
-        if (ws_bytes < vb_image_bytes(K, Kv)) return DSMIL_E_WORKSPACE;
-        packed = ws;
-    }
-    if ((uintptr_t)packed % 16) return DSMIL_E_ALIGN;
-    if (cut) {
-        const int rc = dsmil_value_pack_bf16(v_w, K, Kv, ws, stream);
-        if (rc) return rc;
-    }
-    const int nks = vp_nks(K);
-    const int lds = 2 * nks * VB_BM * 16;
-    const bool full = K % 64 == 0;
-    void (*fn)(const bf16_t*, const f32x4*, const float*, bf16_t*, long long, int, int) =
-        full ? (nks == 32 ? k_value_proj_b16<32, true> : k_value_proj_b16<0, true>) : k_value_proj_b16<0, false>;
-    if (!dsmil_lds::allow((const void*)fn, lds)) return DSMIL_E_LAUNCH;
-    const long long tiles = (rows + VB_BM - 1) / VB_BM;
-    hipLaunchKernelGGL(fn, dim3((unsigned)tiles), dim3(VP_THREADS), lds, st, x, (const f32x4*)packed, v_b, V, (long long)rows, K,
-                       Kv);
     return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 

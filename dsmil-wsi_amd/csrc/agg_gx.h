@@ -1,4 +1,5 @@
-// agg_gx.h — the gradient of the INPUT rows of the aggregator and of the value layer.  Included from agg_bwd.hip.
+// agg_gx.h — the gradient of the INPUT rows of the aggregator and of the value layer.  Included from agg_bwd.hip (k_bwd_gx,
+// k_bags_gx) and, through agg_value.h, from agg_value.hip (k_value_gx): the tile body, the arguments and the launcher.
 //
 //   k_bwd_gx    g_x [N,K] = G W1  (+ g_c Wf) (+ g_max[c] Wf[c] at row idx_c) (+ A gB)       G = gH (gz2 for the linear query)
 //   k_value_gx  g_x [N,K] (+)= (g_vals o [V > 0]) Wv                                        dsmil.py:35-39,48
@@ -238,9 +239,11 @@ __device__ __forceinline__ void gx_tile(const GxArgs& a) {
         }
 }
 
-__global__ __launch_bounds__(256, 2) void k_bwd_gx(GxArgs a) { gx_tile<false>(a); }
-__global__ __launch_bounds__(256, 2) void k_value_gx(GxArgs a) { gx_tile<true>(a); }
-__global__ __launch_bounds__(256, 2) void k_bags_gx(GxArgs a) { gx_tile<false, true>(a); }
+// the three kernels are one-line wrappers of gx_tile, each DEFINED in the one unit that launches it, so that each is emitted
+// once: k_bwd_gx in agg_bwd.hip, k_bags_gx in agg_bwd_bags.h, k_value_gx in agg_value.h
+__global__ void k_bwd_gx(GxArgs a);
+__global__ void k_value_gx(GxArgs a);
+__global__ void k_bags_gx(GxArgs a);
 
 // fills the grid fields and launches; returns false when the grid does not fit
 template <bool MASK, bool BAGS = false>

@@ -562,10 +562,6 @@ __device__ __forceinline__ void pack_agg_split_range(const float* __restrict__ q
         out[i] = (bf16_t)(bits >> 16);
     }
 }
-__global__ void k_pack_agg_split(const float* __restrict__ q0_w, const float* __restrict__ q2_w,
-                                 bf16_t* __restrict__ out, int K, int nks, int tr = 0) {
-    pack_agg_split_range(q0_w, q2_w, out, K, nks, tr, (long long)blockIdx.x * blockDim.x + threadIdx.x,
-                         (long long)gridDim.x * blockDim.x);
-}
+// (k_pack_agg_split, this range over a whole grid, is defined in agg_fwd.hip, the one unit that launches it)
 
 }  // namespace

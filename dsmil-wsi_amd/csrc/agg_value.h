@@ -1,7 +1,8 @@
 // agg_value.h — the value stream of BClassifier(passing_v=True), dsmil.py:35-39,48:  V = ReLU(x Wv^T + bv)  and its
-// parameter gradients.  Included from agg_fwd.hip (DSMIL_VALUE_FWD: k_pack_value, k_value_proj, k_value_proj_valu and, for
-// bf16-stored rows, k_pack_value_b16, k_value_proj_b16, k_value_proj_b16_valu: described above them) and from agg_bwd.hip
-// (DSMIL_VALUE_BWD: k_value_tn, k_value_reduce and, for bf16-stored rows, k_value_tn_b16: described above it).
+// gradients.  Included from agg_value.hip alone, the unit that holds the layer's entries: the forward's k_pack_value,
+// k_value_proj, k_value_proj_valu and, for bf16-stored rows, k_pack_value_b16, k_value_proj_b16, k_value_proj_b16_valu
+// (described above them); the parameter gradients' k_value_tn, k_value_reduce and, for bf16-stored rows, k_value_tn_b16
+// (described above it); the input-row gradient's k_value_gx, a wrapper of agg_gx.h's tile body.
 //
 // Forward, k_value_proj.  A GEMM with Kv output columns per row on v_mfma_f32_32x32x16_f16 in the arithmetic of agg_f2.h:
 // x' = x * 2^e per ROW, Wv' = Wv * 2^f per TENSOR (f2_scale), both cut into two fp16 planes (split2h_scaled / the pack
@@ -30,6 +31,7 @@
 #pragma once
 #include "agg_f2.h"
 #include "agg_split.h"
+#include "agg_gx.h"
 
 namespace {
 
@@ -52,19 +54,19 @@ inline void vtn_plan(long long rows, int K, int Kv, int& S, int& R) {
     R = (int)r;
     S = (int)((rows + r - 1) / r);
 }
-struct VpWs { size_t image, part, pb, total; };
-inline VpWs vp_ws_layout(long long rows, int K, int Kv) {
+// the backward's workspace: the row-range partials behind `image_bytes` of weight image (fp32: the forward's image, which a
+// caller may cut there, vp_image_bytes; bf16-stored rows: 0, the partials start the workspace)
+struct VpWs { size_t part, pb, total; };
+inline VpWs vp_ws_layout(long long rows, int K, int Kv, size_t image_bytes) {
     VpWs L;
     int S, R;
     vtn_plan(rows, K, Kv, S, R);
-    L.image = 0;
-    L.part = vp_al(vp_image_bytes(K, Kv));
+    L.part = vp_al(image_bytes);
     L.pb = L.part + vp_al((size_t)S * Kv * K * 4);
     L.total = L.pb + vp_al((size_t)S * Kv * 4);
     return L;
 }
 
-#ifdef DSMIL_VALUE_FWD
 // fp32 Wv [Kv, K] -> two fp16 planes of a Wv (a = f2_scale(max |Wv|)), B-fragment order:
 //   [step s][tile t][plane p][lane (l31, hi)][e] = plane_p(a Wv[32 t + l31][16 s + 8 hi + e])   (0 past Kv / K)
 //   trailer: {1 / a}
@@ -442,9 +444,7 @@ __global__ __launch_bounds__(256) void k_value_proj_b16_valu(const bf16_t* __res
     s += bias[j];
     V[i] = f2bf(s < 0.f ? 0.f : s);
 }
-#endif  // DSMIL_VALUE_FWD
 
-#ifdef DSMIL_VALUE_BWD
 constexpr int VTN_LDW = 20;      // 32-bit words per (plane, column) row of the staged operands: 16 row pairs + 4 pad (k_tn_split's)
 struct VtnArgs {
     const float* G;              // g_vals [N, Kv]   (logical row order)
@@ -771,6 +771,8 @@ __global__ __launch_bounds__(256) void k_value_reduce(const float* __restrict__ 
         g_b[j] = s;
     }
 }
-#endif  // DSMIL_VALUE_BWD
+
+// the gradient of the layer's input rows, g_x (+)= (g_vals o [V > 0]) Wv: agg_gx.h's tile body with the ReLU mask
+__global__ __launch_bounds__(256, 2) void k_value_gx(GxArgs a) { gx_tile<true>(a); }
 
 }  // namespace

@@ -149,11 +149,16 @@ def offsets_tensor(lengths, device):
     return t
 
 
+def _cuda(t, name):
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must be a CUDA(HIP) tensor for the native path")
+    return t
+
+
 def _f32c(t, name):
     if t is None:
         return None
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} must be a CUDA(HIP) tensor for the native path")
+    _cuda(t, name)
     if t.dtype != torch.float32:
         raise RuntimeError(f"{name} must be float32 (got {t.dtype})")
     return t if t.is_contiguous() else t.contiguous()
@@ -381,27 +386,6 @@ def _value_params_b16(v_w, v_b, dev):
     return _cached(_split_cache, ("value_b16", str(dev), _tkey(v_w), _tkey(v_b)), dev, [v_w, v_b], make)
 
 
-def _value_proj_b16(feats, v_w, v_b):
-    """dsmil_value_forward_bf16: bf16 rows [rows, K] -> bf16 V [rows, Kv] in one native launch."""
-    if not (feats.is_cuda and v_w.is_cuda and v_b.is_cuda):
-        raise RuntimeError("feats, v_w and v_b must be CUDA(HIP) tensors for the native path")
-    feats = feats if feats.is_contiguous() else feats.contiguous()
-    dev = feats.device
-    rows, K = feats.shape
-    Kv = v_w.shape[0]
-    if v_w.shape[1] != K or v_b.numel() != Kv:
-        raise ValueError(f"v_w must be [Kv,{K}] and v_b [Kv], got {tuple(v_w.shape)} / {tuple(v_b.shape)}")
-    V = torch.empty((rows, Kv), dtype=torch.bfloat16, device=dev)
-    if rows == 0:
-        return V
-    packed, w32, b32 = _value_params_b16(v_w, v_b, dev)
-    with torch.cuda.device(dev):
-        rc = _native.lib().dsmil_value_forward_bf16(_ptr(feats), rows, K, Kv, _ptr(w32), _ptr(b32), _ptr(packed), _ptr(V), None, 0,
-                                                    _stream(dev))
-    _native.check(rc, "dsmil_value_forward_bf16")
-    return V
-
-
 def value_proj(feats, v_w, v_b, row_map=None):
     """dsmil_value_forward: V = ReLU(feats @ v_w^T + v_b), the Linear + ReLU of BClassifier.v (dsmil.py:35-39,48), in ONE
     native launch (fp32 in, fp32 out; the weight planes are cut once per weight set).  feats [rows, K] fp32 CUDA, v_w [Kv, K],
@@ -409,11 +393,13 @@ def value_proj(feats, v_w, v_b, row_map=None):
     bf16 ``feats`` select dsmil_value_forward_bf16 (the bf16-storage path: v_w and v_b — fp32 masters or bf16 parameters —
     are rounded to bf16, fp32 accumulation, one bf16 MFMA product per MAC): bf16 V [rows, Kv], no row map (its
     parameter gradients: value_proj_backward on the same bf16 rows)."""
-    if feats.dtype == torch.bfloat16:
+    b16 = feats.dtype == torch.bfloat16
+    if b16:   # v_w, v_b stay as they are: _value_params_b16 rounds them once per weight set, keyed by their own addresses
         if row_map is not None:
             raise ValueError("row_map is implemented for the fp32 path")
-        return _value_proj_b16(feats, v_w, v_b)
-    feats = _f32c(feats, "feats"); v_w = _f32c(v_w, "v_w"); v_b = _f32c(v_b, "v_b")
+        feats = _cuda(feats, "feats").contiguous(); _cuda(v_w, "v_w"); _cuda(v_b, "v_b")
+    else:
+        feats = _f32c(feats, "feats"); v_w = _f32c(v_w, "v_w"); v_b = _f32c(v_b, "v_b")
     dev = feats.device
     rows, K = feats.shape
     Kv = v_w.shape[0]
@@ -421,43 +407,22 @@ def value_proj(feats, v_w, v_b, row_map=None):
         raise ValueError(f"v_w must be [Kv,{K}] and v_b [Kv], got {tuple(v_w.shape)} / {tuple(v_b.shape)}")
     row_map = _i64c(row_map, "row_map")
     n = int(row_map.numel()) if row_map is not None else rows
-    V = torch.empty((n, Kv), dtype=torch.float32, device=dev)
+    V = torch.empty((n, Kv), dtype=feats.dtype, device=dev)
     if n == 0:
         return V
-    packed = _value_params(v_w, dev)
-    with torch.cuda.device(dev):
-        rc = _native.lib().dsmil_value_forward(_ptr(feats), n, K, Kv, _ptr(v_w), _ptr(v_b), _ptr(packed), _ptr(row_map), _ptr(V),
-                                               None, 0, _stream(dev))
-    _native.check(rc, "dsmil_value_forward")
-    return V
-
-
-def _value_proj_backward_b16(feats, V, g_vals):
-    """dsmil_value_backward_bf16: bf16 rows [rows, K], bf16 V [rows, Kv], fp32 g_vals -> fp32 (g_v_w, g_v_b), two native
-    launches."""
-    if not (feats.is_cuda and V.is_cuda and g_vals.is_cuda):
-        raise RuntimeError("feats, V and g_vals must be CUDA(HIP) tensors for the native path")
-    if V.dtype != torch.bfloat16 or g_vals.dtype != torch.float32:
-        raise ValueError(f"bf16 rows take a bf16 V and fp32 g_vals, got {V.dtype} / {g_vals.dtype}")
-    if feats.dim() != 2 or V.dim() != 2 or V.shape[0] != feats.shape[0] or g_vals.shape != V.shape:
-        raise ValueError(f"V / g_vals must be [{feats.shape[0]},Kv], got {tuple(V.shape)} / {tuple(g_vals.shape)}")
-    feats = feats if feats.is_contiguous() else feats.contiguous()
-    V = V if V.is_contiguous() else V.contiguous()
-    g_vals = g_vals if g_vals.is_contiguous() else g_vals.contiguous()
-    dev = feats.device
-    n, K = feats.shape
-    Kv = V.shape[1]
-    g_w = torch.empty((Kv, K), dtype=torch.float32, device=dev)
-    g_b = torch.empty((Kv,), dtype=torch.float32, device=dev)
-    if n == 0:
-        return g_w.zero_(), g_b.zero_()
     L = _native.lib()
-    ws = _workspace(dev, L.dsmil_value_backward_bf16_workspace_bytes(n, K, Kv))
+    if b16:
+        packed, w32, b32 = _value_params_b16(v_w, v_b, dev)
+        entry, call = "dsmil_value_forward_bf16", lambda: L.dsmil_value_forward_bf16(
+            _ptr(feats), n, K, Kv, _ptr(w32), _ptr(b32), _ptr(packed), _ptr(V), None, 0, _stream(dev))
+    else:
+        packed = _value_params(v_w, dev)
+        entry, call = "dsmil_value_forward", lambda: L.dsmil_value_forward(
+            _ptr(feats), n, K, Kv, _ptr(v_w), _ptr(v_b), _ptr(packed), _ptr(row_map), _ptr(V), None, 0, _stream(dev))
     with torch.cuda.device(dev):
-        rc = L.dsmil_value_backward_bf16(_ptr(feats), _ptr(V), _ptr(g_vals), n, K, Kv, _ptr(g_w), _ptr(g_b), _ptr(ws),
-                                         ws.numel(), _stream(dev))
-    _native.check(rc, "dsmil_value_backward_bf16")
-    return g_w, g_b
+        rc = call()
+    _native.check(rc, entry)
+    return V
 
 
 def value_proj_backward(feats, V, g_vals, row_map=None):
@@ -467,27 +432,38 @@ def value_proj_backward(feats, V, g_vals, row_map=None):
     bf16 ``feats`` select dsmil_value_backward_bf16 (the bf16-storage path): V must then be the bf16 V of ``value_proj`` and
     g_vals fp32 (the bf16 aggregator backward's, unrounded); the operands are read as they are stored — no fp32 copy of
     either — and the results are fp32; no row map."""
-    if feats.dtype == torch.bfloat16:
+    b16 = feats.dtype == torch.bfloat16
+    if b16:
         if row_map is not None:
             raise ValueError("row_map is implemented for the fp32 path")
-        return _value_proj_backward_b16(feats, V, g_vals)
-    feats = _f32c(feats, "feats"); V = _f32c(V, "V"); g_vals = _f32c(g_vals, "g_vals")
+        _cuda(feats, "feats"); _cuda(V, "V"); _cuda(g_vals, "g_vals")
+        if V.dtype != torch.bfloat16 or g_vals.dtype != torch.float32:
+            raise ValueError(f"bf16 rows take a bf16 V and fp32 g_vals, got {V.dtype} / {g_vals.dtype}")
+        feats, V, g_vals = feats.contiguous(), V.contiguous(), g_vals.contiguous()
+    else:
+        feats = _f32c(feats, "feats"); V = _f32c(V, "V"); g_vals = _f32c(g_vals, "g_vals")
     dev = feats.device
-    K = feats.shape[1]
-    n, Kv = V.shape
     row_map = _i64c(row_map, "row_map")
-    if tuple(g_vals.shape) != (n, Kv) or n != (int(row_map.numel()) if row_map is not None else feats.shape[0]):
-        raise ValueError(f"V / g_vals must be [rows,{Kv}], got {tuple(V.shape)} / {tuple(g_vals.shape)}")
+    n = int(row_map.numel()) if row_map is not None else feats.shape[0]
+    if feats.dim() != 2 or V.dim() != 2 or V.shape[0] != n or g_vals.shape != V.shape:
+        raise ValueError(f"V / g_vals must be [{n},Kv], got {tuple(V.shape)} / {tuple(g_vals.shape)}")
+    K, Kv = feats.shape[1], V.shape[1]
     g_w = torch.empty((Kv, K), dtype=torch.float32, device=dev)
     g_b = torch.empty((Kv,), dtype=torch.float32, device=dev)
     if n == 0:
         return g_w.zero_(), g_b.zero_()
     L = _native.lib()
-    ws = _workspace(dev, L.dsmil_value_workspace_bytes(n, K, Kv))
+    if b16:
+        entry, ws = "dsmil_value_backward_bf16", _workspace(dev, L.dsmil_value_backward_bf16_workspace_bytes(n, K, Kv))
+        call = lambda: L.dsmil_value_backward_bf16(_ptr(feats), _ptr(V), _ptr(g_vals), n, K, Kv, _ptr(g_w), _ptr(g_b), _ptr(ws),
+                                                   ws.numel(), _stream(dev))
+    else:
+        entry, ws = "dsmil_value_backward", _workspace(dev, L.dsmil_value_workspace_bytes(n, K, Kv))
+        call = lambda: L.dsmil_value_backward(_ptr(feats), _ptr(V), _ptr(g_vals), n, K, Kv, _ptr(row_map), _ptr(g_w), _ptr(g_b),
+                                              _ptr(ws), ws.numel(), _stream(dev))
     with torch.cuda.device(dev):
-        rc = L.dsmil_value_backward(_ptr(feats), _ptr(V), _ptr(g_vals), n, K, Kv, _ptr(row_map), _ptr(g_w), _ptr(g_b), _ptr(ws),
-                                    ws.numel(), _stream(dev))
-    _native.check(rc, "dsmil_value_backward")
+        rc = call()
+    _native.check(rc, entry)
     return g_w, g_b
 
 

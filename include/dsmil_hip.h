@@ -388,7 +388,7 @@ int dsmil_agg_backward_bags_bf16(const void* feats_bf16, const void* vals_bf16, 
  *                        g_feats [rows, K] = (g_vals * (V > 0)) v_w, or g_feats += that with accumulate != 0 (the
  *                        aggregator's own g_feats and this term then share one buffer, no separate add pass).  Logical row
  *                        order throughout.  gZ is never written to memory; bf16 MFMA over exact three-plane cuts, six plane
- *                        products, fixed order: two runs give the same bits.  One launch (k_value_gx, csrc/agg_gx.h), any K
+ *                        products, fixed order: two runs give the same bits.  One launch (k_value_gx: csrc/agg_gx.h's tile), any K
  *                        and Kv on the matrix cores.  feats and packed are not read by this product (v_w is cut as it is
  *                        staged: the forward's image is ordered along K, this contraction runs along Kv) and may be NULL;
  *                        it needs no workspace: ws may be NULL (ws_bytes 0); a non-NULL ws must be 256-B aligned.

@@ -289,9 +289,9 @@ class Driver:
 W_KEYS = ("fc_w", "fc_b", "q0_w", "q0_b", "q2_w", "q2_b", "fcc_w", "fcc_b")
 
 
-def trace_case(lib_path, name, timeout):
+def trace_case(lib_path, name, timeout, script=os.path.abspath(__file__)):
     with tempfile.TemporaryDirectory() as d:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "-f", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "-f", "csv", "-d", d, "--", sys.executable, script,
                "case", "--lib", lib_path, "--case", name]
         subprocess.run(cmd, check=True, timeout=timeout, stdout=subprocess.DEVNULL)
         rows = []
@@ -300,7 +300,8 @@ def trace_case(lib_path, name, timeout):
     rows.sort(key=lambda r: int(r.get("Dispatch_Id") or r.get("Start_Timestamp")))
     out = []
     for r in rows:
-        m = re.search(r"(?:^|[\s:])(k_[a-z0-9_]+(?:<.*>)?)", r["Kernel_Name"])
+        # (a name the profiler leaves mangled, as k_pack_value's with its _Float16 argument, has its length in front)
+        m = re.search(r"(?:^|[\s:\d])(k_[a-z0-9_]+(?:<.*>)?)", r["Kernel_Name"])
         if not m:
             continue   # the framework's own kernels (tensor fills, casts)
         dims = lambda stem: [int(r[k]) for k in (stem + "_X", stem + "_Y", stem + "_Z") if k in r] or [int(r[stem])]  # noqa: E731
@@ -309,10 +310,10 @@ def trace_case(lib_path, name, timeout):
     return out
 
 
-def compare_bits(dir_a, dir_b):
+def compare_bits(dir_a, dir_b, cases=None):
     import numpy as np
     res = {"a": os.path.basename(os.path.normpath(dir_a)), "b": os.path.basename(os.path.normpath(dir_b)), "cases": {}}
-    for name in CASES:
+    for name in (CASES if cases is None else cases):
         fa = sorted(os.listdir(os.path.join(dir_a, name))) if os.path.isdir(os.path.join(dir_a, name)) else []
         fb = sorted(os.listdir(os.path.join(dir_b, name))) if os.path.isdir(os.path.join(dir_b, name)) else []
         tensors = {}

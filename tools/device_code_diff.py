@@ -1,9 +1,13 @@
 #!/usr/bin/env python
-"""Is the device code of one translation unit the same in two trees?  For a change that claims "host code only".
+"""Is the device code of one translation unit, or of a set of them, the same in two trees?  For a change that claims
+"host code only", or that moves kernels between units.
 
-    python tools/device_code_diff.py <parent tree> <new tree> dsmil-wsi_amd/csrc/agg_bwd.hip [--allow-missing k_name ...] [--out F.json]
+    python tools/device_code_diff.py <parent tree> <new tree> dsmil-wsi_amd/csrc/agg_bwd.hip [more units ...]
+                                     [--new-files unit ...] [--allow-missing k_name ...] [--out F.json]
 
-Compiles the file in both trees device-only to assembly with build.py's flags (--cuda-device-only -S), once as the
+The units named first are the parent's; --new-files names the new tree's where the set differs (default: the same).  A
+side's symbols are the union over its units, and a symbol that two units of one side emit is reported (`emitted_twice`).
+Compiles every unit device-only device-only to assembly with build.py's flags (--cuda-device-only -S), once as the
 product and once with -DDSMIL_EXPERIMENTS, and compares per kernel symbol: the symbol sets and every symbol's
 instruction stream, with comments, assembler directives and the numbering of local labels taken out (they move with
 the line numbers of the source).  It compares only: it reads no instruction's meaning and looks for nothing.
@@ -59,8 +63,18 @@ def kernels(asm):
     return {k: v for k, v in out.items() if k in names or any(not s.endswith(":") for s in v)}
 
 
-def compare(parent, new, rel, extra, allow_missing):
-    a, b = kernels(assembly(parent, rel, extra)), kernels(assembly(new, rel, extra))
+def side(tree, rels, extra):
+    """The union of the units' symbols and the symbols that more than one unit emits."""
+    out, twice = {}, []
+    for rel in rels:
+        k = kernels(assembly(tree, rel, extra))
+        twice += sorted(set(k) & set(out))
+        out.update(k)
+    return out, twice
+
+
+def compare(parent, new, rels, new_rels, extra, allow_missing):
+    (a, twice_a), (b, twice_b) = side(parent, rels, extra), side(new, new_rels, extra)
     missing = sorted(set(a) - set(b))
     added = sorted(set(b) - set(a))
     differing = sorted(k for k in set(a) & set(b) if a[k] != b[k])
@@ -69,6 +83,7 @@ def compare(parent, new, rel, extra, allow_missing):
             "instructions_parent": sum(len(v) for v in a.values()), "instructions_new": sum(len(v) for v in b.values()),
             "only_in_parent": missing, "only_in_new": added, "allowed_missing": excused,
             "symbol_sets_equal": not added and missing == excused,
+            "emitted_twice_parent": twice_a, "emitted_twice_new": twice_b,
             "differing_instruction_streams": len(differing), "differing": differing}
 
 
@@ -76,15 +91,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("parent")
     ap.add_argument("new")
-    ap.add_argument("file", help="path of the .hip file relative to a tree's root")
+    ap.add_argument("files", nargs="+", help="paths of the .hip files relative to a tree's root")
+    ap.add_argument("--new-files", nargs="+", default=None, metavar="FILE", help="the new tree's units (default: the same)")
     ap.add_argument("--allow-missing", nargs="*", default=[], metavar="KERNEL")
     ap.add_argument("--out")
     a = ap.parse_args()
-    res = {"compile": "build.py's HIPCC + BASE_FLAGS [-DDSMIL_EXPERIMENTS] --cuda-device-only -S " + a.file,
-           "product": compare(a.parent, a.new, a.file, [], a.allow_missing),
-           "experiment": compare(a.parent, a.new, a.file, ["-DDSMIL_EXPERIMENTS"], a.allow_missing)}
+    new_files = a.new_files or a.files
+    res = {"compile": "build.py's HIPCC + BASE_FLAGS [-DDSMIL_EXPERIMENTS] --cuda-device-only -S, per unit",
+           "units_parent": a.files, "units_new": new_files,
+           "product": compare(a.parent, a.new, a.files, new_files, [], a.allow_missing),
+           "experiment": compare(a.parent, a.new, a.files, new_files, ["-DDSMIL_EXPERIMENTS"], a.allow_missing)}
     res["same_device_code"] = all(res[k]["symbol_sets_equal"] and not res[k]["differing_instruction_streams"] and
-                                  res[k]["symbols_new"] > 0 for k in ("product", "experiment"))
+                                  not res[k]["emitted_twice_new"] and res[k]["symbols_new"] > 0
+                                  for k in ("product", "experiment"))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         json.dump(res, open(a.out, "w"), indent=1)
