@@ -289,6 +289,11 @@ SIGNATURES = {
     "dsmil_conv_bwd_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32] * 9),
     "dsmil_conv_bwd_weight": (ctypes.c_int, [c_f32p] * 5 + [ctypes.c_int32] * 8 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "dsmil_conv_bwd_data": (ctypes.c_int, [c_f32p] * 3 + [ctypes.c_int32] * 8 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # InstanceNorm / ReLU / residual-add backward for embedder training
+    "dsmil_norm_bwd_plan": (ctypes.c_int, [ctypes.c_int32] * 4 + [ctypes.POINTER(ctypes.c_int32)]),
+    "dsmil_norm_bwd_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32] * 4),
+    "dsmil_norm_bwd": (ctypes.c_int, [ctypes.c_int32] + [c_f32p] * 11 + [ctypes.c_int32] * 3 +
+                       [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "dsmil_agg_forward": (ctypes.c_int, [c_f32p, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64,
                                          ctypes.c_int64, ctypes.POINTER(AggParams), c_f32p, c_f32p,
                                          c_f32p, c_f32p, c_f32p, c_i64p, ctypes.c_void_p,

@@ -1387,6 +1387,84 @@ def conv_backward_supported(Cin, Cout, ks, stride, pad, B, H, W, which):
 
 
 # ---------------------------------------------------------------------------------------------
+# InstanceNorm / ReLU / residual-add backward for training the embedder (csrc/norm_bwd.hip behind dsmil_norm_bwd*): the gradient
+# of a RAW conv output from the gradient of relu(IN(y)) or of a block's relu(IN(y) + identity | IN(yd)).  Refusals as for the
+# conv backward: NotImplementedError for DSMIL_E_UNSUPPORTED, RuntimeError otherwise, nothing launched in either case.
+# ---------------------------------------------------------------------------------------------
+NORM_BWD_KINDS = {"relu": 0, "add": 1, "add_down": 2}
+_NORM_BWD_PLAN_FIELDS = ("kind", "chunk", "n_partials", "run_len", "lanes", "n_sums", "grid_partial", "grid_finish", "grid_apply",
+                         "block", "groups")
+
+
+def _nb_check(rc, what):
+    if rc == _native.DSMIL_E_UNSUPPORTED:
+        raise NotImplementedError(f"{what}: shape outside what the norm backward kernels implement")
+    _native.check(rc, what)
+
+
+def norm_backward_plan(kind, B, HW, C):
+    """What the host decides for this call (no device needed): a dict of ``chunk`` (pixels per chunk), ``n_partials`` (partials
+    an (n, c) sum is added from, in chunk order), ``lanes`` (accumulators per channel and chunk, combined in a fixed tree),
+    ``run_len`` (the longest serial run of terms one accumulator adds), ``n_sums`` (2; "add_down" 3), ``grid_partial,
+    grid_finish, grid_apply, block`` and ``groups`` (4-channel groups per thread)."""
+    out = (ctypes.c_int32 * 16)()
+    rc = _native.lib().dsmil_norm_bwd_plan(NORM_BWD_KINDS[kind], B, HW, C, out)
+    _nb_check(rc, "dsmil_norm_bwd_plan")
+    d = dict(zip(_NORM_BWD_PLAN_FIELDS, list(out)))
+    d["kind"] = kind
+    return d
+
+
+def norm_backward_supported(kind, B, HW, C):
+    """True where dsmil_norm_bwd takes the shape.  No device."""
+    return _native.lib().dsmil_norm_bwd_workspace_bytes(NORM_BWD_KINDS[kind], B, HW, C) > 0
+
+
+def norm_backward(kind, g, y, stats, out=None, down=None, ws=None):
+    """dsmil_norm_bwd on fp32 maps [B,...,C] (NHWC) with ``stats`` = (mean, rstd) [B,C] of the raw conv output ``y``:
+    "relu"      g = the gradient of relu(IN(y))                     -> gy
+    "add"       g = the gradient of ``out`` = relu(IN(y) + idn)      -> (gy, gres), gres the gradient of idn
+    "add_down"  g = the gradient of ``out`` = relu(IN(y) + IN(yd)), ``down`` = (yd, (md, rd))   -> (gy, gyd)
+    ``ws``: a caller's workspace (uint8, any contents); default a fresh one.  No host sync."""
+    k = NORM_BWD_KINDS[kind]
+    g, y = _f32c(g, "g"), _f32c(y, "y")
+    if g.shape != y.shape or y.dim() < 2:
+        raise ValueError("g must have y's shape [B, ..., C]")
+    B, C = y.shape[0], y.shape[-1]
+    HW = y.numel() // max(B * C, 1)
+    m, r = (_f32c(t, "stats") for t in stats)
+    if (out is None) != (kind == "relu") or (down is None) != (kind != "add_down"):
+        raise ValueError(f'kind "{kind}": out is given for "add" and "add_down" only, down for "add_down" only')
+    o = yd = md = rd = gyd = gres = None
+    if out is not None:
+        o = _f32c(out, "out")
+    if down is not None:
+        yd = _f32c(down[0], "down")
+        md, rd = (_f32c(t, "down stats") for t in down[1])
+    for t, name in ((o, "out"), (yd, "down")):
+        if t is not None and t.shape != y.shape:
+            raise ValueError(f"{name} must have y's shape")
+    for t in (m, r, md, rd):
+        if t is not None and tuple(t.shape) != (B, C):
+            raise ValueError("statistics must be [B, C]")
+    L = _native.lib()
+    need = L.dsmil_norm_bwd_workspace_bytes(k, B, HW, C)
+    if need == 0:
+        _nb_check(L.dsmil_norm_bwd_plan(k, B, HW, C, (ctypes.c_int32 * 16)()), "dsmil_norm_bwd")
+    ws = _cb_scratch(y.device, need, ws)
+    gy = torch.empty_like(y)
+    if kind == "add":
+        gres = torch.empty_like(y)
+    elif kind == "add_down":
+        gyd = torch.empty_like(y)
+    with torch.cuda.device(y.device):
+        rc = L.dsmil_norm_bwd(k, _ptr(g), _ptr(o), _ptr(y), _ptr(m), _ptr(r), _ptr(yd), _ptr(md), _ptr(rd), _ptr(gy), _ptr(gyd),
+                              _ptr(gres), B, HW, C, _ptr(ws), ws.numel(), _stream(y.device))
+    _nb_check(rc, "dsmil_norm_bwd")
+    return gy if kind == "relu" else (gy, gres) if kind == "add" else (gy, gyd)
+
+
+# ---------------------------------------------------------------------------------------------
 # background filters of the tilers (deepzoom_tiler.py:56-61, test_crop_single.py:17-24)
 # ---------------------------------------------------------------------------------------------
 def tile_stats(tiles):

@@ -13,7 +13,7 @@ the cosine form by dR_a = (dR^_a - R^_a (R^_a . dR^_a)) / |R_a|.  Contiguous fp3
 row blocks, so no path forms more than a [block, M] slab."""
 import torch
 
-from . import ops
+from . import ops, resnet
 
 _CHUNK = 1024      # rows per slab of the composite path
 
@@ -318,6 +318,163 @@ def use_native_convs(model):
             new = NativeConv2d(m.in_channels, m.out_channels, m.kernel_size, m.stride, m.padding, m.dilation, m.groups, False,
                                m.padding_mode, device="meta")
             new.weight = m.weight
+            new.train(m.training)
+            setattr(parent, name, new)
+            swapped += 1
+    return swapped
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# training the embedder: a whole BasicBlock on the native path.  The forward is composed from the fp32-class trunk's stage entries
+# (ops.trunk32_conv: raw map + fused statistics, the next conv stages relu(IN(.)) itself; ops.trunk32_tail), the backward from
+# ops.norm_backward (csrc/norm_bwd.hip) and the conv backward entries.  No normalised copy of a map is ever stored.  OPT-IN.
+# ---------------------------------------------------------------------------------------------------------------------------
+class _BasicBlockNative(torch.autograd.Function):
+    """out = relu(IN(conv2(relu(IN(conv1(x))))) + (x | IN(convd(x)))) on NHWC fp32 maps; ``wd`` is None for an identity block."""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2, wd, stride):
+        y1, m1, r1 = ops.trunk32_conv(x, w1, stride, 1)
+        y2, m2, r2 = ops.trunk32_conv(y1, w2, 1, 1, in_stats=(m1, r1))
+        if wd is None:
+            yd = md = rd = None
+            out = ops.trunk32_tail("identity", y2, (m2, r2), x)
+        else:
+            yd, md, rd = ops.trunk32_conv(x, wd, stride, 0)
+            out = ops.trunk32_tail("down", y2, (m2, r2), yd, (md, rd))
+        ctx.save_for_backward(x, w1, w2, wd, y1, m1, r1, y2, m2, r2, out, yd, md, rd)
+        ctx.stride = stride
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, w1, w2, wd, y1, m1, r1, y2, m2, r2, out, yd, md, rd = ctx.saved_tensors
+        need_x, need_w1, need_w2, need_wd = ctx.needs_input_grad[:4]
+        stride = ctx.stride
+        H, W = x.shape[1], x.shape[2]
+        g = g.contiguous()
+        if wd is None:
+            gy2, gres = ops.norm_backward("add", g, y2, (m2, r2), out=out)
+        else:
+            gy2, gyd = ops.norm_backward("add_down", g, y2, (m2, r2), out=out, down=(yd, (md, rd)))
+        dx = dw1 = dw2 = dwd = None
+        if need_w2:
+            dw2 = ops.conv_backward_weight(y1, gy2, 3, 1, 1, in_stats=(m1, r1))
+        if need_x or need_w1:
+            ga = ops.conv_backward_data(gy2, w2, y1.shape[1], y1.shape[2], 1, 1)
+            gy1 = ops.norm_backward("relu", ga, y1, (m1, r1))
+            if need_w1:
+                dw1 = ops.conv_backward_weight(x, gy1, 3, stride, 1)
+            if need_x:
+                dx = ops.conv_backward_data(gy1, w1, H, W, stride, 1)
+                dx.add_(gres if wd is None else ops.conv_backward_data(gyd, wd, H, W, stride, 0))
+        if wd is not None and need_wd:
+            dwd = ops.conv_backward_weight(x, gyd, 1, stride, 0)
+        return dx, dw1, dw2, dwd, None
+
+
+def _block_parts(blk):
+    """(stride, downsample conv or None) of a BasicBlock whose modules are the stock ones with plain InstanceNorm, else None."""
+    try:
+        stride = _same2(blk.conv1.stride)
+        if stride not in (1, 2) or not resnet._conv_is(blk.conv1, 3, stride, 1) or not resnet._conv_is(blk.conv2, 3, 1, 1):
+            return None
+        if not (resnet._is_plain_instance_norm(blk.bn1) and resnet._is_plain_instance_norm(blk.bn2)):
+            return None
+        if not isinstance(blk.relu, torch.nn.ReLU) or blk.conv2.in_channels != blk.conv1.out_channels:
+            return None
+        down = blk.downsample
+        if down is None:
+            return (stride, None) if stride == 1 and blk.conv1.in_channels == blk.conv2.out_channels else None
+        if len(down) != 2 or not resnet._conv_is(down[0], 1, stride, 0) or not resnet._is_plain_instance_norm(down[1]):
+            return None
+        if down[0].in_channels != blk.conv1.in_channels or down[0].out_channels != blk.conv2.out_channels:
+            return None
+        return stride, down[0]
+    except (AttributeError, TypeError):
+        return None
+
+
+class NativeBasicBlock(resnet.BasicBlock):
+    """resnet.BasicBlock (same submodules, same state-dict keys) that trains on the native path.
+
+    On a 4-d fp32 CUDA input, with plain InstanceNorm behind both convs (and behind the downsample conv), the stock bias-free
+    3x3 / 1x1 convs and a shape every entry involved takes (dsmil_trunk32_conv, the conv backward for every gradient that will
+    be asked for, dsmil_norm_bwd), the forward is ``_BasicBlockNative``: a ``channels_last`` input is read as NHWC without a
+    copy, the output is the NCHW view of the NHWC result, so a chain of blocks copies nothing between them.  Everything else —
+    the CPU, other dtypes, BatchNorm, a refused shape — is ``BasicBlock.forward`` unchanged."""
+
+    def _native_plan(self, x):
+        if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32):
+            return None
+        parts = _block_parts(self)
+        if parts is None:
+            return None
+        stride, dconv = parts
+        ws = [self.conv1.weight, self.conv2.weight] + ([dconv.weight] if dconv is not None else [])
+        if not all(w.is_cuda and w.dtype == torch.float32 and w.device == x.device and w.is_contiguous() for w in ws):
+            return None
+        B, Cin, H, W = x.shape
+        P = self.conv1.out_channels
+        if Cin != self.conv1.in_channels or min(B, H, W) < 1:
+            return None
+        Ho, Wo = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
+        convs = [(Cin, P, 3, stride, 1, B, H, W), (P, P, 3, 1, 1, B, Ho, Wo)]
+        if dconv is not None:
+            convs.append((Cin, P, 1, stride, 0, B, H, W))
+        L = ops._native.lib()
+        if not all(L.dsmil_trunk32_conv_workspace_bytes(*c, 0) > 0 for c in convs):
+            return None
+        if not ops.norm_backward_supported("relu", B, Ho * Wo, P):          # the tail's condition on C too; "add_down" alike
+            return None
+        if torch.is_grad_enabled():
+            want_x = x.requires_grad
+            want_w = [w.requires_grad for w in ws]
+            data = [want_x, want_x or want_w[0], want_x]                      # conv2's data gradient feeds conv1's weight
+            for c, w_w, w_d in zip(convs, want_w, data):
+                if w_w and not ops.conv_backward_supported(*c, "weight"):
+                    return None
+                if w_d and not ops.conv_backward_supported(*c, "data"):
+                    return None
+        return stride, dconv
+
+    def forward(self, x):
+        plan = self._native_plan(x)
+        if plan is None:
+            return super().forward(x)
+        stride, dconv = plan
+        xp = x.permute(0, 2, 3, 1)
+        if not xp.is_contiguous():
+            xp = xp.contiguous()
+        out = _BasicBlockNative.apply(xp, self.conv1.weight, self.conv2.weight, dconv.weight if dconv is not None else None, stride)
+        return out.permute(0, 3, 1, 2)
+
+
+def native_block_eligible(m):
+    """True for a plain resnet.BasicBlock whose modules and widths the native block path takes at some input size."""
+    if not isinstance(m, resnet.BasicBlock) or isinstance(m, NativeBasicBlock) or _block_parts(m) is None:
+        return False
+    return m.conv1.in_channels % 16 == 0 and m.conv1.out_channels % 64 == 0 and m.conv1.out_channels <= 2048
+
+
+def use_native_blocks(model):
+    """Swaps every eligible ``BasicBlock`` of ``model`` (in place) for a ``NativeBasicBlock`` holding the SAME submodules (hence
+    the same Parameter objects, submodule names and state_dict() keys and values), and returns how many it swapped.
+    resnet18_in_convs / modules.resnet_convs_of and IClassifier's native inference route are unaffected; it composes with
+    ``use_native_convs`` in either order (which then still covers the stem)."""
+    swapped = 0
+    for parent in list(model.modules()):
+        for name, m in list(parent.named_children()):
+            if not native_block_eligible(m):
+                continue
+            new = NativeBasicBlock.__new__(NativeBasicBlock)
+            torch.nn.Module.__init__(new)
+            for child, sub in m._modules.items():                  # registration order: conv1, bn1, relu, conv2, bn2, downsample
+                new.register_module(child, sub)
+            if m.downsample is None:                               # a None set in __init__ is a plain attribute, not a child
+                new.downsample = None
+            new.stride = m.stride
             new.train(m.training)
             setattr(parent, name, new)
             swapped += 1

@@ -982,6 +982,54 @@ int dsmil_conv_bwd_weight(const float* x, const float* in_mean, const float* in_
 int dsmil_conv_bwd_data(const float* dy, const float* w_oihw, float* dx, int32_t B, int32_t H, int32_t W, int32_t Cin,
                         int32_t Cout, int32_t ks, int32_t stride, int32_t pad, void* ws, size_t ws_bytes, void* stream);
 
+/* InstanceNorm / ReLU / residual-add backward for training the embedder (csrc/norm_bwd.hip): the gradient of a RAW conv output
+ * from the gradient of what the forward made of it, in the layout of dsmil_trunk32_conv / dsmil_trunk32_tail — fp32 NHWC maps
+ * [B,HW,C], statistics [B,C] fp32 (biased variance, no affine).  For a map t with statistics (m, r), x^ = (t - m) r and a masked
+ * upstream gradient q:
+ *     INB(q; t, m, r)[n,p,c] = r[n,c] ( q[n,p,c] - mean_p q[n,.,c] - x^[n,p,c] mean_p (q x^)[n,.,c] )
+ *   DSMIL_NORM_BWD_RELU      g = the gradient of a = relu((y - mean) rstd), the operand dsmil_trunk32_conv stages and
+ *                            dsmil_conv_bwd_data differentiates against.  q = g where fl(fl(y - mean) rstd) > 0 (the forward's own
+ *                            fp32 evaluation), else 0;  gy = INB(q; y, mean, rstd).  out, yd, md, rd, gyd, gres are NULL.
+ *   DSMIL_NORM_BWD_ADD       g = the gradient of out = relu((y - mean) rstd + idn) (dsmil_trunk32_tail kind 0).  q = g where the
+ *                            saved out > 0, else 0;  gy = INB(q; y, mean, rstd);  gres = q, the gradient of idn.  yd, md, rd, gyd
+ *                            are NULL.
+ *   DSMIL_NORM_BWD_ADD_DOWN  as ADD for tail kind 1: gy as above and gyd = INB(q; yd, md, rd); g and out are read once for both
+ *                            branches.  gres is NULL.
+ *   ws       device, 256-byte aligned, dsmil_norm_bwd_workspace_bytes(kind, B, HW, C) bytes, any contents
+ * Arithmetic, all fp32: x^ = fl(fl(t - m) r); the sums of q and of q x^ (fmaf) per (n, c); mean = sum / HW (a correctly rounded
+ * division); gy = fl(r fmaf(-x^, mean(q x^), fl(q - mean q))).
+ * Order.  The HW pixels of an image are dealt to chunks of plan[CHUNK]; inside a chunk plan[LANES] threads per channel each add
+ * every LANES-th pixel serially (at most plan[RUN_LEN] terms per accumulator), their LANES sums are combined in a fixed tree
+ * (xor shuffles inside a wave, then the waves through LDS in wave order) into one fp32 partial in ws; the plan[PARTIALS] partials
+ * of an (n, c) are added in chunk order; the element pass then runs.  No atomics anywhere: two calls on the same inputs are
+ * bit-identical, and a call never reads what another call left in ws.  HW = 1 (with mean = y), a channel whose every element is
+ * masked and an all-zero g give exact zeros.
+ * Checks, all before the first launch, in this order: DSMIL_E_INVALID (unknown kind; non-positive sizes; a NULL pointer the
+ * kind needs, or one given that the kind forbids; an output sharing a byte with an input or with another output);
+ * DSMIL_E_UNSUPPORTED (C % 4 != 0, C / 4 neither dividing 256 nor a multiple of it, C > 2048, B HW C >= 2^31; the size function
+ * returns 0); DSMIL_E_ALIGN (maps or statistics off 16 bytes, ws off 256); DSMIL_E_WORKSPACE (a short workspace).  Asynchronous
+ * on `stream`; nothing is allocated.  dsmil_norm_bwd_plan is a HOST function: out[DSMIL_NORM_BWD_PLAN_*], the rest 0.
+ * Added without a change of DSMIL_ABI_VERSION (it stays 6, no existing signature moved): a caller finds them by symbol. */
+enum { DSMIL_NORM_BWD_RELU = 0, DSMIL_NORM_BWD_ADD = 1, DSMIL_NORM_BWD_ADD_DOWN = 2 };
+enum {
+    DSMIL_NORM_BWD_PLAN_KIND = 0,
+    DSMIL_NORM_BWD_PLAN_CHUNK = 1,         /* pixels per chunk */
+    DSMIL_NORM_BWD_PLAN_PARTIALS = 2,      /* partials per (n, c) and sum: ceil(HW / chunk) */
+    DSMIL_NORM_BWD_PLAN_RUN_LEN = 3,       /* the longest serial run of terms one accumulator adds: ceil(min(HW, chunk) / lanes) */
+    DSMIL_NORM_BWD_PLAN_LANES = 4,         /* accumulators per channel and chunk, combined in a fixed tree: 256 / min(C / 4, 256) */
+    DSMIL_NORM_BWD_PLAN_SUMS = 5,          /* sums per (n, c): 2, ADD_DOWN 3 */
+    DSMIL_NORM_BWD_PLAN_GRID_PARTIAL = 6,  /* workgroups of the chunk sums: B * partials */
+    DSMIL_NORM_BWD_PLAN_GRID_FINISH = 7,   /* of the pass that adds the partials */
+    DSMIL_NORM_BWD_PLAN_GRID_APPLY = 8,    /* of the element pass: 8192 at most, grid stride beyond */
+    DSMIL_NORM_BWD_PLAN_BLOCK = 9,         /* threads per workgroup of every launch */
+    DSMIL_NORM_BWD_PLAN_GROUPS = 10        /* 4-channel groups per thread: 1, or 2 at C = 2048 */
+};
+int dsmil_norm_bwd_plan(int32_t kind, int32_t B, int32_t HW, int32_t C, int32_t out[16]);
+size_t dsmil_norm_bwd_workspace_bytes(int32_t kind, int32_t B, int32_t HW, int32_t C);
+int dsmil_norm_bwd(int32_t kind, const float* g, const float* out, const float* y, const float* mean, const float* rstd,
+                   const float* yd, const float* md, const float* rd, float* gy, float* gyd, float* gres, int32_t B, int32_t HW,
+                   int32_t C, void* ws, size_t ws_bytes, void* stream);
+
 /* Measurement hooks (bench.py's roofline leg; no reference counterpart).  While enabled, every
  * launch of a dominant kernel is bracketed by hipEventRecord on its own launch stream (up to 4096
  * launches per channel: 0 = k_query_attend of the aggregator, 1 = k_conv of the embedder);
