@@ -18,8 +18,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dsmil_hip.h"
+#include "emb_host.h"
 
 namespace {
+using namespace emb;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -354,8 +356,6 @@ __global__ __launch_bounds__(256) void k_conv_dgrad(DgArgs a) {
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
-inline size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 struct CbPlan {
     int which, Ho, Wo, Kc, colpad, chunk, nchunks, run_len, gmax, tile0[5];
     long long M, n_dy;
@@ -368,18 +368,16 @@ int cb_check(int Cin, int Cout, int ks, int stride, int pad, int B, int H, int W
     if (which != DSMIL_CONV_BWD_WEIGHT && which != DSMIL_CONV_BWD_DATA) return DSMIL_E_INVALID;
     if (!(Cin % 16 == 0 || (Cin == 3 && which == DSMIL_CONV_BWD_WEIGHT)) || Cout % 64 != 0) return DSMIL_E_UNSUPPORTED;
     if ((ks != 1 && ks != 3 && ks != 7) || (stride != 1 && stride != 2) || pad > ks / 2) return DSMIL_E_UNSUPPORTED;
-    if (H + 2 * pad < ks || W + 2 * pad < ks) return DSMIL_E_UNSUPPORTED;
-    const long long Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1, lim = 0x7fffffffLL;
-    if ((long long)B * H * W * Cin >= lim || (long long)B * Ho * Wo * Cout >= lim || (long long)Cout * Cin * ks * ks >= lim)
-        return DSMIL_E_UNSUPPORTED;
-    return DSMIL_OK;
+    ConvMap m;
+    if (!conv_map(B, H, W, Cin, Cout, ks, stride, pad, m)) return DSMIL_E_UNSUPPORTED;
+    return map_fits(Cout, Cin, ks, ks) ? DSMIL_OK : DSMIL_E_UNSUPPORTED;   // the OIHW weights: the finish and pack kernels' index
 }
 
 // the shape has passed cb_check.  false: the partials would not fit an int (refused as unsupported)
 bool cb_plan(int Cin, int Cout, int ks, int stride, int pad, int B, int H, int W, int which, CbPlan& p) {
     p.which = which;
-    p.Ho = (H + 2 * pad - ks) / stride + 1;
-    p.Wo = (W + 2 * pad - ks) / stride + 1;
+    p.Ho = outdim(H, ks, stride, pad);
+    p.Wo = outdim(W, ks, stride, pad);
     p.n_dy = (long long)B * p.Ho * p.Wo * Cout;
     p.gmax = (int)((p.n_dy / 4 + 255) / 256 < CB_MAXBLOCKS ? (p.n_dy / 4 + 255) / 256 : CB_MAXBLOCKS);
     p.off_sc = 0;
@@ -420,8 +418,6 @@ bool cb_plan(int Cin, int Cout, int ks, int stride, int pad, int B, int H, int W
     p.total = p.off_main + al256(main_bytes);
     return true;
 }
-
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 void cb_scale(const float* dy, const CbPlan& p, char* ws, hipStream_t st) {
     float* pmax = (float*)(ws + p.off_pmax);
@@ -473,7 +469,7 @@ int dsmil_conv_bwd_weight(const float* x, const float* in_mean, const float* in_
     if (!cb_plan(Cin, Cout, ks, stride, pad, B, H, W, DSMIL_CONV_BWD_WEIGHT, p)) return DSMIL_E_UNSUPPORTED;
     const bool vec = Cin % 4 == 0;
     if ((vec ? !al16(x) || !al16(in_mean) || !al16(in_rstd) : (((uintptr_t)x | (uintptr_t)in_mean | (uintptr_t)in_rstd) & 3) != 0) ||
-        !al16(dy) || ((uintptr_t)dw_oihw & 3) || ((uintptr_t)ws & 255)) return DSMIL_E_ALIGN;
+        !al16(dy) || ((uintptr_t)dw_oihw & 3) || !al256p(ws)) return DSMIL_E_ALIGN;
     if (ws_bytes < p.total) return DSMIL_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     char* w = (char*)ws;
@@ -499,7 +495,7 @@ int dsmil_conv_bwd_data(const float* dy, const float* w_oihw, float* dx, int32_t
     if (const int rc = cb_check(Cin, Cout, ks, stride, pad, B, H, W, DSMIL_CONV_BWD_DATA)) return rc;
     CbPlan p;
     if (!cb_plan(Cin, Cout, ks, stride, pad, B, H, W, DSMIL_CONV_BWD_DATA, p)) return DSMIL_E_UNSUPPORTED;
-    if (!al16(dy) || !al16(dx) || ((uintptr_t)w_oihw & 3) || ((uintptr_t)ws & 255)) return DSMIL_E_ALIGN;
+    if (!al16(dy) || !al16(dx) || ((uintptr_t)w_oihw & 3) || !al256p(ws)) return DSMIL_E_ALIGN;
     if (ws_bytes < p.total) return DSMIL_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     char* w = (char*)ws;

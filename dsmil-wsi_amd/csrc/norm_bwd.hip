@@ -7,24 +7,26 @@
 //   kind ADD_DOWN  as ADD, and gyd = rd (q - mean_p q - x^d mean_p (q x^d)) for the raw downsample branch yd
 // Three launches, memory-bound, no MFMA, no atomics, no hand-off between workgroups inside a launch:
 //   k_nb_partial   one workgroup per (image, chunk of pixels): sum q, sum q x^ (and sum q x^d) per channel over the chunk.  The
-//                  thread layout is k_norm_add_relu's (resnet_fwd.hip): C / 4 channel groups across the threads, 16-byte loads,
-//                  256 / (C / 4) pixel lanes; a thread adds its pixels serially (fmaf for the products), the pixel lanes of a wave
-//                  are combined by xor shuffles (widest stride last), the waves through LDS in wave order -> ws partials
+//                  thread layout is emb::chan_layout (emb_host.h, the forward tail's too): C / 4 channel groups across the threads,
+//                  16-byte loads, 256 / (C / 4) pixel lanes; a thread adds its pixels serially (fmaf for the products), the pixel
+//                  lanes of a wave are combined by xor shuffles (widest stride last), the waves through LDS in wave order -> ws
+//                  partials
 //   k_nb_finish    one thread per (sum, image, channel): the partials in chunk order, divided by HW -> ws coefficients
-//   k_nb_apply     the element pass, k_norm_add_relu's grid (8192 workgroups at most, grid stride beyond, a thread keeps its
-//                  channel group, 32-bit indices)
+//   k_nb_apply     the element pass on emb::chan_grid, the forward tail's grid (a cap on the workgroups, a grid stride beyond, a
+//                  thread keeps its channel group, 32-bit indices)
 // Every output element has one writer and every sum a fixed order: two calls on the same inputs are bit-identical, and a call
 // reads nothing from ws that it has not written itself.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dsmil_hip.h"
+#include "emb_host.h"
 
 namespace {
+using namespace emb;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int NB_CHUNK0 = 256, NB_CHUNK_MAX = 4096, NB_WG_TARGET = 2048;   // pixels per chunk: doubled while B chunks > target
-constexpr int NB_APPLY_MAX = 8192;                                         // k_norm_add_relu's cap
 
 struct NbArgs {
     const float *g, *out, *y, *mean, *rstd, *yd, *md, *rd;
@@ -47,6 +49,8 @@ template <int KIND>
 __global__ __launch_bounds__(256) void k_nb_partial(const NbArgs a) {
     constexpr int NS = KIND == DSMIL_NORM_BWD_ADD_DOWN ? 3 : 2;
     __shared__ f32x4 red[NS][256];
+    // emb::chan_layout(C), written out: taking it from the struct changes this kernel's instruction stream (k_nb_apply's and
+    // k_norm_add_relu's it leaves alone), and the refactor that introduced emb_host.h was to change no device code
     const int C = a.C, c4n = C / 4;
     const int lanes_c = c4n < 256 ? c4n : 256;              // threads across the channel groups of one pixel
     const int cpt = (c4n + 255) / 256;                      // channel groups per thread (2 at C = 2048)
@@ -130,10 +134,9 @@ __global__ __launch_bounds__(256) void k_nb_finish(const float* __restrict__ par
 template <int KIND>
 __global__ __launch_bounds__(256) void k_nb_apply(const NbArgs a) {
     constexpr bool DOWN = KIND == DSMIL_NORM_BWD_ADD_DOWN;
-    const int C = a.C, c4n = C / 4;
-    const int lanes_c = c4n < 256 ? c4n : 256;
-    const int cpt = (c4n + 255) / 256;
-    const int tpb = 256 / lanes_c;
+    const int C = a.C;
+    const ChanLayout cl = chan_layout(C);
+    const int lanes_c = cl.lanes_c, cpt = cl.cpt, tpb = cl.tpb;
     const int c40 = threadIdx.x % lanes_c, pl = threadIdx.x / lanes_c;
     const unsigned np = (unsigned)a.B * (unsigned)a.HW, pstep = gridDim.x * (unsigned)tpb, bc = (unsigned)a.B * C;
     int ncur = -1;
@@ -179,9 +182,6 @@ __global__ __launch_bounds__(256) void k_nb_apply(const NbArgs a) {
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
-inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 struct NbPlan {
     int nsums, chunk, nparts, run_len, lanes, cpt, grid_partial, grid_finish, grid_apply;
     size_t off_coef, total;
@@ -190,17 +190,17 @@ struct NbPlan {
 int nb_check(int kind, int B, int HW, int C) {
     if (B < 1 || HW < 1 || C < 1) return DSMIL_E_INVALID;
     if (kind != DSMIL_NORM_BWD_RELU && kind != DSMIL_NORM_BWD_ADD && kind != DSMIL_NORM_BWD_ADD_DOWN) return DSMIL_E_INVALID;
-    if (C % 4 != 0 || C > 2048 || (C / 4 < 256 ? 256 % (C / 4) != 0 : (C / 4) % 256 != 0)) return DSMIL_E_UNSUPPORTED;
-    if ((long long)B * HW >= 0x7fffffffLL || (long long)B * HW * C >= 0x7fffffffLL) return DSMIL_E_UNSUPPORTED;
+    if (!chan_ok(C) || C > 2048) return DSMIL_E_UNSUPPORTED;     // the layout the forward tail takes too; C <= 2048 is this entry's own limit
+    if (!map_fits(B, HW, 1, C)) return DSMIL_E_UNSUPPORTED;
     return DSMIL_OK;
 }
 
 // the shape has passed nb_check.  false: the partials would not fit a 32-bit index (refused as unsupported)
 bool nb_plan(int kind, int B, int HW, int C, NbPlan& p) {
     p.nsums = kind == DSMIL_NORM_BWD_ADD_DOWN ? 3 : 2;
-    const int c4n = C / 4, lanes_c = c4n < 256 ? c4n : 256;
-    p.lanes = 256 / lanes_c;
-    p.cpt = (c4n + 255) / 256;
+    const ChanLayout cl = chan_layout(C);
+    p.lanes = cl.tpb;
+    p.cpt = cl.cpt;
     p.chunk = NB_CHUNK0;
     auto nch = [&](int c) { return (long long)(HW + c - 1) / c; };
     while (nch(p.chunk) * B > NB_WG_TARGET && p.chunk < NB_CHUNK_MAX) p.chunk *= 2;
@@ -211,17 +211,10 @@ bool nb_plan(int kind, int B, int HW, int C, NbPlan& p) {
     p.grid_partial = B * p.nparts;                           // <= B HW < 2^31
     const long long nfin = ((long long)p.nsums * B * C + 255) / 256;
     p.grid_finish = (int)(nfin < 4096 ? nfin : 4096);
-    const long long nap = ((long long)B * HW + p.lanes - 1) / p.lanes;
-    p.grid_apply = (int)(nap < NB_APPLY_MAX ? nap : NB_APPLY_MAX);
+    p.grid_apply = chan_grid((long long)B * HW, cl);
     p.off_coef = al256((size_t)p.nsums * B * p.nparts * C * sizeof(float));
     p.total = p.off_coef + al256((size_t)p.nsums * B * C * sizeof(float));
     return true;
-}
-
-// [p, p + bytes) and [q, q + qbytes) share a byte
-inline bool overlap(const void* p, size_t bytes, const void* q, size_t qbytes) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b ? b - a < bytes : a - b < qbytes;
 }
 
 }  // namespace
@@ -285,7 +278,7 @@ int dsmil_norm_bwd(int32_t kind, const float* g, const float* out, const float* 
     NbPlan p;
     if (!nb_plan(kind, B, HW, C, p)) return DSMIL_E_UNSUPPORTED;
     if (!al16(g) || !al16(out) || !al16(y) || !al16(mean) || !al16(rstd) || !al16(yd) || !al16(md) || !al16(rd) || !al16(gy) ||
-        !al16(gyd) || !al16(gres) || ((uintptr_t)ws & 255)) return DSMIL_E_ALIGN;
+        !al16(gyd) || !al16(gres) || !al256p(ws)) return DSMIL_E_ALIGN;
     if (ws_bytes < p.total) return DSMIL_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     float* part = (float*)ws;

@@ -634,8 +634,8 @@ template <bool F16>
 inline int run_conv(hipStream_t st, const unsigned short* in, const unsigned short* wpk, unsigned short* out, int B, int Hi, int Wi, const ConvSpec& s, int* Ho_, int* Wo_) {
     ConvGeo g;
     g.B = B; g.Hi = Hi; g.Wi = Wi; g.Cin = s.cin; g.Cout = s.cout; g.ks = s.ks; g.stride = s.stride;
-    g.Ho = (Hi + 2 * s.pad - s.ks) / s.stride + 1;
-    g.Wo = (Wi + 2 * s.pad - s.ks) / s.stride + 1;
+    g.Ho = outdim(Hi, s.ks, s.stride, s.pad);
+    g.Wo = outdim(Wi, s.ks, s.stride, s.pad);
     g.cin_c = chunk_for(s);
     g.M = npos(B, g.Ho, g.Wo);
     g.Mint = (long long)B * (g.Ho + 1) * (g.Wo + 1);

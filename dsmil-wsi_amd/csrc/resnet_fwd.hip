@@ -37,6 +37,7 @@
 #include "dsmil_hip.h"
 #include "prof.h"
 #include "lds_attr.h"
+#include "emb_host.h"
 
 namespace {
 
@@ -1931,10 +1932,8 @@ __global__ __launch_bounds__(256) void k_norm_add_relu(const float* __restrict__
                                                        const float* __restrict__ r2, const float* __restrict__ idn,
                                                        const float* __restrict__ md, const float* __restrict__ rd,
                                                        float* __restrict__ out, long long npix, int HW, int C) {
-    const int c4n = C / 4;
-    const int lanes_c = c4n < 256 ? c4n : 256;              // threads across the channel groups of one pixel
-    const int cpt = (c4n + 255) / 256;                      // channel groups per thread (2 only for the 2048-wide Bottleneck tail)
-    const int tpb = 256 / lanes_c;                          // pixels per workgroup per iteration
+    const emb::ChanLayout cl = emb::chan_layout(C);         // (emb_host.h; cpt = 2 only for the 2048-wide Bottleneck tail)
+    const int lanes_c = cl.lanes_c, cpt = cl.cpt, tpb = cl.tpb;
     const int c40 = threadIdx.x % lanes_c, pl = threadIdx.x / lanes_c;
     const unsigned np = (unsigned)npix, pstep = gridDim.x * (unsigned)tpb;
     int ncur = -1;
@@ -2051,7 +2050,7 @@ const Arch* arch_of(int depth) {
     return depth == 18 ? &a18 : depth == 34 ? &a34 : depth == 50 ? &a50 : depth == 101 ? &a101 : nullptr;
 }
 
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+using namespace emb;   // al256, al16, outdim, conv_map, chan_layout ...: the shape rules shared with conv_bwd.hip / norm_bwd.hip
 
 // hipFuncAttributeMaxDynamicSharedMemorySize once per (device, kernel), not once per launch (lds_attr.h: the attribute
 // applies to the current device only, so a process that drives several GPUs must set it on each)
@@ -2128,7 +2127,6 @@ inline unsigned long long* wino_trace_buffer() {
     return buf;
 }
 #endif
-inline int outdim(int x, int ks, int s, int p) { return (x + 2 * p - ks) / s + 1; }
 
 struct Dims { int H1, W1, Hp, Wp, h[5], w[5]; };
 Dims dims_for(int H, int W) {
@@ -2319,6 +2317,12 @@ struct RWs {
     size_t y0, buf[5], stat[4][2], part, total;  // stat[k] = {mean, rstd}
     long long act_elems, part_elems;
 };
+// the stem's statistics partials, (cnt, mean, M2) per (image, tile, wave, channel): 8 x 16-pixel tiles x 4 waves (k_stem) or
+// 16 x 16 x 8 waves (k_stem_s6), whichever is more
+long long stem_part_elems(int B, const Dims& d) {
+    const long long stem_rows = std::max<long long>(((d.H1 + 7) / 8) * 4, ((d.H1 + SS_TR - 1) / SS_TR) * 8);
+    return (long long)B * stem_rows * ((d.W1 + 15) / 16) * 64 * 3;
+}
 RWs rws_layout(int B, int H, int W, int depth = 18) {
     const Dims d = dims_for(H, W);
     const Arch& A = *arch_of(depth);
@@ -2335,9 +2339,7 @@ RWs rws_layout(int B, int H, int W, int depth = 18) {
     // cache it) and must not depend on the form or the experiment knobs of a call, so this sizes per LAYER for every kind of
     // conv a form could run there — both Winograd unit shapes, a direct conv at the layer's full width — rather than asking the
     // plans of one form; the forward checks each plan against it.
-    // stem: per (image, tile, wave): 8 x 16-pixel tiles x 4 waves (k_stem) or 16 x 16 x 8 waves (k_stem_s6), whichever is more
-    const long long stem_rows = std::max<long long>(((d.H1 + 7) / 8) * 4, ((d.H1 + SS_TR - 1) / SS_TR) * 8);
-    long long mx = (long long)B * stem_rows * ((d.W1 + 15) / 16) * 64 * 3;
+    long long mx = stem_part_elems(B, d);
     for (int l = 1; l <= 4; ++l) {
         const int Cw = 64 << (l - 1);
         // direct convs of layer l: outputs at this layer's resolution (up to Cw*exp channels) and, for a Bottleneck's
@@ -2542,8 +2544,8 @@ int finish_stem(hipStream_t st, const StemPlan& sp, const float* bn_m, const flo
 }
 
 // the elementwise pass that closes a block: relu(IN(yout) + identity | IN(yd)) over npix = B * HW pixels of C channels, or — the
-// last block — the same averaged over the pixels into the feature row.  k_norm_add_relu keeps one 4-channel group per thread and
-// grid-strides past 8192 workgroups.
+// last block — the same averaged over the pixels into the feature row.  k_norm_add_relu's threads and grid are emb::chan_layout /
+// chan_grid: one 4-channel group per thread, a grid stride past CHAN_GRID_MAX workgroups.  C has passed chan_ok.
 void launch_tail(hipStream_t st, bool last, bool down, const float* yout, const float* m, const float* r, const float* idn,
                  const float* md, const float* rd, float* out, int B, int HW, int C) {
     if (last) {
@@ -2551,9 +2553,7 @@ void launch_tail(hipStream_t st, bool last, bool down, const float* yout, const 
         return;
     }
     const long long npix = (long long)B * HW;
-    const int c4n = C / 4, tpb = 256 / (c4n < 256 ? c4n : 256);
-    long long nb = (npix + tpb - 1) / tpb;
-    if (nb > 8192) nb = 8192;
+    const int nb = chan_grid(npix, chan_layout(C));
     if (down) hipLaunchKernelGGL(k_norm_add_relu<true>, dim3((unsigned)nb), dim3(256), 0, st, yout, m, r, idn, md, rd, out, npix, HW, C);
     else hipLaunchKernelGGL(k_norm_add_relu<false>, dim3((unsigned)nb), dim3(256), 0, st, yout, m, r, idn, nullptr, nullptr, out, npix, HW, C);
 }
@@ -2730,8 +2730,6 @@ int dsmil_resnet_forward_ex(int32_t depth, const void* x, int32_t x_is_u8_nhwc, 
 // pack_all make them — behind argument checks that all run before the first launch: no kernel, geometry or plan of its own.
 // kind as Form::trunk: 1 = bf16, 2 = fp16.
 namespace {
-inline bool t16_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline bool t16_al256(const void* p) { return ((uintptr_t)p & 255) == 0; }
 inline bool t16_kind(int kind) { return kind == 1 || kind == 2; }
 inline bool t16_pos(int B, int H, int W, int C) { return B >= 1 && H >= 1 && W >= 1 && C >= 1; }
 // a map every kernel of the trunk can index: eight channels per 16-B piece, images on gridDim.y, element offsets inside an int
@@ -2764,7 +2762,7 @@ int dsmil_trunk16_layout(const float* x_nhwc, void* out16, int32_t B, int32_t H,
                          int32_t borders_only, void* stream) {
     if (!out16 || (!borders_only && !x_nhwc) || !t16_pos(B, H, W, C) || !t16_kind(kind)) return DSMIL_E_INVALID;
     if (!t16_map(B, H, W, C)) return DSMIL_E_UNSUPPORTED;
-    if (!t16_al16(out16) || !t16_al16(x_nhwc)) return DSMIL_E_ALIGN;
+    if (!al16(out16) || !al16(x_nhwc)) return DSMIL_E_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     unsigned short* out = (unsigned short*)out16;
     const int oc = C / 8;
@@ -2792,11 +2790,11 @@ int dsmil_trunk16_conv(const void* in16, const float* w_oihw, void* out16, int32
     if (!in16 || !w_oihw || !out16 || !ws || in16 == out16 || !t16_pos(B, Hi, Wi, Cin) || Cout < 1 || ks < 1 || stride < 1 || pad < 0 ||
         !t16_kind(kind)) return DSMIL_E_INVALID;
     const ConvSpec s{Cout, Cin, ks, stride, pad};
-    if (Hi > 32767 || Wi > 32767 || Hi + 2 * pad < ks || Wi + 2 * pad < ks) return DSMIL_E_UNSUPPORTED;
-    const int Ho = (Hi + 2 * pad - ks) / stride + 1, Wo = (Wi + 2 * pad - ks) / stride + 1;
-    if (!t16_map(B, Hi, Wi, Cin) || !t16_map(B, Ho, Wo, Cout)) return DSMIL_E_UNSUPPORTED;
-    if (const int rc = t16_conv_check(s, Wo)) return rc;
-    if (!t16_al16(in16) || !t16_al16(out16) || ((uintptr_t)w_oihw & 3) || !t16_al256(ws)) return DSMIL_E_ALIGN;
+    ConvMap m;
+    if (Hi > 32767 || Wi > 32767 || !conv_map(B, Hi, Wi, Cin, Cout, ks, stride, pad, m)) return DSMIL_E_UNSUPPORTED;
+    if (!t16_map(B, Hi, Wi, Cin) || !t16_map(B, m.Ho, m.Wo, Cout)) return DSMIL_E_UNSUPPORTED;   // (the shared-border layout's limits)
+    if (const int rc = t16_conv_check(s, m.Wo)) return rc;
+    if (!al16(in16) || !al16(out16) || ((uintptr_t)w_oihw & 3) || !al256p(ws)) return DSMIL_E_ALIGN;
     if (ws_bytes < dsmil_trunk16_conv_workspace_bytes(Cin, Cout, ks)) return DSMIL_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     unsigned short* wpk = (unsigned short*)ws;
@@ -2815,7 +2813,7 @@ int dsmil_trunk16_norm(const void* x16, const void* idn16, void* y16, int32_t B,
     if (!x16 || !y16 || !ws || !t16_pos(B, H, W, C) || !t16_kind(kind) || (relu != 0 && relu != 1)) return DSMIL_E_INVALID;
     if (!t16_map(B, H, W, C) || !t16_norm_c(C)) return DSMIL_E_UNSUPPORTED;
     if (idn16 && !relu) return DSMIL_E_UNSUPPORTED;          // (the trunk has no residual form without the ReLU)
-    if (!t16_al16(x16) || !t16_al16(idn16) || !t16_al16(y16) || !t16_al256(ws)) return DSMIL_E_ALIGN;
+    if (!al16(x16) || !al16(idn16) || !al16(y16) || !al256p(ws)) return DSMIL_E_ALIGN;
     if (ws_bytes < t16_part_bytes(B, C)) return DSMIL_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const unsigned short* x = (const unsigned short*)x16;
@@ -2831,7 +2829,7 @@ int dsmil_trunk16_pool(const void* x16, const void* idn16, float* feats, int32_t
                        void* ws, size_t ws_bytes, void* stream) {
     if (!x16 || !idn16 || !feats || !ws || !t16_pos(B, H, W, C) || !t16_kind(kind)) return DSMIL_E_INVALID;
     if (!t16_map(B, H, W, C) || !t16_norm_c(C)) return DSMIL_E_UNSUPPORTED;
-    if (!t16_al16(x16) || !t16_al16(idn16) || ((uintptr_t)feats & 3) || !t16_al256(ws)) return DSMIL_E_ALIGN;
+    if (!al16(x16) || !al16(idn16) || ((uintptr_t)feats & 3) || !al256p(ws)) return DSMIL_E_ALIGN;
     if (ws_bytes < t16_part_bytes(B, C)) return DSMIL_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const unsigned short* x = (const unsigned short*)x16;
@@ -2864,13 +2862,13 @@ int dsmil_trunk16_forward(int32_t depth, const float* x_nhwc, int32_t B, int32_t
         for (int b = 0; b < A->nblk[l - 1]; ++b) {               // (the walk of b16::trunk_t)
             const int nc = l > 1 && b == 0 ? 3 : 2;              // conv1, conv2 and — first block of layers 2..4 — downsample.0
             const ConvSpec& s1 = A->specs[ci];
-            const int Ho = (H + 2 * s1.pad - s1.ks) / s1.stride + 1, Wo = (W + 2 * s1.pad - s1.ks) / s1.stride + 1;
+            const int Ho = outdim(H, s1.ks, s1.stride, s1.pad), Wo = outdim(W, s1.ks, s1.stride, s1.pad);
             for (int k = 0; k < nc; ++k)
                 if (const int rc = t16_conv_check(A->specs[ci + k], Wo)) return rc;
             if ((size_t)b16::npos(B, Ho, Wo) * s1.cout * 2 > b16::act_bytes(B, Hp, Wp)) return DSMIL_E_UNSUPPORTED;
             ci += nc; H = Ho; W = Wo;
         }
-    if (!t16_al16(x_nhwc) || ((uintptr_t)feats & 3) || !t16_al256(ws)) return DSMIL_E_ALIGN;
+    if (!al16(x_nhwc) || ((uintptr_t)feats & 3) || !al256p(ws)) return DSMIL_E_ALIGN;
     if (ws_bytes < dsmil_trunk16_workspace_bytes(depth, B, Hp, Wp)) return DSMIL_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     unsigned short* wpk = (unsigned short*)ws;
@@ -2878,13 +2876,14 @@ int dsmil_trunk16_forward(int32_t depth, const float* x_nhwc, int32_t B, int32_t
     return b16::trunk(st, *A, x_nhwc, wpk, (char*)ws + al256(b16::packed_bytes(*A)), B, Hp, Wp, feats, kind);
 }
 
-// ---- the stages of the fp32-class trunk (this file and wino_w1.h) ALONE, FOR TESTS (tests/test_trunk32_gpu.py compares each with
-// fp64 at a derived bar; include/dsmil_hip.h states the contracts).  Each entry is the trunk's own host call — plan_conv, pack_conv,
-// run_conv, plan_stem, pack_stem, launch_stem, finish_stem, launch_tail, exactly what pack_impl and resnet_forward_impl call —
-// behind argument checks that all run before the first launch: no kernel, geometry or plan of its own.  precision as in
-// dsmil_resnet_forward_ex: 0 = the process form (NPD: two fp16 planes, three products), 1 = one fp16 plane.
+// ---- the stages of the fp32-class trunk (this file and wino_w1.h) ALONE: tests/test_trunk32_gpu.py compares each with fp64 at a
+// derived bar, and the embedder's training forward (simclr.NativeConv2d, NativeBasicBlock) is composed from dsmil_trunk32_conv
+// and dsmil_trunk32_tail; the plan and stem entries serve tests and tools only (include/dsmil_hip.h states the contracts).  Each
+// entry is the trunk's own host call — plan_conv, pack_conv, run_conv, plan_stem, pack_stem, launch_stem, finish_stem,
+// launch_tail, exactly what pack_impl and resnet_forward_impl call — behind argument checks that all run before the first launch:
+// no kernel, geometry or plan of its own.  precision as in dsmil_resnet_forward_ex: 0 = the process form (NPD: two fp16 planes,
+// three products), 1 = one fp16 plane.
 namespace {
-inline bool t32_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline bool t32_prec(int precision) { return precision == 0 || precision == 1; }
 // the convs the kernels behind run_conv take: 16-channel chunks of the input (S6K, SK), 64-cout workgroups at the narrowest
 // (tile 42, k_conv_wino_s3), element offsets of either map inside an int (the staging offsets of the Winograd kernels), the
@@ -2892,10 +2891,8 @@ inline bool t32_prec(int precision) { return precision == 0 || precision == 1; }
 inline int t32_conv_check(const ConvSpec& s, int B, int H, int W) {
     if ((s.ks != 1 && s.ks != 3) || (s.stride != 1 && s.stride != 2) || s.pad > s.ks / 2) return DSMIL_E_UNSUPPORTED;
     if (s.cin % 16 || s.cout % 64 || s.cin > 2048 || s.cout > 2048) return DSMIL_E_UNSUPPORTED;
-    if (H > 32767 || W > 32767 || H + 2 * s.pad < s.ks || W + 2 * s.pad < s.ks) return DSMIL_E_UNSUPPORTED;
-    const long long Ho = outdim(H, s.ks, s.stride, s.pad), Wo = outdim(W, s.ks, s.stride, s.pad);
-    if ((long long)B * H * W * s.cin >= 0x7fffffffLL || (long long)B * Ho * Wo * s.cout >= 0x7fffffffLL) return DSMIL_E_UNSUPPORTED;
-    return DSMIL_OK;
+    ConvMap m;
+    return H > 32767 || W > 32767 || !conv_map(B, H, W, s.cin, s.cout, s.ks, s.stride, s.pad, m) ? DSMIL_E_UNSUPPORTED : DSMIL_OK;
 }
 struct T32ConvWs { size_t packed, part, total; };
 inline T32ConvWs t32_conv_ws(const ConvPlan& p) {
@@ -2917,13 +2914,9 @@ inline T32StemWs t32_stem_ws(int B, const Dims& d) {
     w.wimg = 0;
     w.y0 = al256((size_t)SS_WIMG * sizeof(unsigned short));
     w.part = w.y0 + al256((size_t)B * d.H1 * d.W1 * 64 * sizeof(float));
-    // (cnt, mean, M2) per (image, tile, wave, channel): the larger of k_stem's and k_stem_s6's tilings, as rws_layout sizes it
-    const long long stem_rows = std::max<long long>(((d.H1 + 7) / 8) * 4, ((d.H1 + SS_TR - 1) / SS_TR) * 8);
-    w.total = w.part + al256((size_t)((long long)B * stem_rows * ((d.W1 + 15) / 16) * 64 * 3) * sizeof(float));
+    w.total = w.part + al256((size_t)stem_part_elems(B, d) * sizeof(float));
     return w;
 }
-// k_norm_add_relu: C / 4 channel groups across the 256 threads (a divisor of 256, or a multiple of it); pixels inside an unsigned
-inline bool t32_tail_c(int C) { return C % 4 == 0 && (C / 4 < 256 ? 256 % (C / 4) == 0 : (C / 4) % 256 == 0); }
 }  // namespace
 
 int dsmil_trunk32_conv_plan(int32_t Cin, int32_t Cout, int32_t ks, int32_t stride, int32_t pad, int32_t B, int32_t H, int32_t W,
@@ -2958,8 +2951,8 @@ int dsmil_trunk32_conv(const float* x, const float* w_oihw, const float* in_mean
     if (!t32_prec(precision)) return DSMIL_E_UNSUPPORTED;
     const ConvSpec s{Cout, Cin, ks, stride, pad};
     if (const int rc = t32_conv_check(s, B, H, W)) return rc;
-    if (!t32_al16(x) || !t32_al16(y) || !t32_al16(in_mean) || !t32_al16(in_rstd) || ((uintptr_t)w_oihw & 3) || ((uintptr_t)bn_m & 3) ||
-        ((uintptr_t)bn_r & 3) || ((uintptr_t)mean & 3) || ((uintptr_t)rstd & 3) || ((uintptr_t)ws & 255)) return DSMIL_E_ALIGN;
+    if (!al16(x) || !al16(y) || !al16(in_mean) || !al16(in_rstd) || ((uintptr_t)w_oihw & 3) || ((uintptr_t)bn_m & 3) ||
+        ((uintptr_t)bn_r & 3) || ((uintptr_t)mean & 3) || ((uintptr_t)rstd & 3) || !al256p(ws)) return DSMIL_E_ALIGN;
     const ConvPlan p = plan_conv(s, B, H, W, in_mean != nullptr, make_form(precision, expt()), expt());
     const T32ConvWs L = t32_conv_ws(p);
     if (ws_bytes < L.total) return DSMIL_E_WORKSPACE;
@@ -2982,7 +2975,7 @@ int dsmil_trunk32_stem(const void* x, int32_t x_is_u8_nhwc, const float* conv1_w
     if (!t32_prec(precision)) return DSMIL_E_UNSUPPORTED;
     if (const int rc = t32_stem_check(B, H, W)) return rc;
     if ((!x_is_u8_nhwc && ((uintptr_t)x & 3)) || ((uintptr_t)conv1_w & 3) || ((uintptr_t)bn_m & 3) || ((uintptr_t)bn_r & 3) ||
-        !t32_al16(pooled) || !t32_al16(mean) || !t32_al16(rstd) || ((uintptr_t)ws & 255)) return DSMIL_E_ALIGN;
+        !al16(pooled) || !al16(mean) || !al16(rstd) || !al256p(ws)) return DSMIL_E_ALIGN;
     const Dims d = dims_for(H, W);
     const T32StemWs L = t32_stem_ws(B, d);
     if (ws_bytes < L.total) return DSMIL_E_WORKSPACE;
@@ -3003,9 +2996,9 @@ int dsmil_trunk32_tail(int32_t kind, const float* y2, const float* m2, const flo
     if (!y2 || !m2 || !r2 || !idn || !out || B < 1 || HW < 1 || C < 1 || kind < 0 || kind > 2) return DSMIL_E_INVALID;
     if (kind == 1 ? (!md || !rd) : (md || rd)) return DSMIL_E_INVALID;
     if (!t32_prec(precision)) return DSMIL_E_UNSUPPORTED;
-    if (!t32_tail_c(C) || (long long)B * HW * C >= 0x7fffffffLL) return DSMIL_E_UNSUPPORTED;
-    if (!t32_al16(y2) || !t32_al16(m2) || !t32_al16(r2) || !t32_al16(idn) || !t32_al16(md) || !t32_al16(rd) ||
-        (kind == 2 ? ((uintptr_t)out & 3) != 0 : !t32_al16(out))) return DSMIL_E_ALIGN;
+    if (!chan_ok(C) || !map_fits(B, HW, 1, C)) return DSMIL_E_UNSUPPORTED;   // k_norm_add_relu's layout; pixels inside an unsigned
+    if (!al16(y2) || !al16(m2) || !al16(r2) || !al16(idn) || !al16(md) || !al16(rd) ||
+        (kind == 2 ? ((uintptr_t)out & 3) != 0 : !al16(out))) return DSMIL_E_ALIGN;
     launch_tail((hipStream_t)stream, kind == 2, kind == 1, y2, m2, r2, idn, md, rd, out, B, HW, C);
     return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }

@@ -1079,6 +1079,47 @@ def resnet18in_forward(x, convs, fc_w=None, fc_b=None, bn_norms=None, precision=
     return feats, classes
 
 
+# ---- the ctypes glue the embedder's stage, conv-backward and norm-backward wrappers below share ----
+_REFUSALS = {"dsmil_trunk16": "shape outside what the 16-bit trunk's kernels implement",       # by the entry family's prefix
+             "dsmil_trunk32": "shape or precision outside what the fp32-class trunk's kernels implement",
+             "dsmil_conv_bwd": "shape outside what the conv backward kernels implement",
+             "dsmil_norm_bwd": "shape outside what the norm backward kernels implement"}
+
+
+def _refused(rc, what):
+    """Raises for a non-zero rc of entry ``what``: NotImplementedError for DSMIL_E_UNSUPPORTED, else as _native.check."""
+    if rc == _native.DSMIL_E_UNSUPPORTED:
+        raise NotImplementedError(f"{what}: {next(v for k, v in _REFUSALS.items() if what.startswith(k))}")
+    _native.check(rc, what)
+
+
+def _scratch(dev, need, ws=None):
+    """A workspace of ``need`` bytes: a fresh one (256 bytes at least), or the caller's ``ws`` once seen to be large enough."""
+    if ws is None:
+        return torch.empty(max(int(need), 256), dtype=torch.uint8, device=dev)
+    if not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
+        raise RuntimeError(f"ws must be a contiguous uint8 CUDA(HIP) tensor of at least {need} bytes")
+    return ws
+
+
+def _plan(entry, fields, *args, what=None):
+    """The 16 int32 plan entry ``entry`` writes behind ``args``, as a dict of ``fields``; a refusal raises as ``what``'s."""
+    out = (ctypes.c_int32 * 16)()
+    _refused(getattr(_native.lib(), entry)(*args, out), what or entry)
+    return dict(zip(fields, list(out)))
+
+
+def _size_or_reason(need, plan_entry, what, *args):
+    """``need`` as a size query answered it — or, where it answered 0, the refusal of the plan entry that knows why."""
+    if need == 0:
+        _plan(plan_entry, (), *args, what=what)
+    return need
+
+
+def _conv_out(H, W, ks, stride, pad):      # (emb::outdim, csrc/emb_host.h)
+    return (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
+
+
 # ---------------------------------------------------------------------------------------------
 # the stages of the 16-bit activation trunk ALONE (csrc/resnet_b16.h behind dsmil_trunk16_*): FOR TESTS — no product path
 # calls these.  16-bit maps are int16 tensors [positions(B,H,W), C] holding the raw bf16 / fp16 bits in the shared-border
@@ -1088,20 +1129,10 @@ def resnet18in_forward(x, convs, fc_w=None, fc_b=None, bn_norms=None, precision=
 TRUNK16_KINDS = {"bf16": 1, "fp16": 2}
 
 
-def _t16_check(rc, what):
-    if rc == _native.DSMIL_E_UNSUPPORTED:
-        raise NotImplementedError(f"{what}: shape outside what the 16-bit trunk's kernels implement")
-    _native.check(rc, what)
-
-
 def _t16_buf(t, name):
     if not t.is_cuda or t.dtype not in (torch.int16, torch.uint16) or not t.is_contiguous():
         raise RuntimeError(f"{name} must be a contiguous int16 / uint16 CUDA(HIP) tensor")
     return t
-
-
-def _t16_scratch(dev, nbytes):
-    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
 
 
 def trunk16_positions(B, H, W):
@@ -1118,7 +1149,7 @@ def trunk16_layout(x_nhwc, kind, borders_only=False):
     with torch.cuda.device(x.device):
         rc = _native.lib().dsmil_trunk16_layout(_ptr(x), _ptr(out), B, H, W, C, TRUNK16_KINDS[kind], 1 if borders_only else 0,
                                                 _stream(x.device))
-    _t16_check(rc, "dsmil_trunk16_layout")
+    _refused(rc, "dsmil_trunk16_layout")
     return out
 
 
@@ -1128,14 +1159,14 @@ def trunk16_conv(buf, w, B, Hi, Wi, stride, pad, kind):
     Cout, Cin, ks, _ = w.shape
     if tuple(buf.shape) != (trunk16_positions(B, Hi, Wi), Cin):
         raise ValueError(f"buf {tuple(buf.shape)} is not a [{B},{Hi},{Wi},{Cin}] map in the shared-border layout")
-    Ho, Wo = (Hi + 2 * pad - ks) // stride + 1, (Wi + 2 * pad - ks) // stride + 1
+    Ho, Wo = _conv_out(Hi, Wi, ks, stride, pad)
     L = _native.lib()
-    ws = _t16_scratch(buf.device, L.dsmil_trunk16_conv_workspace_bytes(Cin, Cout, ks))
+    ws = _scratch(buf.device, L.dsmil_trunk16_conv_workspace_bytes(Cin, Cout, ks))
     out = torch.empty((max(trunk16_positions(B, Ho, Wo), 1), Cout), dtype=torch.int16, device=buf.device)
     with torch.cuda.device(buf.device):
         rc = L.dsmil_trunk16_conv(_ptr(buf), _ptr(w), _ptr(out), B, Hi, Wi, Cin, Cout, ks, stride, pad, TRUNK16_KINDS[kind],
                                   _ptr(ws), ws.numel(), _stream(buf.device))
-    _t16_check(rc, "dsmil_trunk16_conv")
+    _refused(rc, "dsmil_trunk16_conv")
     return out, Ho, Wo
 
 
@@ -1151,11 +1182,11 @@ def trunk16_norm(buf, B, H, W, kind, idn=None, relu=True, out=None):
             raise ValueError(f"{name} must have buf's shape")
     y = torch.zeros_like(buf) if out is None else out
     L = _native.lib()
-    ws = _t16_scratch(buf.device, L.dsmil_trunk16_norm_workspace_bytes(B, C))
+    ws = _scratch(buf.device, L.dsmil_trunk16_norm_workspace_bytes(B, C))
     with torch.cuda.device(buf.device):
         rc = L.dsmil_trunk16_norm(_ptr(buf), _ptr(idn), _ptr(y), B, H, W, C, 1 if relu else 0, TRUNK16_KINDS[kind], _ptr(ws),
                                   ws.numel(), _stream(buf.device))
-    _t16_check(rc, "dsmil_trunk16_norm")
+    _refused(rc, "dsmil_trunk16_norm")
     return y
 
 
@@ -1166,12 +1197,12 @@ def trunk16_pool(buf, idn, B, H, W, kind):
     if tuple(buf.shape) != (trunk16_positions(B, H, W), C) or idn.shape != buf.shape:
         raise ValueError(f"buf / idn are not [{B},{H},{W},{C}] maps in the shared-border layout")
     L = _native.lib()
-    ws = _t16_scratch(buf.device, L.dsmil_trunk16_norm_workspace_bytes(B, C))
+    ws = _scratch(buf.device, L.dsmil_trunk16_norm_workspace_bytes(B, C))
     feats = torch.empty((B, C), dtype=torch.float32, device=buf.device)
     with torch.cuda.device(buf.device):
         rc = L.dsmil_trunk16_pool(_ptr(buf), _ptr(idn), _ptr(feats), B, H, W, C, TRUNK16_KINDS[kind], _ptr(ws), ws.numel(),
                                   _stream(buf.device))
-    _t16_check(rc, "dsmil_trunk16_pool")
+    _refused(rc, "dsmil_trunk16_pool")
     return feats
 
 
@@ -1186,18 +1217,20 @@ def trunk16_forward(x_nhwc, convs, kind):
     L = _native.lib()
     keep = [_f32c(w.detach(), "conv weight") for w in convs]
     arr = (ctypes.c_void_p * len(keep))(*[t.data_ptr() for t in keep])
-    ws = _t16_scratch(x.device, L.dsmil_trunk16_workspace_bytes(depth, B, Hp, Wp))
+    ws = _scratch(x.device, L.dsmil_trunk16_workspace_bytes(depth, B, Hp, Wp))
     feats = torch.empty((B, L.dsmil_resnet_feature_dim(depth)), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         rc = L.dsmil_trunk16_forward(depth, _ptr(x), B, Hp, Wp, arr, _ptr(feats), TRUNK16_KINDS[kind], _ptr(ws), ws.numel(),
                                      _stream(x.device))
-    _t16_check(rc, "dsmil_trunk16_forward")
+    _refused(rc, "dsmil_trunk16_forward")
     return feats
 
 
 # ---------------------------------------------------------------------------------------------
-# the stages of the fp32-class trunk ALONE (csrc/resnet_fwd.hip, csrc/wino_w1.h behind dsmil_trunk32_*): FOR TESTS — no product
-# path calls these.  Maps are fp32 NHWC tensors, statistics fp32 [B,C].  precision "fp32" = the product form (two fp16 planes,
+# the stages of the fp32-class trunk ALONE (csrc/resnet_fwd.hip, csrc/wino_w1.h behind dsmil_trunk32_*).  The TRAINING forward is
+# composed from them (simclr.NativeConv2d: trunk32_conv; NativeBasicBlock: trunk32_conv, trunk32_tail; both ask
+# trunk32_conv_supported); trunk32_conv_plan and trunk32_stem serve tests and tools only.  Maps are fp32 NHWC tensors,
+# statistics fp32 [B,C].  precision "fp32" = the product form (two fp16 planes,
 # three products), "half" = one fp16 plane.  A shape the kernels do not take raises NotImplementedError (DSMIL_E_UNSUPPORTED),
 # every other refusal RuntimeError; nothing is launched in either case.
 # ---------------------------------------------------------------------------------------------
@@ -1207,22 +1240,18 @@ TRUNK32_TAILS = {"identity": 0, "down": 1, "pool": 2}
 _T32_PLAN_FIELDS = ("kernel", "tile", "IB", "TYB", "TXB", "nby", "nbx", "Ho", "Wo", "nslots", "grid_x", "grid_y", "block", "products")
 
 
-def _t32_check(rc, what):
-    if rc == _native.DSMIL_E_UNSUPPORTED:
-        raise NotImplementedError(f"{what}: shape or precision outside what the fp32-class trunk's kernels implement")
-    _native.check(rc, what)
-
-
 def trunk32_conv_plan(Cin, Cout, ks, stride, pad, B, H, W, norm=False, precision="fp32"):
     """What plan_conv decides for this conv on B maps of H x W (no device needed): a dict of ``kernel`` ("w1", "unit", "s6"),
     ``tile`` (direct: 42 / 22 / 24), the Winograd unit ``IB, TYB, TXB, nby, nbx``, ``Ho, Wo, nslots``, ``grid_x, grid_y, block``
     and ``products`` (plane products per MAC)."""
-    out = (ctypes.c_int32 * 16)()
-    rc = _native.lib().dsmil_trunk32_conv_plan(Cin, Cout, ks, stride, pad, B, H, W, 1 if norm else 0, TRUNK32_PRECISIONS[precision], out)
-    _t32_check(rc, "dsmil_trunk32_conv_plan")
-    d = dict(zip(_T32_PLAN_FIELDS, list(out)))
+    d = _plan("dsmil_trunk32_conv_plan", _T32_PLAN_FIELDS, Cin, Cout, ks, stride, pad, B, H, W, 1 if norm else 0, TRUNK32_PRECISIONS[precision])
     d["kernel"] = TRUNK32_KERNELS[d["kernel"]]
     return d
+
+
+def trunk32_conv_supported(Cin, Cout, ks, stride, pad, B, H, W, precision="fp32"):
+    """True where dsmil_trunk32_conv takes the shape.  No device."""
+    return _native.lib().dsmil_trunk32_conv_workspace_bytes(Cin, Cout, ks, stride, pad, B, H, W, TRUNK32_PRECISIONS[precision]) > 0
 
 
 def trunk32_conv(x_nhwc, w, stride, pad, in_stats=None, frozen=None, precision="fp32"):
@@ -1237,16 +1266,16 @@ def trunk32_conv(x_nhwc, w, stride, pad, in_stats=None, frozen=None, precision="
     im, ir = (_f32c(t, "in_stats") for t in in_stats) if in_stats is not None else (None, None)
     bm, br = (_f32c(t, "frozen") for t in frozen) if frozen is not None else (None, None)
     p = TRUNK32_PRECISIONS[precision]
-    Ho, Wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
+    Ho, Wo = _conv_out(H, W, ks, stride, pad)
     L = _native.lib()
-    ws = _t16_scratch(x.device, L.dsmil_trunk32_conv_workspace_bytes(Cin, Cout, ks, stride, pad, B, H, W, p))
+    ws = _scratch(x.device, L.dsmil_trunk32_conv_workspace_bytes(Cin, Cout, ks, stride, pad, B, H, W, p))
     y = torch.empty((B, max(Ho, 0), max(Wo, 0), Cout), dtype=torch.float32, device=x.device)
     mean = torch.empty((B, Cout), dtype=torch.float32, device=x.device)
     rstd = torch.empty_like(mean)
     with torch.cuda.device(x.device):
         rc = L.dsmil_trunk32_conv(_ptr(x), _ptr(w), _ptr(im), _ptr(ir), _ptr(bm), _ptr(br), _ptr(y), _ptr(mean), _ptr(rstd), B, H, W,
                                   Cin, Cout, ks, stride, pad, p, _ptr(ws), ws.numel(), _stream(x.device))
-    _t32_check(rc, "dsmil_trunk32_conv")
+    _refused(rc, "dsmil_trunk32_conv")
     return y, mean, rstd
 
 
@@ -1263,17 +1292,16 @@ def trunk32_stem(x, conv1_w, frozen=None, precision="fp32"):
     if tuple(w.shape) != (64, 3, 7, 7):
         raise ValueError("conv1_w must be [64,3,7,7]")
     bm, br = (_f32c(t, "frozen") for t in frozen) if frozen is not None else (None, None)
-    H1, W1 = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
-    Hp, Wp = (H1 + 2 - 3) // 2 + 1, (W1 + 2 - 3) // 2 + 1
+    Hp, Wp = _conv_out(*_conv_out(H, W, 7, 2, 3), 3, 2, 1)
     L = _native.lib()
-    ws = _t16_scratch(x.device, L.dsmil_trunk32_stem_workspace_bytes(B, H, W))
+    ws = _scratch(x.device, L.dsmil_trunk32_stem_workspace_bytes(B, H, W))
     pooled = torch.empty((B, Hp, Wp, 64), dtype=torch.float32, device=x.device)
     mean = torch.empty((B, 64), dtype=torch.float32, device=x.device)
     rstd = torch.empty_like(mean)
     with torch.cuda.device(x.device):
         rc = L.dsmil_trunk32_stem(_ptr(x), 1 if u8 else 0, _ptr(w), _ptr(bm), _ptr(br), _ptr(pooled), _ptr(mean), _ptr(rstd), B, H, W,
                                   TRUNK32_PRECISIONS[precision], _ptr(ws), ws.numel(), _stream(x.device))
-    _t32_check(rc, "dsmil_trunk32_stem")
+    _refused(rc, "dsmil_trunk32_stem")
     return pooled, mean, rstd
 
 
@@ -1292,7 +1320,7 @@ def trunk32_tail(kind, y2, stats, idn, down_stats=None):
     with torch.cuda.device(y2.device):
         rc = _native.lib().dsmil_trunk32_tail(TRUNK32_TAILS[kind], _ptr(y2), _ptr(m2), _ptr(r2), _ptr(idn), _ptr(md), _ptr(rd), _ptr(out),
                                               B, HW, C, 0, _stream(y2.device))
-    _t32_check(rc, "dsmil_trunk32_tail")
+    _refused(rc, "dsmil_trunk32_tail")
     return out
 
 
@@ -1307,31 +1335,14 @@ _CONV_BWD_PLAN_FIELDS = ("which", "Ho", "Wo", "out_rows", "out_cols", "grid_x", 
                          "run_len", "cols_pad")
 
 
-def _cb_check(rc, what):
-    if rc == _native.DSMIL_E_UNSUPPORTED:
-        raise NotImplementedError(f"{what}: shape outside what the conv backward kernels implement")
-    _native.check(rc, what)
-
-
 def conv_backward_plan(Cin, Cout, ks, stride, pad, B, H, W, which="weight"):
     """What the host decides for this gradient (no device needed): a dict of ``Ho, Wo`` (the map of dy), ``out_rows, out_cols``
     (the output GEMM), ``grid_x, grid_y, grid_z, block``, and for the weight gradient ``chunk`` (positions per chunk),
     ``n_partials`` (partials a dw element is summed from), ``run_len`` (the longest run of positions one accumulator sums)
     and ``cols_pad``.  For the data gradient ``run_len`` = Cout ks^2 and ``n_partials`` = 1."""
-    out = (ctypes.c_int32 * 16)()
-    rc = _native.lib().dsmil_conv_bwd_plan(Cin, Cout, ks, stride, pad, B, H, W, CONV_BWD_WHICH[which], out)
-    _cb_check(rc, "dsmil_conv_bwd_plan")
-    d = dict(zip(_CONV_BWD_PLAN_FIELDS, list(out)))
+    d = _plan("dsmil_conv_bwd_plan", _CONV_BWD_PLAN_FIELDS, Cin, Cout, ks, stride, pad, B, H, W, CONV_BWD_WHICH[which])
     d["which"] = which
     return d
-
-
-def _cb_scratch(dev, need, ws):
-    if ws is None:
-        return _t16_scratch(dev, need)
-    if not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
-        raise RuntimeError(f"ws must be a contiguous uint8 CUDA(HIP) tensor of at least {need} bytes")
-    return ws
 
 
 def conv_backward_weight(x_nhwc, dy_nhwc, ks, stride, pad, in_stats=None, ws=None):
@@ -1341,20 +1352,19 @@ def conv_backward_weight(x_nhwc, dy_nhwc, ks, stride, pad, in_stats=None, ws=Non
     x, dy = _f32c(x_nhwc, "x_nhwc"), _f32c(dy_nhwc, "dy_nhwc")
     B, H, W, Cin = x.shape
     Cout = dy.shape[3]
-    Ho, Wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
+    Ho, Wo = _conv_out(H, W, ks, stride, pad)
     if tuple(dy.shape) != (B, Ho, Wo, Cout):
         raise ValueError(f"dy is {tuple(dy.shape)}, this conv of x gives {(B, Ho, Wo, 'Cout')}")
     im, ir = (_f32c(t, "in_stats") for t in in_stats) if in_stats is not None else (None, None)
     L = _native.lib()
-    need = L.dsmil_conv_bwd_workspace_bytes(Cin, Cout, ks, stride, pad, B, H, W, 0)
-    if need == 0:
-        _cb_check(L.dsmil_conv_bwd_plan(Cin, Cout, ks, stride, pad, B, H, W, 0, (ctypes.c_int32 * 16)()), "dsmil_conv_bwd_weight")
-    ws = _cb_scratch(x.device, need, ws)
+    shape = (Cin, Cout, ks, stride, pad, B, H, W, 0)
+    need = _size_or_reason(L.dsmil_conv_bwd_workspace_bytes(*shape), "dsmil_conv_bwd_plan", "dsmil_conv_bwd_weight", *shape)
+    ws = _scratch(x.device, need, ws)
     dw = torch.empty((Cout, Cin, ks, ks), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         rc = L.dsmil_conv_bwd_weight(_ptr(x), _ptr(im), _ptr(ir), _ptr(dy), _ptr(dw), B, H, W, Cin, Cout, ks, stride, pad, _ptr(ws),
                                      ws.numel(), _stream(x.device))
-    _cb_check(rc, "dsmil_conv_bwd_weight")
+    _refused(rc, "dsmil_conv_bwd_weight")
     return dw
 
 
@@ -1366,18 +1376,17 @@ def conv_backward_data(dy_nhwc, w, H, W, stride, pad, ws=None):
     Cout_w, Cin, ks, _ = w.shape
     if Cout_w != Cout:
         raise ValueError(f"w gives {Cout_w} output channels, dy has {Cout}")
-    if (Ho, Wo) != ((H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1):
+    if (Ho, Wo) != _conv_out(H, W, ks, stride, pad):
         raise ValueError(f"dy is {Ho} x {Wo}, this conv of a {H} x {W} input gives another map")
     L = _native.lib()
-    need = L.dsmil_conv_bwd_workspace_bytes(Cin, Cout, ks, stride, pad, B, H, W, 1)
-    if need == 0:
-        _cb_check(L.dsmil_conv_bwd_plan(Cin, Cout, ks, stride, pad, B, H, W, 1, (ctypes.c_int32 * 16)()), "dsmil_conv_bwd_data")
-    ws = _cb_scratch(dy.device, need, ws)
+    shape = (Cin, Cout, ks, stride, pad, B, H, W, 1)
+    need = _size_or_reason(L.dsmil_conv_bwd_workspace_bytes(*shape), "dsmil_conv_bwd_plan", "dsmil_conv_bwd_data", *shape)
+    ws = _scratch(dy.device, need, ws)
     dx = torch.empty((B, H, W, Cin), dtype=torch.float32, device=dy.device)
     with torch.cuda.device(dy.device):
         rc = L.dsmil_conv_bwd_data(_ptr(dy), _ptr(w), _ptr(dx), B, H, W, Cin, Cout, ks, stride, pad, _ptr(ws), ws.numel(),
                                    _stream(dy.device))
-    _cb_check(rc, "dsmil_conv_bwd_data")
+    _refused(rc, "dsmil_conv_bwd_data")
     return dx
 
 
@@ -1396,21 +1405,12 @@ _NORM_BWD_PLAN_FIELDS = ("kind", "chunk", "n_partials", "run_len", "lanes", "n_s
                          "block", "groups")
 
 
-def _nb_check(rc, what):
-    if rc == _native.DSMIL_E_UNSUPPORTED:
-        raise NotImplementedError(f"{what}: shape outside what the norm backward kernels implement")
-    _native.check(rc, what)
-
-
 def norm_backward_plan(kind, B, HW, C):
     """What the host decides for this call (no device needed): a dict of ``chunk`` (pixels per chunk), ``n_partials`` (partials
     an (n, c) sum is added from, in chunk order), ``lanes`` (accumulators per channel and chunk, combined in a fixed tree),
     ``run_len`` (the longest serial run of terms one accumulator adds), ``n_sums`` (2; "add_down" 3), ``grid_partial,
     grid_finish, grid_apply, block`` and ``groups`` (4-channel groups per thread)."""
-    out = (ctypes.c_int32 * 16)()
-    rc = _native.lib().dsmil_norm_bwd_plan(NORM_BWD_KINDS[kind], B, HW, C, out)
-    _nb_check(rc, "dsmil_norm_bwd_plan")
-    d = dict(zip(_NORM_BWD_PLAN_FIELDS, list(out)))
+    d = _plan("dsmil_norm_bwd_plan", _NORM_BWD_PLAN_FIELDS, NORM_BWD_KINDS[kind], B, HW, C)
     d["kind"] = kind
     return d
 
@@ -1448,10 +1448,8 @@ def norm_backward(kind, g, y, stats, out=None, down=None, ws=None):
         if t is not None and tuple(t.shape) != (B, C):
             raise ValueError("statistics must be [B, C]")
     L = _native.lib()
-    need = L.dsmil_norm_bwd_workspace_bytes(k, B, HW, C)
-    if need == 0:
-        _nb_check(L.dsmil_norm_bwd_plan(k, B, HW, C, (ctypes.c_int32 * 16)()), "dsmil_norm_bwd")
-    ws = _cb_scratch(y.device, need, ws)
+    need = _size_or_reason(L.dsmil_norm_bwd_workspace_bytes(k, B, HW, C), "dsmil_norm_bwd_plan", "dsmil_norm_bwd", k, B, HW, C)
+    ws = _scratch(y.device, need, ws)
     gy = torch.empty_like(y)
     if kind == "add":
         gres = torch.empty_like(y)
@@ -1460,7 +1458,7 @@ def norm_backward(kind, g, y, stats, out=None, down=None, ws=None):
     with torch.cuda.device(y.device):
         rc = L.dsmil_norm_bwd(k, _ptr(g), _ptr(o), _ptr(y), _ptr(m), _ptr(r), _ptr(yd), _ptr(md), _ptr(rd), _ptr(gy), _ptr(gyd),
                               _ptr(gres), B, HW, C, _ptr(ws), ws.numel(), _stream(y.device))
-    _nb_check(rc, "dsmil_norm_bwd")
+    _refused(rc, "dsmil_norm_bwd")
     return gy if kind == "relu" else (gy, gres) if kind == "add" else (gy, gyd)
 
 

@@ -224,6 +224,23 @@ def _conv_geometry(m):
     return ks, stride, pad
 
 
+def _nhwc(x):
+    """The NHWC view of an NCHW tensor: no copy where x is ``channels_last``, else one."""
+    xp = x.permute(0, 2, 3, 1)
+    return xp if xp.is_contiguous() else xp.contiguous()
+
+
+def _swap_children(model, eligible, make):
+    """Replaces every module m under ``model`` with ``eligible(m)`` by ``make(m)``, in m's training mode; returns how many."""
+    swapped = 0
+    for parent in list(model.modules()):
+        for name, m in list(parent.named_children()):
+            if eligible(m):
+                setattr(parent, name, make(m).train(m.training))
+                swapped += 1
+    return swapped
+
+
 class _ConvNative(torch.autograd.Function):
     """y = conv(x, w) on NHWC fp32 maps.  Forward: ops.trunk32_conv (the fp32-class trunk's kernels) where it takes the shape;
     the stem (Cin = 3), which that entry leaves to the fused stem kernel, runs aten's conv.  Backward: ops.conv_backward_data /
@@ -278,8 +295,7 @@ class NativeConv2d(torch.nn.Conv2d):
             return None
         if not ops.conv_backward_supported(*args, "weight"):         # also the geometry check of a call without gradients
             return None
-        from . import _native
-        fwd_native = _native.lib().dsmil_trunk32_conv_workspace_bytes(*args, 0) > 0
+        fwd_native = ops.trunk32_conv_supported(*args)
         if not fwd_native and Cin != 3:
             return None
         return ks, stride, pad, fwd_native
@@ -288,10 +304,7 @@ class NativeConv2d(torch.nn.Conv2d):
         plan = self._native_plan(x)
         if plan is None:
             return super().forward(x)
-        xp = x.permute(0, 2, 3, 1)
-        if not xp.is_contiguous():
-            xp = xp.contiguous()
-        return _ConvNative.apply(xp, self.weight, *plan).permute(0, 3, 1, 2)
+        return _ConvNative.apply(_nhwc(x), self.weight, *plan).permute(0, 3, 1, 2)
 
 
 def native_conv_eligible(m):
@@ -310,18 +323,12 @@ def use_native_convs(model):
     """Swaps every eligible ``nn.Conv2d`` of ``model`` (in place) for a ``NativeConv2d`` holding the SAME Parameter object, and
     returns how many it swapped.  state_dict() keys and values, optimizers holding the parameters and ``isinstance(m,
     nn.Conv2d)`` checks (modules.resnet_convs_of, IClassifier's native inference route) are unaffected."""
-    swapped = 0
-    for parent in list(model.modules()):
-        for name, m in list(parent.named_children()):
-            if not native_conv_eligible(m):
-                continue
-            new = NativeConv2d(m.in_channels, m.out_channels, m.kernel_size, m.stride, m.padding, m.dilation, m.groups, False,
-                               m.padding_mode, device="meta")
-            new.weight = m.weight
-            new.train(m.training)
-            setattr(parent, name, new)
-            swapped += 1
-    return swapped
+    def make(m):
+        new = NativeConv2d(m.in_channels, m.out_channels, m.kernel_size, m.stride, m.padding, m.dilation, m.groups, False,
+                           m.padding_mode, device="meta")
+        new.weight = m.weight
+        return new
+    return _swap_children(model, native_conv_eligible, make)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -419,14 +426,14 @@ class NativeBasicBlock(resnet.BasicBlock):
         P = self.conv1.out_channels
         if Cin != self.conv1.in_channels or min(B, H, W) < 1:
             return None
-        Ho, Wo = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
+        Ho, Wo = ops._conv_out(H, W, 3, stride, 1)
         convs = [(Cin, P, 3, stride, 1, B, H, W), (P, P, 3, 1, 1, B, Ho, Wo)]
         if dconv is not None:
             convs.append((Cin, P, 1, stride, 0, B, H, W))
-        L = ops._native.lib()
-        if not all(L.dsmil_trunk32_conv_workspace_bytes(*c, 0) > 0 for c in convs):
+        if not all(ops.trunk32_conv_supported(*c) for c in convs):
             return None
-        if not ops.norm_backward_supported("relu", B, Ho * Wo, P):          # the tail's condition on C too; "add_down" alike
+        # (emb::chan_ok, the tail's rule on P too, and C <= 2048 of the norm backward's own: this answer covers the tail)
+        if not ops.norm_backward_supported("relu", B, Ho * Wo, P):
             return None
         if torch.is_grad_enabled():
             want_x = x.requires_grad
@@ -444,10 +451,7 @@ class NativeBasicBlock(resnet.BasicBlock):
         if plan is None:
             return super().forward(x)
         stride, dconv = plan
-        xp = x.permute(0, 2, 3, 1)
-        if not xp.is_contiguous():
-            xp = xp.contiguous()
-        out = _BasicBlockNative.apply(xp, self.conv1.weight, self.conv2.weight, dconv.weight if dconv is not None else None, stride)
+        out = _BasicBlockNative.apply(_nhwc(x), self.conv1.weight, self.conv2.weight, dconv.weight if dconv is not None else None, stride)
         return out.permute(0, 3, 1, 2)
 
 
@@ -463,19 +467,13 @@ def use_native_blocks(model):
     the same Parameter objects, submodule names and state_dict() keys and values), and returns how many it swapped.
     resnet18_in_convs / modules.resnet_convs_of and IClassifier's native inference route are unaffected; it composes with
     ``use_native_convs`` in either order (which then still covers the stem)."""
-    swapped = 0
-    for parent in list(model.modules()):
-        for name, m in list(parent.named_children()):
-            if not native_block_eligible(m):
-                continue
-            new = NativeBasicBlock.__new__(NativeBasicBlock)
-            torch.nn.Module.__init__(new)
-            for child, sub in m._modules.items():                  # registration order: conv1, bn1, relu, conv2, bn2, downsample
-                new.register_module(child, sub)
-            if m.downsample is None:                               # a None set in __init__ is a plain attribute, not a child
-                new.downsample = None
-            new.stride = m.stride
-            new.train(m.training)
-            setattr(parent, name, new)
-            swapped += 1
-    return swapped
+    def make(m):
+        new = NativeBasicBlock.__new__(NativeBasicBlock)
+        torch.nn.Module.__init__(new)
+        for child, sub in m._modules.items():                      # registration order: conv1, bn1, relu, conv2, bn2, downsample
+            new.register_module(child, sub)
+        if m.downsample is None:                                   # a None set in __init__ is a plain attribute, not a child
+            new.downsample = None
+        new.stride = m.stride
+        return new
+    return _swap_children(model, native_block_eligible, make)

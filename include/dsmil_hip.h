@@ -682,12 +682,15 @@ size_t dsmil_trunk16_workspace_bytes(int32_t depth, int32_t B, int32_t Hp, int32
 int dsmil_trunk16_forward(int32_t depth, const float* x_nhwc, int32_t B, int32_t Hp, int32_t Wp, const float* const* conv_w,
                           float* feats, int32_t kind, void* ws, size_t ws_bytes, void* stream);
 
-/* ---- the stages of the fp32-class trunk ALONE — FOR TESTS (tests/test_trunk32_gpu.py; no reference counterpart).  The default
+/* ---- the stages of the fp32-class trunk ALONE (no reference counterpart): what tests/test_trunk32_gpu.py compares kernel by
+ * kernel, and what the embedder's TRAINING forward is composed from (dsmil-wsi_amd/simclr.py).  The default
  * embedder path (fp32 activations, conv operands as two fp16 planes and three plane products: csrc/resnet_fwd.hip, csrc/wino_w1.h)
  * is otherwise reachable only as a whole network, where an InstanceNorm behind every conv rescales what a kernel got wrong; these
  * entries run ONE stage of it on buffers the caller controls, through the trunk's own host calls (plan_conv / pack_conv / run_conv,
  * plan_stem / pack_stem / launch_stem / finish_stem, launch_tail: what dsmil_resnet_pack and dsmil_resnet_forward call — same
- * kernels, same plans, same launch geometry).  No product path calls them.
+ * kernels, same plans, same launch geometry).  The training path calls dsmil_trunk32_conv (and its size query, as the eligibility
+ * answer) from NativeConv2d and NativeBasicBlock and dsmil_trunk32_tail from NativeBasicBlock; dsmil_trunk32_conv_plan and
+ * dsmil_trunk32_stem are FOR TESTS and tools; the inference path calls none of them.
  *   precision  0 = the product form (two fp16 planes of each operand, products h0 w0 + h0 w1 + h1 w0), 1 = one fp16 plane
  *              (what precision 1 of dsmil_resnet_forward_ex runs); anything else is DSMIL_E_UNSUPPORTED.
  *   maps       fp32 NHWC, 16-byte aligned; statistics [B,C] fp32 (16-byte aligned where a kernel reads them: in_mean / in_rstd,
@@ -713,7 +716,8 @@ int dsmil_trunk16_forward(int32_t depth, const float* x_nhwc, int32_t B, int32_t
  *   dsmil_trunk32_tail     kind 0: out = relu((y2 - m2) r2 + idn); kind 1: out = relu((y2 - m2) r2 + (idn - md) rd) (idn = the raw
  *                          downsample branch; md / rd only here); kind 2: out [B,C] = mean over pixels of kind 0.  y2, idn, out
  *                          [B,HW,C]; k_norm_add_relu's grid is the forward's (8192 workgroups at most, grid stride beyond).  C / 4
- *                          must divide 256 or be a multiple of it.
+ *                          must divide 256 or be a multiple of it (the rule dsmil_norm_bwd states too: one function,
+ *                          csrc/emb_host.h).
  * Every check runs BEFORE the first launch, in the order DSMIL_E_INVALID (null pointers, pointer pairs half given, in place,
  * non-positive sizes, kind), DSMIL_E_UNSUPPORTED (precision, the forms, channel multiples and sizes above), DSMIL_E_ALIGN,
  * DSMIL_E_WORKSPACE; the *_workspace_bytes queries answer 0 for arguments the entry refuses.
