@@ -26,6 +26,13 @@ def _wdict(fc_w, fc_b, q0_w, q0_b, q2_w, q2_b, fcc_w, fcc_b, detach=False):
     return dict(zip(ops.W_KEYS, ts))
 
 
+def check_row_map(row_map, n_rows):
+    """An out-of-range index of a row map would become an out-of-bounds device read in the native row loads: checked once
+    per call on the device, surfaced with the step's only host sync (the loss .item() of train_tcga.py:74)."""
+    if row_map is not None and row_map.numel():
+        torch._assert_async((row_map.min() >= 0) & (row_map.max() < n_rows), "row_map index out of range")
+
+
 class FCLayer(nn.Module):
     """dsmil.py:6-12."""
 
@@ -275,19 +282,9 @@ class MILNet(nn.Module):
         around ``self(x)``.  ``pos_weight`` / ``weight``: the class weights of BCEWithLogitsLoss(weight, pos_weight)
         (train_mil.py:172-173), each None or a tensor of 1 or C elements; the fused path hands them to the weighted loss head
         (dsmil_agg_loss_head_w / _bags_w) as fp32 [C] device vectors (ops.bce_class_weights)."""
-        bc = self.b_classifier
-        if (self._fused(feats) and self._loss_dtype(feats) and not bc.passing_v and not feats.requires_grad
-                and self.i_classifier.fc[0].out_features <= 64):   # dsmil_agg_loss_head: one wave of classes; more take the torch expression
-            if feats.dtype == torch.bfloat16 and row_map is not None:
-                feats, row_map = feats.index_select(0, row_map), None
-            if row_map is not None and row_map.numel():
-                # an out-of-range index would become an out-of-bounds device read in the row loads: checked once per
-                # bag on the device, surfaced with the step's only host sync (the loss .item() of train_tcga.py:74)
-                torch._assert_async((row_map.min() >= 0) & (row_map.max() < feats.shape[0]),
-                                    "row_map index out of range")
-            _, w = self._lin_weights()
-            cw = ops.bce_class_weights(pos_weight, weight, self.i_classifier.fc[0].out_features, feats.device)
-            return _BagLossFunction.apply(feats, label, row_map, None, *w.values(), bc.nonlinear, *cw)
+        out = self._native_loss(feats, label, row_map, None, pos_weight, weight)
+        if out is not None:
+            return out
         x = feats if row_map is None else feats.index_select(0, row_map)
         ins, bag, _, _ = self._forward(x, _f32_out=True)
         mx, _ = torch.max(ins, 0)
@@ -295,6 +292,22 @@ class MILNet(nn.Module):
         loss = 0.5 * F.binary_cross_entropy_with_logits(bag.view(1, -1), y, weight, pos_weight=pos_weight) + \
             0.5 * F.binary_cross_entropy_with_logits(mx.view(1, -1), y, weight, pos_weight=pos_weight)
         return loss, bag, mx
+
+    def _native_loss(self, feats, labels, row_map, lengths, pos_weight, weight):
+        """The native objective of ``bag_loss`` (``lengths`` None) / ``batch_loss`` (a tuple): _BagLossFunction's result, or None
+        where the rows, the model or the class count are not the native loss call's."""
+        # (a batch alone also needs what dsmil_agg_backward_bags asks of the query biases: _batch_native)
+        if not (self._batch_native(feats) if lengths is not None else self._fused(feats) and self._loss_dtype(feats)):
+            return None
+        bc, C = self.b_classifier, self.i_classifier.fc[0].out_features
+        if bc.passing_v or feats.requires_grad or C > 64:   # (dsmil_agg_loss_head: one wave of classes; more take the torch expression)
+            return None
+        if feats.dtype == torch.bfloat16 and row_map is not None:
+            feats, row_map = feats.index_select(0, row_map), None
+        check_row_map(row_map, feats.shape[0])
+        _, w = self._lin_weights()
+        cw = ops.bce_class_weights(pos_weight, weight, C, feats.device)
+        return _BagLossFunction.apply(feats, labels, row_map, lengths, *w.values(), bc.nonlinear, *cw)
 
     @torch.no_grad()
     def forward_bags(self, bags):
@@ -381,17 +394,9 @@ class MILNet(nn.Module):
         lengths = [int(n) for n in lengths]
         n = len(lengths)
         labels = labels.reshape(n, -1)
-        bc = self.b_classifier
-        if (self._batch_native(feats) and not bc.passing_v and not feats.requires_grad
-                and self.i_classifier.fc[0].out_features <= 64):
-            if feats.dtype == torch.bfloat16 and row_map is not None:
-                feats, row_map = feats.index_select(0, row_map), None
-            if row_map is not None and row_map.numel():
-                torch._assert_async((row_map.min() >= 0) & (row_map.max() < feats.shape[0]), "row_map index out of range")
-            _, w = self._lin_weights()
-            cw = ops.bce_class_weights(pos_weight, weight, self.i_classifier.fc[0].out_features, feats.device)
-            loss, pred, mx, each = _BagLossFunction.apply(feats, labels, row_map, tuple(lengths), *w.values(), bc.nonlinear, *cw)
-            return (loss, pred, mx, each) if per_bag else (loss, pred, mx)
+        out = self._native_loss(feats, labels, row_map, tuple(lengths), pos_weight, weight)
+        if out is not None:
+            return out if per_bag else out[:3]
         x = feats if row_map is None else feats.index_select(0, row_map)
         ins, pred, _, _ = self._forward_batch(x, lengths, _f32_out=True)
         mx = torch.stack([t.max(0)[0] for t in torch.split(ins, lengths, dim=0)])

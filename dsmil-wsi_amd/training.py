@@ -123,6 +123,14 @@ def _native_bce(criterion, C=None):
     return criterion.pos_weight, criterion.weight
 
 
+def _objective(criterion, ins_prediction, bag_prediction, bag_label):
+    """train_tcga.py:66-70 / train_mil.py:50-55 for an arbitrary criterion, from torch ops: (loss, max_prediction)."""
+    max_prediction, _ = torch.max(ins_prediction, 0)
+    loss = 0.5 * criterion(bag_prediction.view(1, -1), bag_label.view(1, -1)) + \
+        0.5 * criterion(max_prediction.view(1, -1), bag_label.view(1, -1))
+    return loss, max_prediction
+
+
 def bag_loss(milnet, criterion, bag_feats, bag_label, row_map=None):
     """train_tcga.py:64-71.  ``row_map``: dropout_patches as an index list (rows of bag_feats that enter the bag).
     With a criterion the native objective computes (_native_bce: the stock BCEWithLogitsLoss, or one with per-class
@@ -134,9 +142,7 @@ def bag_loss(milnet, criterion, bag_feats, bag_label, row_map=None):
     if row_map is not None:
         bag_feats = bag_feats.index_select(0, row_map)
     ins_prediction, bag_prediction, _, _ = milnet(bag_feats)
-    max_prediction, _ = torch.max(ins_prediction, 0)
-    loss = 0.5 * criterion(bag_prediction.view(1, -1), bag_label.view(1, -1)) + \
-        0.5 * criterion(max_prediction.view(1, -1), bag_label.view(1, -1))
+    loss, max_prediction = _objective(criterion, ins_prediction, bag_prediction, bag_label)
     return loss, bag_prediction, max_prediction
 
 
@@ -179,7 +185,7 @@ class FusedTrainStep:
         self.bce = bce   # the criterion's own (pos_weight, weight) tensors, each None or 1 / C elements
         self.weighted = any(t is not None for t in bce)
         self.group = optimizer.param_groups[0]
-        self.m, self.v, steps = [], [], []
+        self.m, self.v = [], []
         for p in params:
             if p is None:
                 self.m.append(None); self.v.append(None)
@@ -190,10 +196,7 @@ class FusedTrainStep:
                 st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
             self.m.append(st["exp_avg"]); self.v.append(st["exp_avg_sq"])
-            steps.append(int(float(st["step"])))
-        if len(set(steps)) != 1:
-            raise RuntimeError("Adam state with different step counts per parameter")
-        self.step = steps[0]
+        self.resync()
         self.nonlinear = milnet.b_classifier.nonlinear
         self._live = [p for p in params if p is not None] + [t for t in self.m + self.v if t is not None]
 
@@ -232,23 +235,31 @@ class FusedTrainStep:
             return False
         return bag_feats.dtype == torch.float32 or (bag_feats.dtype == torch.bfloat16 and bag_feats.shape[1] % 8 == 0)
 
+    def _enqueue(self, entry, *data, **kw):
+        """One native step: ``entry`` (ops.agg_train_step or agg_train_step_bags) on ``data`` with the parameters, the
+        optimiser's state tensors and Adam's hyper-parameters of this step; returns what the entry returns."""
+        g = self.group
+        with torch.no_grad():
+            out = entry(*data, [p.data if p is not None else None for p in self.params], self.m, self.v, self.step + 1, g["lr"],
+                        g["betas"], g["eps"], g["weight_decay"], nonlinear=self.nonlinear, **kw)
+        self.step += 1   # only once the native step was enqueued: a call that raised applied no update (sync() stays consistent)
+        # the kernels wrote the parameters through raw pointers: tell torch (version counters key the packed-weight caches
+        # of the inference path, and autograd's saved-tensor checks)
+        torch.autograd.graph.increment_version(self._live)
+        return out
+
     def step_bags(self, feats, lengths, labels, row_map=None):
         """One optimiser step on a BATCH of bags stored back to back (dsmil_agg_train_step_bags, or its bf16 form for
         bf16-stored rows): the objective is the mean of the bags' losses (MILNet.batch_loss).  ``lengths`` count logical
         rows, ``row_map`` as in batch_loss.  Returns (loss, each bag's own loss [n]) as detached device tensors."""
         from . import ops
-        g = self.group
-        if row_map is not None and row_map.numel() and feats.dtype == torch.float32:
-            # (as MILNet.batch_loss: an out-of-range index would be an out-of-bounds device read in the row loads)
-            torch._assert_async((row_map.min() >= 0) & (row_map.max() < feats.shape[0]), "row_map index out of range")
-        with torch.no_grad():
-            # (per version of the criterion's tensors: a pos_weight edited in place between steps is picked up)
-            pos_weight, weight = ops.bce_class_weights(*self.bce, self.params[0].shape[0], feats.device)
-            loss, each = ops.agg_train_step_bags(feats, lengths, labels, [p.data if p is not None else None for p in self.params],
-                                                 self.m, self.v, self.step + 1, g["lr"], g["betas"], g["eps"], g["weight_decay"],
-                                                 nonlinear=self.nonlinear, row_map=row_map, pos_weight=pos_weight, weight=weight)
-        self.step += 1   # only once the native step was enqueued (see __call__)
-        torch.autograd.graph.increment_version(self._live)
+        from .modules import check_row_map
+        if feats.dtype == torch.float32:
+            check_row_map(row_map, feats.shape[0])
+        # (per version of the criterion's tensors: a pos_weight edited in place between steps is picked up)
+        pos_weight, weight = ops.bce_class_weights(*self.bce, self.params[0].shape[0], feats.device)
+        loss, each = self._enqueue(ops.agg_train_step_bags, feats, lengths, labels, row_map=row_map, pos_weight=pos_weight,
+                                   weight=weight)
         return loss.reshape(()), each
 
     def __call__(self, bag_feats, bag_label, row_map=None):
@@ -258,16 +269,7 @@ class FusedTrainStep:
         if bag_feats.dtype == torch.bfloat16 or self.weighted:
             n = int(row_map.numel()) if row_map is not None else bag_feats.shape[0]
             return self.step_bags(bag_feats, [n], bag_label.reshape(1, -1), row_map)[0]
-        g = self.group
-        with torch.no_grad():
-            loss = ops.agg_train_step(bag_feats, bag_label, [p.data if p is not None else None for p in self.params], self.m,
-                                      self.v, self.step + 1, g["lr"], g["betas"], g["eps"], g["weight_decay"],
-                                      nonlinear=self.nonlinear, row_map=row_map)
-        self.step += 1   # only once the native step was enqueued: a call that raised applied no update (sync() stays consistent)
-        # the kernels wrote the parameters through raw pointers: tell torch (version counters key the packed-weight caches
-        # of the inference path, and autograd's saved-tensor checks)
-        torch.autograd.graph.increment_version(self._live)
-        return loss.reshape(())
+        return self._enqueue(ops.agg_train_step, bag_feats, bag_label, row_map=row_map).reshape(())
 
     def resync(self):
         """Re-read the step count from the optimiser's state (after a generic optimizer.step() between fused steps)."""
@@ -286,170 +288,121 @@ class FusedTrainStep:
 class LossReadback:
     """The per-step `loss.item()` of train_tcga.py:75 without the per-step stall: every step's loss is still copied to the host
     and reported, but through a pinned two-slot ring — `push(loss)` enqueues this step's device-to-host copy and hands back the
-    PREVIOUS step's value (its copy finished while this step was being enqueued), `flush()` the last one.  The host stays at
-    most one step ahead of the GPU, every value arrives, in order; only the moment of the read moves by one step."""
+    PREVIOUS step's value (its copy finished while this step was being enqueued), `flush()` the last one and empties the ring.
+    The host stays at most one step ahead of the GPU, every value arrives, in order; only the moment of the read moves by one
+    step.  A 0-dim loss comes back as a float; a 1-D tensor (the per-bag losses of one minibatch step) as a list of floats."""
 
     def __init__(self, device):
         self.cuda = torch.device(device).type == "cuda"
-        self.buf = torch.zeros(2, dtype=torch.float32, pin_memory=True) if self.cuda else None
+        self.buf = torch.zeros(2, dtype=torch.float32, pin_memory=True) if self.cuda else None   # the slots of a 0-dim loss
         self.ev = [torch.cuda.Event(), torch.cuda.Event()] if self.cuda else None
-        self.n = 0
-        self.pending = None
+        self.slot = [None, None]   # per slot the host copy of what was pushed (CUDA: pinned, complete once ev[k] has passed)
+        self.n = 0                 # pushes since the ring was last empty
+
+    def _read(self, k):
+        if self.cuda:
+            self.ev[k].synchronize()
+        return self.slot[k].tolist()
 
     def push(self, loss):
-        """loss: 0-dim tensor of this step.  Returns the previous step's loss as a float (None on the first call)."""
-        if not self.cuda:
-            prev, self.pending = self.pending, float(loss.detach())
-            return prev
+        """loss: this step's 0-dim or 1-D tensor.  Returns the previous step's value (None on the first call)."""
+        loss = loss.detach()
+        if loss.dim() != 1:
+            loss = loss.reshape(())
         k = self.n & 1
-        self.buf[k:k + 1].copy_(loss.detach().reshape(1), non_blocking=True)
-        self.ev[k].record()
-        prev = None
-        if self.n > 0:
-            self.ev[k ^ 1].synchronize()
-            prev = float(self.buf[k ^ 1])
+        if self.cuda:
+            self.slot[k] = self.buf[k] if loss.dim() == 0 else torch.empty(loss.shape, dtype=torch.float32, pin_memory=True)
+            self.slot[k].copy_(loss, non_blocking=True)
+            self.ev[k].record()
+        else:
+            self.slot[k] = loss.clone()
         self.n += 1
-        return prev
-
-    def push_many(self, losses):
-        """The same hand-over for a 1-D tensor (the per-bag losses of one minibatch step): returns the previous call's
-        values as a list of floats (None on the first call)."""
-        if not self.cuda:
-            prev, self.pending = self.pending, [float(v) for v in losses.detach()]
-            return prev
-        if not hasattr(self, "many"):
-            self.many, self.many_ev, self.many_n = [None, None], [torch.cuda.Event(), torch.cuda.Event()], 0
-        k = self.many_n & 1
-        self.many[k] = torch.empty(losses.numel(), dtype=torch.float32, pin_memory=True)
-        self.many[k].copy_(losses.detach().reshape(-1), non_blocking=True)
-        self.many_ev[k].record()
-        prev = None
-        if self.many_n > 0:
-            self.many_ev[k ^ 1].synchronize()
-            prev = self.many[k ^ 1].tolist()
-        self.many_n += 1
-        return prev
-
-    def flush_many(self):
-        if not self.cuda:
-            prev, self.pending = self.pending, None
-            return prev
-        if not getattr(self, "many_n", 0):
-            return None
-        k = (self.many_n - 1) & 1
-        self.many_ev[k].synchronize()
-        return self.many[k].tolist()
+        return self._read(k ^ 1) if self.n > 1 else None
 
     def flush(self):
-        if not self.cuda:
-            prev, self.pending = self.pending, None
-            return prev
         if self.n == 0:
             return None
-        k = (self.n - 1) & 1
-        self.ev[k].synchronize()
-        return float(self.buf[k])
+        last, self.n = self._read((self.n - 1) & 1), 0
+        return last
 
 
-def _train_groups(args, dirs, milnet, criterion, optimizer, cache, log, per_step):
-    """``train`` with ``bags_per_step`` > 1: consecutive bags of the shuffled order, per_step at a time (the last group may
-    be short), ONE summed objective (batch_loss: the mean of the bags' losses), one backward and one optimizer.step() per
-    group.  This is minibatch training — a different optimisation schedule from the reference's one step per bag.
-    With the reference's model / criterion / optimiser (FusedTrainStep.create) a group's whole step is one native call
-    (FusedTrainStep.step_bags) unless ``args.fused_step`` is false; the generic lines remain for everything else."""
-    device = next(milnet.parameters()).device
-    readback = LossReadback(device)
-    losses, done = [], 0
-    # the whole step of a group as one native call when the model / criterion / optimiser are the reference's
-    fused = FusedTrainStep.create(milnet, criterion, optimizer) if getattr(args, "fused_step", True) else None
+def _optimiser_step(fused, optimizer, feats, native, generic):
+    """One optimiser step, the same for every loop here: ``native()`` — the whole step as one native call (FusedTrainStep) —
+    when there is a fused step and it takes these rows, else the generic lines around ``generic()`` -> (loss, per-bag
+    losses): zero_grad, backward, optimizer.step(), with the fused step's counter written back before (the optimiser's own
+    step count = every update so far, fused ones included) and re-read after.  Returns the step's per-bag losses, detached."""
+    if fused is not None and fused.accepts(feats):
+        return native()
+    if fused is not None:
+        fused.sync()
+    optimizer.zero_grad()
+    loss, each = generic()
+    loss.backward()
+    optimizer.step()
+    if fused is not None:
+        fused.resync()
+    return each.detach()
 
-    def report(vals):
-        nonlocal done
-        for v in vals or ():
-            sys.stdout.write("\r Training bag [%d/%d] bag loss: %.4f" % (done, len(dirs), v))
-            done += 1
-    try:
-        for g0 in range(0, len(dirs), per_step):
-            bags, labels, maps, off, any_map = [], [], [], 0, False
-            for item in dirs[g0:g0 + per_step]:
-                bag_feats, bag_label = cache.get(item, args.feats_size)
-                rows = dropout_rows(bag_feats.size(0), 1 - args.dropout_patch, bag_feats.device)
-                any_map = any_map or rows is not None
-                maps.append((rows if rows is not None else torch.arange(bag_feats.size(0), device=bag_feats.device)) + off)
-                off += bag_feats.size(0)
-                bags.append(bag_feats); labels.append(bag_label.reshape(1, -1))
-            feats = torch.cat(bags, dim=0) if len(bags) > 1 else bags[0]
-            lengths, row_map = [int(m.numel()) for m in maps], torch.cat(maps) if any_map else None
-            if fused is not None and fused.accepts(feats):
-                _, each = fused.step_bags(feats, lengths, torch.cat(labels), row_map)
-            else:
-                if fused is not None:
-                    fused.sync()          # (as in the per-bag loop of ``train``)
-                optimizer.zero_grad()
-                loss, _, _, each = batch_loss(milnet, criterion, feats, lengths, torch.cat(labels), row_map)
-                loss.backward()
-                optimizer.step()
-                if fused is not None:
-                    fused.resync()
-            losses.append(each)
-            if log:   # every bag's own loss, one step late
-                report(readback.push_many(each))
-    finally:
-        if log and dirs:
-            report(readback.flush_many())
-        if fused is not None:
-            fused.sync()
-    return float(torch.cat(losses).sum().item()) / max(1, len(dirs)) if losses else 0.0
+
+def _group(bags):
+    """A group of (feats, label, kept rows or None) as batch_loss / step_bags take it: the rows back to back, the kept rows'
+    counts, the labels [n, C] and — if any bag drops rows — every bag's index list with its offset added, concatenated."""
+    maps, off = [], 0
+    for feats, _, rows in bags:
+        maps.append((rows if rows is not None else torch.arange(feats.size(0), device=feats.device)) + off)
+        off += feats.size(0)
+    feats = torch.cat([b[0] for b in bags], dim=0) if len(bags) > 1 else bags[0][0]
+    row_map = torch.cat(maps) if any(b[2] is not None for b in bags) else None
+    return feats, [int(m.numel()) for m in maps], torch.cat([b[1].reshape(1, -1) for b in bags]), row_map
 
 
 def train(args, train_df, milnet, criterion, optimizer, cache=None, log=True):
     """train_tcga.py:55-76: one optimiser step per bag, bags in random order.  ``args.bags_per_step`` > 1 (not in the
-    reference): one step per group of that many bags instead (_train_groups)."""
+    reference): consecutive bags of the shuffled order, that many at a time (the last group may be short), ONE objective
+    (batch_loss: the mean of the bags' losses), one backward and one optimizer.step() per group — minibatch training, a
+    different optimisation schedule from the reference's.  With the reference's model / criterion / optimiser
+    (FusedTrainStep.create) a whole step is one native call unless ``args.fused_step`` is false; the generic lines remain
+    for everything else (_optimiser_step)."""
     from sklearn.utils import shuffle
     milnet.train()
     device = next(milnet.parameters()).device
     cache = cache or BagCache(device)
-    total_loss = 0.0
     dirs = shuffle(list(train_df))
     per_step = int(getattr(args, "bags_per_step", 1) or 1)
-    if per_step > 1:
-        return _train_groups(args, dirs, milnet, criterion, optimizer, cache, log, per_step)
-    losses = []
-    # the whole step as one native call when the model / criterion / optimiser are the reference's (FusedTrainStep)
     fused = FusedTrainStep.create(milnet, criterion, optimizer) if getattr(args, "fused_step", True) else None
     readback = LossReadback(device)
+    losses, done = [], 0
+
+    def report(vals):   # the progress line of train_tcga.py:74-75 for every bag, in order, written one step late: no stall
+        nonlocal done
+        for v in [vals] if isinstance(vals, float) else vals or ():
+            sys.stdout.write("\r Training bag [%d/%d] bag loss: %.4f" % (done, len(dirs), v))
+            done += 1
     try:
-        for i, item in enumerate(dirs):
-            bag_feats, bag_label = cache.get(item, args.feats_size)
-            rows = dropout_rows(bag_feats.size(0), 1 - args.dropout_patch, bag_feats.device)
-            if fused is not None and fused.accepts(bag_feats):
-                loss = fused(bag_feats, bag_label, rows)
+        for g0 in range(0, len(dirs), per_step):
+            bags = []
+            for item in dirs[g0:g0 + per_step]:
+                bag_feats, bag_label = cache.get(item, args.feats_size)
+                bags.append((bag_feats, bag_label, dropout_rows(bag_feats.size(0), 1 - args.dropout_patch, bag_feats.device)))
+            if per_step == 1:   # the one-bag entries (they launch other kernels than a batch of one); the loss stays 0-dim
+                (feats, label, rows), = bags
+                each = _optimiser_step(fused, optimizer, feats, lambda: fused(feats, label, rows),
+                                       lambda: (bag_loss(milnet, criterion, feats, label, rows)[0],) * 2)
             else:
-                if fused is not None:
-                    fused.sync()          # the optimiser's own step count = every update so far, fused ones included
-                optimizer.zero_grad()
-                loss, _, _ = bag_loss(milnet, criterion, bag_feats, bag_label, rows)
-                loss.backward()
-                optimizer.step()
-                if fused is not None:
-                    fused.resync()        # ... and the fused counter follows the generic update
-            losses.append(loss.detach())
-            if log:   # the progress line of train_tcga.py:74-75, every bag's loss, written one step late (LossReadback): no stall
-                prev = readback.push(loss)
-                if prev is not None:
-                    sys.stdout.write("\r Training bag [%d/%d] bag loss: %.4f" % (i - 1, len(dirs), prev))
+                feats, lengths, labels, row_map = _group(bags)
+                each = _optimiser_step(fused, optimizer, feats, lambda: fused.step_bags(feats, lengths, labels, row_map)[1],
+                                       lambda: batch_loss(milnet, criterion, feats, lengths, labels, row_map)[0::3])
+            losses.append(each)
+            if log:
+                report(readback.push(each))
     finally:
         # also when a step raised: the loss of the last COMPLETED step is still reported and the optimiser's step count is
         # written back (a checkpoint saved by the caller's handler is then consistent)
-        if log and dirs:
-            last = readback.flush()
-            if last is not None:
-                sys.stdout.write("\r Training bag [%d/%d] bag loss: %.4f" % (len(losses) - 1, len(dirs), last))
+        if log:
+            report(readback.flush())
         if fused is not None:
             fused.sync()
-    if losses:
-        total_loss = float(torch.stack(losses).sum().item())
-    return total_loss / max(1, len(dirs))
+    return float(torch.cat([each.reshape(-1) for each in losses]).sum().item()) / max(1, len(dirs)) if losses else 0.0
 
 
 def optimal_thresh(fpr, tpr, thresholds, p=0):
@@ -756,9 +709,7 @@ def mil_epoch_train(bags, ys, idx, milnet, criterion, optimizer, device):
         x = torch.from_numpy(bags[i][np.random.permutation(len(bags[i]))]).to(device)
         y = torch.tensor([[ys[i]]], device=device)
         classes, bag_prediction, _, _ = milnet(x)
-        max_prediction, _ = torch.max(classes, 0)
-        loss = 0.5 * criterion(bag_prediction.view(1, -1), y.view(1, -1)) + \
-            0.5 * criterion(max_prediction.view(1, -1), y.view(1, -1))
+        loss, _ = _objective(criterion, classes, bag_prediction, y)
         loss.backward()
         optimizer.step()
         total += loss.item()
@@ -784,10 +735,7 @@ def mil_epoch_test(bags, ys, idx, milnet, criterion, device):
         x = torch.from_numpy(bags[i]).to(device)
         y = torch.tensor([[ys[i]]], device=device)
         classes, bag_prediction, _, _ = milnet(x)
-        max_prediction, _ = torch.max(classes, 0)
-        loss = 0.5 * criterion(bag_prediction.view(1, -1), y.view(1, -1)) + \
-            0.5 * criterion(max_prediction.view(1, -1), y.view(1, -1))
-        total += loss.item()
+        total += _objective(criterion, classes, bag_prediction, y)[0].item()
         preds.append(float(torch.sigmoid(bag_prediction).squeeze()))  # train_mil.py:77
     return total / max(1, len(idx)), np.asarray(preds)
 

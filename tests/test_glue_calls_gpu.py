@@ -1,4 +1,4 @@
-"""Which entries of libdsmil_hip.so the Python glue (dsmil-wsi_amd/ops.py, modules.py) calls, and in which order: the one-bag
+"""Which entries of libdsmil_hip.so the Python glue (dsmil-wsi_amd/ops.py, modules.py, training.py) calls, and in which order: the one-bag
 and the batched paths keep their own native entries (they launch different kernels), and a packed weight image is cut once
 per weight set — not once per call, not once per stream.  A recording proxy around ``_native.lib()`` notes the name of every
 called symbol and forwards the call.  Shapes: the `tcga` / `passv` weight sets, bags of 5, 64 and 33 rows.  Needs a real MI355X."""
@@ -17,7 +17,9 @@ PACKS = {"dsmil_agg_pack_split", "dsmil_agg_pack_f2", "dsmil_value_pack", "dsmil
 WORK = PACKS | {"dsmil_agg_forward_ex", "dsmil_agg_forward_bf16", "dsmil_agg_forward", "dsmil_agg_loss_head",
                 "dsmil_agg_loss_head_bags", "dsmil_agg_backward", "dsmil_agg_backward_ex", "dsmil_agg_backward_rows",
                 "dsmil_agg_backward_bags", "dsmil_agg_train_step", "dsmil_value_forward", "dsmil_value_backward",
-                "dsmil_value_backward_rows", "dsmil_fc_forward"}
+                "dsmil_value_backward_rows", "dsmil_fc_forward", "dsmil_agg_train_step_bags", "dsmil_agg_train_step_bags_bf16",
+                "dsmil_agg_train_step_bags_w", "dsmil_agg_train_step_bags_bf16_w", "dsmil_agg_loss_head_w",
+                "dsmil_agg_loss_head_bags_w", "dsmil_agg_backward_bags_bf16", "dsmil_adam_step"}
 
 
 class _Recorder:
@@ -163,3 +165,40 @@ def test_packed_images_are_cut_once_per_weight_set(rec, tag):
     for out in outs:
         for a, b in zip(out, ref):
             assert torch.equal(a, b)
+
+
+TRAIN_ROWS = (5, 64, 33, 40)   # one wave of rows, two full tiles, not a multiple of 32; three per step leave a group of one
+
+
+def _train_calls(rec, **kw):
+    """The work entries (packs aside) of one training.train epoch over four small fp32 `tcga` bags: stock criterion, Adam."""
+    import argparse
+    from dsmil_wsi_amd import training as T
+    K, C = VARIANT["tcga"][:2]
+    net = _net("tcga")
+    opt = torch.optim.Adam(net.parameters(), lr=1e-3, betas=(0.5, 0.9), weight_decay=1e-3)
+    bags = []
+    for b, n in enumerate(TRAIN_ROWS):
+        label = torch.zeros(n, C, device="cuda")
+        label[:, b % C] = 1.0
+        bags.append(torch.cat([_rows(n, seed=20 + b), label], 1))
+    args = argparse.Namespace(feats_size=K, num_classes=C, **{"dropout_patch": 0.0, "bags_per_step": 1, "fused_step": True, **kw})
+    rec.take()
+    torch.manual_seed(5)
+    loss = T.train(args, bags, net, torch.nn.BCEWithLogitsLoss(), opt, cache=T.BagCache("cuda", K), log=False)
+    assert loss == loss and 0 < loss < 10, loss
+    assert all(int(opt.state[p]["step"]) == -(-len(bags) // args.bags_per_step) for p in net.parameters())
+    return rec.take()[1]
+
+
+@pytest.mark.parametrize("dropout", [0.0, 0.4])
+def test_train_of_one_bag_per_step_calls_the_one_bag_step(rec, dropout):
+    assert _train_calls(rec, dropout_patch=dropout) == ["dsmil_agg_train_step"] * 4
+
+
+def test_train_of_groups_calls_the_bags_step_also_for_a_short_last_group(rec):
+    assert _train_calls(rec, bags_per_step=3) == ["dsmil_agg_train_step_bags"] * 2
+
+
+def test_train_without_the_fused_step_calls_the_one_bag_entries(rec):
+    assert _train_calls(rec, fused_step=False) == ["dsmil_agg_forward_ex", "dsmil_agg_loss_head", "dsmil_agg_backward_ex"] * 4

@@ -33,7 +33,7 @@ IDS = [f"{t}-{'x'.join(map(str, L)) if len(L) < 4 else 'G1'}-{'bf16' if d is B16
 
 def _batch(tag, lengths, dtype, drop, seed):
     """One batch: rows [sum(lengths), K] on the GPU in ``dtype``, labels [n, C], and with ``drop`` the concatenated per-bag
-    index lists (lengths then count the kept rows) — what training._train_groups builds."""
+    index lists (lengths then count the kept rows) — what training.train builds for a group (training._group)."""
     K, C = VARIANT[tag][0], VARIANT[tag][1]
     x = torch.from_numpy(np.concatenate([make_bag(seed + 13 * i, n, K) for i, n in enumerate(lengths)])).cuda().to(dtype)
     labels = torch.zeros(len(lengths), C)
