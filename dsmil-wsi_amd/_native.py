@@ -72,6 +72,24 @@ class AggGrads(ctypes.Structure):
                 ("fc_w", "fc_b", "q0_w", "q0_b", "q2_w", "q2_b", "fcc_w", "fcc_b")]
 
 
+class AggBwdLayout(ctypes.Structure):
+    """struct dsmil_agg_bwd_layout (include/dsmil_hip.h): where a backward call leaves its intermediates — FOR TESTS."""
+    REGIONS = ("gB", "Dv", "qmax", "gq", "gA", "gs", "gz2", "Hb", "Qb", "gH", "gqp", "part0", "part1", "pb0", "pb1", "part", "part_b")
+    _fields_ = [(n, ctypes.c_uint64) for n in REGIONS + ("total",)] + [("T32", ctypes.c_int64)] + \
+        [(n, ctypes.c_int32) for n in ("S", "R", "splits", "small_rows", "tile", "qrow_vec")]
+
+
+BWD_TILE = ("hs", "w1_reg", "w4_dma", "w4_reg")     # DSMIL_BWD_TILE_*, by value
+
+
+def backward_layout(n_bags, N, K, Kv, C, nonlinear=1, rows_aligned16=1, q0w_aligned16=1):
+    """dsmil_agg_backward_layout (FOR TESTS; host only): n_bags == 0 for the one-bag entries."""
+    out = AggBwdLayout()
+    check(lib().dsmil_agg_backward_layout(n_bags, N, K, Kv, C, nonlinear, rows_aligned16, q0w_aligned16, ctypes.byref(out)),
+          "dsmil_agg_backward_layout")
+    return out
+
+
 class BceWeights(ctypes.Structure):
     """struct dsmil_bce_weights (include/dsmil_hip.h): device pointers, [C] fp32 each, either may be NULL."""
     _fields_ = [("pos_weight", ctypes.c_void_p), ("weight", ctypes.c_void_p)]
@@ -212,6 +230,7 @@ SIGNATURES = {
                                                ctypes.POINTER(AggParams), c_f32p, c_f32p, c_i64p, c_f32p, c_f32p, c_f32p,
                                                c_f32p, c_f32p, ctypes.POINTER(AggGrads), c_f32p, c_i64p, ctypes.c_void_p,
                                                ctypes.c_size_t, ctypes.c_void_p, c_f32p]),
+    "dsmil_agg_backward_layout": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64] + [ctypes.c_int32] * 6 + [ctypes.POINTER(AggBwdLayout)]),
     "dsmil_agg_backward_bags_bf16_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
                                                                        ctypes.c_int32, ctypes.c_int32]),
     "dsmil_agg_backward_bags_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i64p, ctypes.c_int32, ctypes.c_int64,

@@ -1260,6 +1260,14 @@ BwdWs bwd_layout(int n_bags, long long N, int K, int Kv, int C, int nonlinear) {
     return w;
 }
 
+// What the size queries answer: they do not know the query's form, and NEITHER layout is always the larger one — the linear
+// query has two column slabs fewer, so k_tn_split gets more row ranges (TN_WGS / nslab) and their partials can outweigh the
+// regions only the nonlinear query uses (10 000 x 512: 53 ranges against 40).  A size that fits both.
+size_t bwd_bytes_either(int n_bags, long long N, int K, int Kv, int C) {
+    const size_t a = bwd_layout(n_bags, N, K, Kv, C, 1).total, b = bwd_layout(n_bags, N, K, Kv, C, 0).total;
+    return a > b ? a : b;
+}
+
 // the regions of a workspace as typed pointers
 struct BwdBufs {
     float *gB, *Dv, *zero, *qmax, *gq, *gA, *gs, *gz2, *Hb, *Qb, *gH, *gqp;
@@ -1574,7 +1582,7 @@ extern "C" {
 
 size_t dsmil_agg_backward_workspace_bytes(int64_t N, int32_t K, int32_t Kv, int32_t C) {
     if (N <= 0 || K <= 0 || Kv <= 0 || C <= 0) return 0;
-    return bwd_layout(0, N, K, Kv, C, 1).total;   // the nonlinear layout is the larger one
+    return bwd_bytes_either(0, N, K, Kv, C);
 }
 
 int dsmil_agg_backward(const float* feats, const float* vals, int64_t N, const dsmil_agg_params* p,
@@ -1612,7 +1620,27 @@ int dsmil_agg_backward_rows(const float* feats, const float* vals, int64_t N, co
 
 size_t dsmil_agg_backward_bags_workspace_bytes(int32_t n_bags, int64_t total_rows, int32_t K, int32_t Kv, int32_t C) {
     if (n_bags <= 0 || total_rows <= 0 || K <= 0 || Kv <= 0 || C <= 0) return 0;
-    return bwd_layout(n_bags, total_rows, K, Kv, C, 1).total;   // the nonlinear layout is the larger one
+    return bwd_bytes_either(n_bags, total_rows, K, Kv, C);
+}
+
+// FOR TESTS: the layout and the row tile of a call, host arithmetic only.  The offsets are bwd_layout's; the tile is step 4's
+// choice in agg_backward_impl (n_bags == 0) / agg_backward_bags_impl, by the expressions written there (v4, nw).
+int dsmil_agg_backward_layout(int32_t n_bags, int64_t N, int32_t K, int32_t Kv, int32_t C, int32_t nonlinear,
+                              int32_t rows_aligned16, int32_t q0w_aligned16, dsmil_agg_bwd_layout* out) {
+    if (!out || n_bags < 0 || N <= 0 || N < n_bags || K <= 0 || Kv <= 0 || C <= 0) return DSMIL_E_INVALID;
+    const BwdWs L = bwd_layout(n_bags, N, K, Kv, C, nonlinear ? 1 : 0);
+    *out = dsmil_agg_bwd_layout{};
+    out->gB = L.gB; out->Dv = L.Dv; out->qmax = L.qmax; out->gq = L.gq; out->gA = L.gA; out->gs = L.gs; out->gz2 = L.gz2;
+    out->Hb = L.Hb; out->Qb = L.Qb; out->gH = L.gH; out->gqp = L.gqp; out->part0 = L.part0; out->part1 = L.part1;
+    out->pb0 = L.pb0; out->pb1 = L.pb1; out->part = L.part; out->part_b = L.part_b; out->total = L.total;
+    out->T32 = L.T32; out->S = L.S; out->R = L.R; out->splits = L.splits; out->small_rows = tn_rows(N);
+    const bool v4 = (K % 4 == 0) && rows_aligned16;
+    const bool w4 = (K % 4 == 0) && rows_aligned16 && q0w_aligned16;
+    const int nw = (N / 128 >= 512) ? 4 : 1;
+    if (n_bags == 0) out->tile = (nw == 4) ? (v4 ? DSMIL_BWD_TILE_W4_DMA : DSMIL_BWD_TILE_W4_REG) : (v4 ? DSMIL_BWD_TILE_HS : DSMIL_BWD_TILE_W1_REG);
+    else out->tile = (nw == 4 && v4) ? DSMIL_BWD_TILE_W4_DMA : (nw == 1 && v4) ? DSMIL_BWD_TILE_HS : DSMIL_BWD_TILE_W1_REG;
+    out->qrow_vec = w4 ? 4 : 1;
+    return DSMIL_OK;
 }
 
 int dsmil_agg_backward_bags(const float* feats, const float* vals, const int64_t* offsets, int32_t n_bags,

@@ -268,6 +268,8 @@ typedef struct dsmil_agg_grads {
     float* fcc_b;  /* [C]         */
 } dsmil_agg_grads;
 
+/* The size fits either form of the query (p->nonlinear is not an argument): the larger of the two layouts, which from a few
+ * thousand rows on is the LINEAR query's (more row ranges of partials).  The same holds for the _rows and _bags queries. */
 size_t dsmil_agg_backward_workspace_bytes(int64_t N, int32_t K, int32_t Kv, int32_t C);
 /* dsmil_agg_backward_ex adds: g_max [C] — the SPARSE instance-stream gradient of the training objective (the max
  * over instances touches one row per class: g_fc_w[c] += g_max[c] * feats[idx_c], g_fc_b[c] += g_max[c]; may be
@@ -340,6 +342,34 @@ int dsmil_agg_loss_head_bags(const float* classes, const int64_t* offsets, const
 int dsmil_agg_loss_head_bags_w(const float* classes, const int64_t* offsets, const float* pred, const int64_t* idx,
                                const float* labels, int32_t n_bags, int32_t C, float* loss, float* max_pred,
                                float* g_pred, float* g_max, const dsmil_bce_weights* bw, void* stream);
+
+/* ---- where the fp32 aggregator backward leaves its intermediates — FOR TESTS (tests/test_agg_bwd_precision_gpu.py; no reference
+ * counterpart).  dsmil_agg_backward_layout answers, on the host alone (no launch, no device memory touched), what
+ * dsmil_agg_backward* (n_bags == 0: the one-bag layout) or dsmil_agg_backward_bags (n_bags >= 1) will do with a workspace for
+ * N rows in all: the byte offset of every intermediate from the workspace's start (each region is written once per call and
+ * never overwritten, so a test can read the inputs and outputs of every launch back after the call), the row ranges of the
+ * contraction over the instances and the row tile of step 4.  The offsets are the launch sequences' own (bwd_layout is called).
+ *   gB [sets, C, Kv], Dv [sets, C], qmax / gq [sets, C, 128] (sets = max(n_bags, 1)); gA, gs [N, C]; gz2, Hb, Qb, gH [N, 128];
+ *   gqp [T32 (one bag) or N / 32 + n_bags + 1 tile slots (bag b's first: offsets[b] / 32 + b), C, 128];
+ *   part0 [S, 128, K], part1 [S, 128, 128], pb0 / pb1 [S, 128]: row range s = rows s R .. min((s + 1) R, N) - 1;
+ *   part [splits, C, K], part_b [splits, C]: k_tn_small's (dense g_classes only): row range s = rows s small_rows .. of N
+ *   total: the bytes the call needs for this `nonlinear` (the *_workspace_bytes queries answer the nonlinear size)
+ *   tile: DSMIL_BWD_TILE_* from N, K and rows_aligned16 (the rows' base address % 16 == 0), as the entry chooses it;
+ *   qrow_vec: 4 when the critical-query kernel loads 16 bytes (K % 4 == 0 and rows_aligned16 and q0w_aligned16), else 1.
+ * Returns DSMIL_E_INVALID for a NULL `out`, n_bags < 0 or a size <= 0 (N < n_bags included).
+ * Added without a change of DSMIL_ABI_VERSION (it stays 6, no existing signature moved): a caller finds it by symbol. */
+#define DSMIL_BWD_TILE_HS 0        /* hidden-split 64-row tile (k_bwd_rows_hs, k_bwd_gh_hs) */
+#define DSMIL_BWD_TILE_W1_REG 1    /* one-wave 32-row tile, register-staged (k_bwd_rows<1,1>) */
+#define DSMIL_BWD_TILE_W4_DMA 2    /* four-wave 128-row tile, LDS-DMA staged (k_bwd_rows<4,4>, k_bwd_gh<4>) */
+#define DSMIL_BWD_TILE_W4_REG 3    /* four-wave 128-row tile, register-staged (k_bwd_rows<4,1>; one bag only) */
+typedef struct dsmil_agg_bwd_layout {
+    uint64_t gB, Dv, qmax, gq, gA, gs, gz2, Hb, Qb, gH, gqp, part0, part1, pb0, pb1, part, part_b;   /* byte offsets */
+    uint64_t total;
+    int64_t T32;                   /* 32-row tiles of N rows */
+    int32_t S, R, splits, small_rows, tile, qrow_vec;
+} dsmil_agg_bwd_layout;
+int dsmil_agg_backward_layout(int32_t n_bags, int64_t N, int32_t K, int32_t Kv, int32_t C, int32_t nonlinear,
+                              int32_t rows_aligned16, int32_t q0w_aligned16, dsmil_agg_bwd_layout* out);
 
 /* ---- the batched aggregator backward on bf16-STORED rows (training on a bf16 feature cache) -----------------------------
  * Replaces what autograd derives for `loss.backward()` in train_tcga.py:60-73 when the bag's rows are stored in bfloat16

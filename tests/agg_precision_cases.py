@@ -333,6 +333,17 @@ def _lanes_rand2(t, nlanes, extra):
     return 4 * rounds * (lane ** 2).sum(axis=-1) + (np.log2(nlanes) + extra) * S ** 2
 
 
+def qmax_rand2(xm, Hm, W1, b1, W2, b2):
+    """The critical query's own rounding variances (the docstring's CRITICAL QUERY; qmax_block, and the backward's qrow_body,
+    which adds in the same order): of the hidden pre-activations and of the query pre-activations z, [C, 128] each, for the
+    critical rows xm [C, K] and their hidden layer Hm [C, 128] (fp64)."""
+    S1m = np.abs(xm) @ np.abs(W1).T + np.abs(b1)
+    S2m = np.abs(Hm) @ np.abs(W2).T + np.abs(b2)
+    rq_H2 = U * U * (_lanes_rand2(xm[:, None, :] * W1[None, :, :], 64, 0) + S1m ** 2)
+    rq_z2 = U * U * (_lanes_rand2(Hm[:, None, :] * W2[None, :, :], 64, 0) / 2 + (6 + 1) * S2m ** 2)
+    return rq_H2, rq_z2
+
+
 def _chains(kernel):
     """The query units a lane adds up by sequential fmas, in its order, and the tree levels behind (agg_common.h attend_tail,
     agg_hs.h attend_tail_hs = agg_f2.h f2_tail, agg_f3.h): [groups, chain] unit indices, levels."""
@@ -407,11 +418,8 @@ def reference(x, w, kinds=KINDS):
     r.bar_sumA = 1.01 * (2 * (Rc + 3) + 40) * U
     # the critical query's own error (plain fp32): per class, per hidden / query unit
     xm = x[idx]                                                 # [C, K]
-    S1m = np.abs(xm) @ np.abs(W1).T + np.abs(b1)
     Hm = H[idx]
-    S2m = Hm @ np.abs(W2).T + np.abs(b2)
-    rq_H2 = U * U * (_lanes_rand2(xm[:, None, :] * W1[None, :, :], 64, 0) + S1m ** 2)          # [C, 128]
-    rq_z2 = U * U * (_lanes_rand2(Hm[:, None, :] * W2[None, :, :], 64, 0) / 2 + (6 + 1) * S2m ** 2)
+    rq_H2, rq_z2 = qmax_rand2(xm, Hm, W1, b1, W2, b2)                                          # [C, 128] each
     T = A.T @ ax                                                # [C, K]
     r.kind = {}
     (rw, w1), (rw2, w12), (wmid, wlo), (wmid2, wlo2) = _weight_cuts(w)

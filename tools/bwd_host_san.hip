@@ -33,8 +33,10 @@ static void check_layout(int n_bags, long long N, int K, int Kv, int C, int nl) 
     CHECK(L.total - L.rowbag == (n_bags ? al((size_t)N * 4) : 0));
     CHECK(L.rowbag - L.off == 256);
     CHECK(L.S >= 1 && L.R >= 64 && L.R % 64 == 0 && (long long)L.S * L.R >= N && L.splits >= 1 && L.nx == (K + 63) / 64);
-    // the public queries answer the nonlinear layout
-    if (nl) CHECK(L.total == (n_bags ? dsmil_agg_backward_bags_workspace_bytes(n_bags, N, K, Kv, C) : dsmil_agg_backward_workspace_bytes(N, K, Kv, C)));
+    // the public queries answer a size that fits both forms of the query: the larger of the two layouts
+    const size_t answered = n_bags ? dsmil_agg_backward_bags_workspace_bytes(n_bags, N, K, Kv, C) : dsmil_agg_backward_workspace_bytes(N, K, Kv, C);
+    const size_t other = bwd_layout(n_bags, N, K, Kv, C, !nl).total;
+    CHECK(L.total <= answered && answered == (L.total > other ? L.total : other));
     // the carve: every pointer at its offset; on a real allocation, the first and the last byte of every region are ours
     if (L.total <= (size_t)64 << 20) {
         char* ws = (char*)std::malloc(L.total);
