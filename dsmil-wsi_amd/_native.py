@@ -313,6 +313,14 @@ SIGNATURES = {
     "dsmil_norm_bwd_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32] * 4),
     "dsmil_norm_bwd": (ctypes.c_int, [ctypes.c_int32] + [c_f32p] * 11 + [ctypes.c_int32] * 3 +
                        [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # the stem on the training path: a forward that keeps the raw map and the pool's winners, and its norm / ReLU / pool backward
+    "dsmil_trunk32_stem_train_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32] * 3),
+    "dsmil_trunk32_stem_train": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32] + [c_f32p] * 5 + [ctypes.c_void_p] +
+                                 [ctypes.c_int32] * 4 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "dsmil_stem_pool_bwd_plan": (ctypes.c_int, [ctypes.c_int32] * 4 + [ctypes.POINTER(ctypes.c_int32)]),
+    "dsmil_stem_pool_bwd_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32] * 4),
+    "dsmil_stem_pool_bwd": (ctypes.c_int, [c_f32p] * 4 + [ctypes.c_void_p, c_f32p] + [ctypes.c_int32] * 4 +
+                            [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "dsmil_agg_forward": (ctypes.c_int, [c_f32p, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64,
                                          ctypes.c_int64, ctypes.POINTER(AggParams), c_f32p, c_f32p,
                                          c_f32p, c_f32p, c_f32p, c_i64p, ctypes.c_void_p,

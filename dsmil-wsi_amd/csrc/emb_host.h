@@ -1,5 +1,5 @@
 // The shape rules that the embedder's host code shares, each stated once ("The shared host rules"): used by
-// resnet_fwd.hip (resnet_b16.h's host part and both stage-entry families included), conv_bwd.hip and norm_bwd.hip.  No kernels
+// resnet_fwd.hip (resnet_b16.h's host part and both stage-entry families included), conv_bwd.hip, norm_bwd.hip and stem_bwd.hip.  No kernels
 // live here; chan_layout alone is also callable from device code, so that the kernels of the channel-group layout and the
 // launches that size their grids read one definition.  Include after <hip/hip_runtime.h>.
 #pragma once
@@ -52,6 +52,36 @@ constexpr int CHAN_GRID_MAX = 8192;
 inline int chan_grid(long long npix, const ChanLayout& l) {
     const long long nb = (npix + l.tpb - 1) / l.tpb;
     return (int)(nb < CHAN_GRID_MAX ? nb : CHAN_GRID_MAX);
+}
+
+// The plan of the per-(image, channel) sums over HW pixels and the element pass behind them (norm_bwd.hip, stem_bwd.hip): chunks
+// of 256 pixels, doubled up to 4096 while B x chunks exceeds 2048 workgroups; in a chunk `lanes` accumulators per channel add at
+// most run_len terms each; nsums sums per (n, c).  ws: partials [nsums][B][nparts][C], then coefficients [nsums][B][C] at
+// off_coef.  B HW C < 2^31 and chan_ok(C) hold.  false: the partials would not fit a 32-bit index (refuse as unsupported)
+struct SumPlan {
+    int nsums, chunk, nparts, run_len, lanes, cpt, grid_partial, grid_finish, grid_apply;
+    size_t off_coef, total;
+};
+inline bool sum_plan(int nsums, int B, int HW, int C, SumPlan& p) {
+    constexpr int CHUNK0 = 256, CHUNK_MAX = 4096, WG_TARGET = 2048;
+    p.nsums = nsums;
+    const ChanLayout cl = chan_layout(C);
+    p.lanes = cl.tpb;
+    p.cpt = cl.cpt;
+    p.chunk = CHUNK0;
+    auto nch = [&](int c) { return (long long)(HW + c - 1) / c; };
+    while (nch(p.chunk) * B > WG_TARGET && p.chunk < CHUNK_MAX) p.chunk *= 2;
+    p.nparts = (int)nch(p.chunk);
+    if (3LL * B * p.nparts * C >= 0x7fffffffLL) return false;
+    const int len = HW < p.chunk ? HW : p.chunk;
+    p.run_len = (len + p.lanes - 1) / p.lanes;
+    p.grid_partial = B * p.nparts;                           // <= B HW < 2^31
+    const long long nfin = ((long long)nsums * B * C + 255) / 256;
+    p.grid_finish = (int)(nfin < 4096 ? nfin : 4096);
+    p.grid_apply = chan_grid((long long)B * HW, cl);
+    p.off_coef = al256((size_t)nsums * B * p.nparts * C * sizeof(float));
+    p.total = p.off_coef + al256((size_t)nsums * B * C * sizeof(float));
+    return true;
 }
 
 }  // namespace emb

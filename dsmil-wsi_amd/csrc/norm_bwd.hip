@@ -26,8 +26,6 @@ using namespace emb;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int NB_CHUNK0 = 256, NB_CHUNK_MAX = 4096, NB_WG_TARGET = 2048;   // pixels per chunk: doubled while B chunks > target
-
 struct NbArgs {
     const float *g, *out, *y, *mean, *rstd, *yd, *md, *rd;
     float *gy, *gyd, *gres;
@@ -182,10 +180,7 @@ __global__ __launch_bounds__(256) void k_nb_apply(const NbArgs a) {
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
-struct NbPlan {
-    int nsums, chunk, nparts, run_len, lanes, cpt, grid_partial, grid_finish, grid_apply;
-    size_t off_coef, total;
-};
+using NbPlan = SumPlan;                                       // (emb_host.h: the chunk rule stem_bwd.hip shares)
 
 int nb_check(int kind, int B, int HW, int C) {
     if (B < 1 || HW < 1 || C < 1) return DSMIL_E_INVALID;
@@ -196,26 +191,7 @@ int nb_check(int kind, int B, int HW, int C) {
 }
 
 // the shape has passed nb_check.  false: the partials would not fit a 32-bit index (refused as unsupported)
-bool nb_plan(int kind, int B, int HW, int C, NbPlan& p) {
-    p.nsums = kind == DSMIL_NORM_BWD_ADD_DOWN ? 3 : 2;
-    const ChanLayout cl = chan_layout(C);
-    p.lanes = cl.tpb;
-    p.cpt = cl.cpt;
-    p.chunk = NB_CHUNK0;
-    auto nch = [&](int c) { return (long long)(HW + c - 1) / c; };
-    while (nch(p.chunk) * B > NB_WG_TARGET && p.chunk < NB_CHUNK_MAX) p.chunk *= 2;
-    p.nparts = (int)nch(p.chunk);
-    if (3LL * B * p.nparts * C >= 0x7fffffffLL) return false;
-    const int len = HW < p.chunk ? HW : p.chunk;
-    p.run_len = (len + p.lanes - 1) / p.lanes;
-    p.grid_partial = B * p.nparts;                           // <= B HW < 2^31
-    const long long nfin = ((long long)p.nsums * B * C + 255) / 256;
-    p.grid_finish = (int)(nfin < 4096 ? nfin : 4096);
-    p.grid_apply = chan_grid((long long)B * HW, cl);
-    p.off_coef = al256((size_t)p.nsums * B * p.nparts * C * sizeof(float));
-    p.total = p.off_coef + al256((size_t)p.nsums * B * C * sizeof(float));
-    return true;
-}
+bool nb_plan(int kind, int B, int HW, int C, NbPlan& p) { return sum_plan(kind == DSMIL_NORM_BWD_ADD_DOWN ? 3 : 2, B, HW, C, p); }
 
 }  // namespace
 

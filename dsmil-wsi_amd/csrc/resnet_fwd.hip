@@ -16,6 +16,7 @@
 //   k_stem            7x7 s2 conv on the NCHW input (Cin = 3, K = 147): input window + weights in LDS
 //   k_norm_relu_maxpool  IN + ReLU + 3x3 s2 max-pool of the stem output (max commutes with the
 //                     increasing map x -> relu((x-mean)*rstd), so the window max is taken on raw values)
+//   k_norm_relu_maxpool_win  the same pool for the TRAINING stem (dsmil_trunk32_stem_train): also writes each window's winner
 //   k_conv<NT,NORM>   implicit-GEMM 3x3 / 1x1 conv, M = flattened (image, y, x) output pixels,
 //                     128 pixels x NT*32 channels per workgroup, K looped as (cin-chunk, tap)
 //   k_in_finalize_*   partials -> mean, rstd
@@ -1924,6 +1925,52 @@ __global__ __launch_bounds__(256) void k_norm_relu_maxpool(const float* __restri
     }
 }
 
+// The training stem's pool (dsmil_trunk32_stem_train): k_norm_relu_maxpool for rstd >= 0 that also writes each window's WINNER,
+// the position dy * 3 + dx (0..8, row-major in the unclipped 3 x 3 window) of the first pixel in scan order whose
+// a = fl(fl(y - mean) rstd) equals the window's largest: a later pixel replaces the current one only if strictly greater,
+// max_pool2d's rule.  fl((. - mean) rstd) is monotone, so relu(max a) is relu((max y - mean) rstd): `out` is bit-identical to
+// the sibling's.  A kernel of its own: k_norm_relu_maxpool keeps its instruction stream.
+__global__ __launch_bounds__(256) void k_norm_relu_maxpool_win(const float* __restrict__ y, const float* __restrict__ mean,
+                                                               const float* __restrict__ rstd, float* __restrict__ out,
+                                                               uint8_t* __restrict__ win, int B, int Hi, int Wi, int Ho, int Wo,
+                                                               int C) {
+    const int c4n = C / 4;
+    const int c4 = threadIdx.x % c4n;
+    const unsigned tpb = 256 / c4n, np = (unsigned)B * Ho * Wo;
+    for (unsigned pp = blockIdx.x * tpb + threadIdx.x / c4n; pp < np; pp += gridDim.x * tpb) {
+        unsigned p = pp;
+        const int ox = (int)(p % (unsigned)Wo); p /= (unsigned)Wo;
+        const int oy = (int)(p % (unsigned)Ho);
+        const int n = (int)(p / (unsigned)Ho);
+        const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + (long long)n * C + c4 * 4);
+        const f32x4 rs = *reinterpret_cast<const f32x4*>(rstd + (long long)n * C + c4 * 4);
+        f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        int w[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy) {
+            const int iy = oy * 2 - 1 + dy;
+            if (iy < 0 || iy >= Hi) continue;
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx) {
+                const int ix = ox * 2 - 1 + dx;
+                if (ix < 0 || ix >= Wi) continue;
+                const f32x4 v = *reinterpret_cast<const f32x4*>(y + (((long long)n * Hi + iy) * Wi + ix) * C + c4 * 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float a = (v[e] - mu[e]) * rs[e];
+                    if (a > m[e]) { m[e] = a; w[e] = dy * 3 + dx; }
+                }
+            }
+        }
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = fmaxf(m[e], 0.f);
+        const long long oo = (((long long)n * Ho + oy) * Wo + ox) * C + c4 * 4;
+        *reinterpret_cast<f32x4*>(out + oo) = o;
+        *reinterpret_cast<uchar4*>(win + oo) = make_uchar4((unsigned char)w[0], (unsigned char)w[1], (unsigned char)w[2], (unsigned char)w[3]);
+    }
+}
+
 // out = relu(IN(y2) + (DOWN ? IN(yd) : idn))   NHWC.  HBM-bound streaming: a thread keeps ONE 4-channel group (256 is a
 // multiple of C/4 for every ResNet width, so the grid stride preserves it) and walks pixels with 32-bit arithmetic —
 // the first version spent three 64-bit divisions per 48 bytes of traffic (4.9 TB/s).
@@ -2989,6 +3036,58 @@ int dsmil_trunk32_stem(const void* x, int32_t x_is_u8_nhwc, const float* conv1_w
     if (!launch_stem(sp, x_is_u8_nhwc != 0, st, x, conv1_w, wimg, y0, pooled, part, B, H, W, d)) return DSMIL_E_UNSUPPORTED;
     if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
     return finish_stem(st, sp, bn_m, bn_r, part, y0, pooled, mean, rstd, B, d, nullptr, 0);
+}
+
+// The stem of a TRAINING forward: the two-kernel route (the one the frozen statistics and DSMIL_STEM_FUSE=0 take) with the raw map
+// in the caller's buffer, and a pool pass that also records the winners.  Workspace: the weight image and the statistics partials.
+namespace {
+inline T32StemWs t32_stem_train_ws(int B, const Dims& d) {
+    T32StemWs w;
+    w.wimg = 0;
+    w.y0 = 0;                                                // (the raw map is an output)
+    w.part = al256((size_t)SS_WIMG * sizeof(unsigned short));
+    w.total = w.part + al256((size_t)stem_part_elems(B, d) * sizeof(float));
+    return w;
+}
+// dsmil_trunk32_stem's shapes whose raw map stays under 2^31 elements (what dsmil_stem_pool_bwd takes of it)
+inline int t32_stem_train_check(int B, int H, int W) {
+    if (const int rc = t32_stem_check(B, H, W)) return rc;
+    const Dims d = dims_for(H, W);
+    return map_fits(B, d.H1, d.W1, 64) ? DSMIL_OK : DSMIL_E_UNSUPPORTED;
+}
+}  // namespace
+
+size_t dsmil_trunk32_stem_train_workspace_bytes(int32_t B, int32_t H, int32_t W) {
+    if (B < 1 || H < 1 || W < 1 || t32_stem_train_check(B, H, W)) return 0;
+    return t32_stem_train_ws(B, dims_for(H, W)).total;
+}
+
+int dsmil_trunk32_stem_train(const void* x, int32_t x_is_u8_nhwc, const float* conv1_w, float* y, float* mean, float* rstd,
+                             float* pooled, uint8_t* win, int32_t B, int32_t H, int32_t W, int32_t precision, void* ws,
+                             size_t ws_bytes, void* stream) {
+    if (!x || !conv1_w || !y || !mean || !rstd || !pooled || !win || !ws || B < 1 || H < 1 || W < 1) return DSMIL_E_INVALID;
+    if (!t32_prec(precision)) return DSMIL_E_UNSUPPORTED;
+    if (const int rc = t32_stem_train_check(B, H, W)) return rc;
+    if ((!x_is_u8_nhwc && ((uintptr_t)x & 3)) || ((uintptr_t)conv1_w & 3) || !al16(y) || !al16(pooled) || !al16(mean) || !al16(rstd) ||
+        ((uintptr_t)win & 3) || !al256p(ws)) return DSMIL_E_ALIGN;
+    const Dims d = dims_for(H, W);
+    const T32StemWs L = t32_stem_train_ws(B, d);
+    if (ws_bytes < L.total) return DSMIL_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const Form form = make_form(precision, expt());
+    Expt e = expt();
+    e.stem_unfused = 1;
+    const StemPlan sp = plan_stem(d, B, false, form, e);
+    unsigned short* wimg = (unsigned short*)((char*)ws + L.wimg);
+    float* part = (float*)((char*)ws + L.part);
+    if (const int rc = pack_stem(conv1_w, wimg, form, st)) return rc;
+    if (!launch_stem(sp, x_is_u8_nhwc != 0, st, x, conv1_w, wimg, y, pooled, part, B, H, W, d)) return DSMIL_E_UNSUPPORTED;
+    if (hipGetLastError() != hipSuccess) return DSMIL_E_LAUNCH;
+    hipLaunchKernelGGL(k_in_finalize_stem, dim3((unsigned)B), dim3(64 * FS_G), 0, st, part, mean, rstd, B, sp.nparts);
+    const long long blocks = std::min<long long>(((long long)B * d.Hp * d.Wp * 16 + 255) / 256, 8192);   // finish_stem's grid
+    hipLaunchKernelGGL(k_norm_relu_maxpool_win, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)y, (const float*)mean,
+                       (const float*)rstd, pooled, win, B, d.H1, d.W1, d.Hp, d.Wp, 64);
+    return hipGetLastError() == hipSuccess ? DSMIL_OK : DSMIL_E_LAUNCH;
 }
 
 int dsmil_trunk32_tail(int32_t kind, const float* y2, const float* m2, const float* r2, const float* idn, const float* md,

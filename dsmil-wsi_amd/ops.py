@@ -1083,7 +1083,8 @@ def resnet18in_forward(x, convs, fc_w=None, fc_b=None, bn_norms=None, precision=
 _REFUSALS = {"dsmil_trunk16": "shape outside what the 16-bit trunk's kernels implement",       # by the entry family's prefix
              "dsmil_trunk32": "shape or precision outside what the fp32-class trunk's kernels implement",
              "dsmil_conv_bwd": "shape outside what the conv backward kernels implement",
-             "dsmil_norm_bwd": "shape outside what the norm backward kernels implement"}
+             "dsmil_norm_bwd": "shape outside what the norm backward kernels implement",
+             "dsmil_stem_pool_bwd": "shape outside what the stem's norm / pool backward kernels implement"}
 
 
 def _refused(rc, what):
@@ -1460,6 +1461,86 @@ def norm_backward(kind, g, y, stats, out=None, down=None, ws=None):
                               _ptr(gres), B, HW, C, _ptr(ws), ws.numel(), _stream(y.device))
     _refused(rc, "dsmil_norm_bwd")
     return gy if kind == "relu" else (gy, gres) if kind == "add" else (gy, gyd)
+
+
+# ---------------------------------------------------------------------------------------------
+# the stem on the training path (dsmil_trunk32_stem_train in csrc/resnet_fwd.hip, dsmil_stem_pool_bwd* in csrc/stem_bwd.hip): a
+# forward that keeps the raw map and the pool's winners, and the gradient of the raw map from the gradient of
+# maxpool(relu(IN(y))).  Refusals as above: NotImplementedError for DSMIL_E_UNSUPPORTED, RuntimeError otherwise, nothing launched.
+# ---------------------------------------------------------------------------------------------
+_STEM_BWD_PLAN_FIELDS = ("Hp", "Wp", "chunk", "n_partials", "run_len", "lanes", "grid_partial", "grid_finish", "grid_apply", "block",
+                         "groups")
+
+
+def trunk32_stem_train_supported(B, H, W):
+    """True where dsmil_trunk32_stem_train takes a [B,3,H,W] input.  No device."""
+    return _native.lib().dsmil_trunk32_stem_train_workspace_bytes(B, H, W) > 0
+
+
+def trunk32_stem_train(x, conv1_w, precision="fp32"):
+    """The stem of a training forward: x fp32 NCHW [B,3,H,W] or uint8 NHWC [B,H,W,3] -> (pooled fp32 NHWC [B,Hp,Wp,64], the raw
+    map y [B,H1,W1,64], (mean, rstd) [B,64], win uint8 [B,Hp,Wp,64]: each pool window's winner as dy * 3 + dx).  pooled, mean
+    and rstd are bit-identical to trunk32_stem's."""
+    if not x.is_cuda or not x.is_contiguous() or x.dtype not in (torch.float32, torch.uint8) or x.dim() != 4:
+        raise RuntimeError("x must be a contiguous float32 NCHW or uint8 NHWC CUDA(HIP) tensor")
+    u8 = x.dtype == torch.uint8
+    B, H, W = (x.shape[0], x.shape[1], x.shape[2]) if u8 else (x.shape[0], x.shape[2], x.shape[3])
+    if (x.shape[3] if u8 else x.shape[1]) != 3:
+        raise ValueError("the stem takes three input channels")
+    w = _f32c(conv1_w, "conv1_w")
+    if tuple(w.shape) != (64, 3, 7, 7):
+        raise ValueError("conv1_w must be [64,3,7,7]")
+    H1, W1 = _conv_out(H, W, 7, 2, 3)
+    Hp, Wp = _conv_out(H1, W1, 3, 2, 1)
+    L = _native.lib()
+    ws = _scratch(x.device, L.dsmil_trunk32_stem_train_workspace_bytes(B, H, W))
+    new = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=x.device)
+    y, pooled, win = new(B, H1, W1, 64), new(B, Hp, Wp, 64), new(B, Hp, Wp, 64, dtype=torch.uint8)
+    mean, rstd = new(B, 64), new(B, 64)
+    with torch.cuda.device(x.device):
+        rc = L.dsmil_trunk32_stem_train(_ptr(x), 1 if u8 else 0, _ptr(w), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(pooled), _ptr(win),
+                                        B, H, W, TRUNK32_PRECISIONS[precision], _ptr(ws), ws.numel(), _stream(x.device))
+    _refused(rc, "dsmil_trunk32_stem_train")
+    return pooled, y, (mean, rstd), win
+
+
+def stem_pool_backward_plan(B, H1, W1, C):
+    """What the host decides for this call (no device needed): ``Hp, Wp`` (the pooled map), and norm_backward_plan's ``chunk,
+    n_partials, run_len, lanes, grid_partial, grid_finish, grid_apply, block, groups`` over the H1 W1 pixels of the raw map."""
+    return _plan("dsmil_stem_pool_bwd_plan", _STEM_BWD_PLAN_FIELDS, B, H1, W1, C)
+
+
+def stem_pool_backward_supported(B, H1, W1, C):
+    """True where dsmil_stem_pool_bwd takes the shape.  No device."""
+    return _native.lib().dsmil_stem_pool_bwd_workspace_bytes(B, H1, W1, C) > 0
+
+
+def stem_pool_backward(g, y, stats, win, ws=None):
+    """dsmil_stem_pool_bwd: g fp32 NHWC [B,Hp,Wp,C] = the gradient of maxpool3x3/2/1(relu(IN(y))), y the raw map [B,H1,W1,C],
+    ``stats`` = (mean, rstd) [B,C], ``win`` uint8 [B,Hp,Wp,C] as trunk32_stem_train returns it -> gy [B,H1,W1,C].
+    ``ws``: a caller's workspace (uint8, any contents); default a fresh one.  No host sync."""
+    g, y = _f32c(g, "g"), _f32c(y, "y")
+    if y.dim() != 4 or g.dim() != 4:
+        raise ValueError("g and y must be [B, H, W, C]")
+    B, H1, W1, C = y.shape
+    Hp, Wp = _conv_out(H1, W1, 3, 2, 1)
+    if tuple(g.shape) != (B, Hp, Wp, C):
+        raise ValueError(f"g is {tuple(g.shape)}, the pool of y gives {(B, Hp, Wp, C)}")
+    if not win.is_cuda or win.dtype != torch.uint8 or not win.is_contiguous() or win.shape != g.shape:
+        raise RuntimeError("win must be a contiguous uint8 CUDA(HIP) tensor of g's shape")
+    m, r = (_f32c(t, "stats") for t in stats)
+    if tuple(m.shape) != (B, C) or tuple(r.shape) != (B, C):
+        raise ValueError("statistics must be [B, C]")
+    L = _native.lib()
+    shape = (B, H1, W1, C)
+    need = _size_or_reason(L.dsmil_stem_pool_bwd_workspace_bytes(*shape), "dsmil_stem_pool_bwd_plan", "dsmil_stem_pool_bwd", *shape)
+    ws = _scratch(y.device, need, ws)
+    gy = torch.empty_like(y)
+    with torch.cuda.device(y.device):
+        rc = L.dsmil_stem_pool_bwd(_ptr(g), _ptr(y), _ptr(m), _ptr(r), _ptr(win), _ptr(gy), B, H1, W1, C, _ptr(ws), ws.numel(),
+                                   _stream(y.device))
+    _refused(rc, "dsmil_stem_pool_bwd")
+    return gy
 
 
 # ---------------------------------------------------------------------------------------------

@@ -97,7 +97,11 @@ class ResNet(nn.Module):
 
     # ---- torch-op graph (CPU tensors, BatchNorm, training) --------------------------------
     def _features_torch(self, x):
-        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        if getattr(self, "_native_stem", False):               # simclr.use_native_stem: opt-in, decided per call
+            from . import simclr
+            x = simclr.stem_forward(self, x)
+        else:
+            x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         return torch.flatten(self.avgpool(x), 1)
 

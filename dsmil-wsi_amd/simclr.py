@@ -477,3 +477,85 @@ def use_native_blocks(model):
         new.stride = m.stride
         return new
     return _swap_children(model, native_block_eligible, make)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# training the embedder: the stem on the native path.  The forward is ops.trunk32_stem_train (the inference stem's kernels on their
+# two-kernel route: the raw map, its statistics, the pooled map and each pool window's winner), the backward
+# ops.stem_pool_backward (csrc/stem_bwd.hip) and the conv's weight gradient.  No normalised map and no index map of torch's is
+# stored.  OPT-IN.
+# ---------------------------------------------------------------------------------------------------------------------------
+class _StemNative(torch.autograd.Function):
+    """pooled = maxpool3x3/2/1(relu(IN(conv7x7/2/3(x, w)))): x fp32 NCHW [B,3,H,W], the result fp32 NHWC [B,Hp,Wp,64]."""
+
+    @staticmethod
+    def forward(ctx, x, w):
+        pooled, y, (mean, rstd), win = ops.trunk32_stem_train(x, w)
+        ctx.save_for_backward(x, y, mean, rstd, win)
+        return pooled
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if ctx.needs_input_grad[0]:
+            raise NotImplementedError("the native stem gives no input gradient")
+        if not ctx.needs_input_grad[1]:
+            return None, None
+        x, y, mean, rstd, win = ctx.saved_tensors
+        gy = ops.stem_pool_backward(g.contiguous(), y, (mean, rstd), win)
+        return None, ops.conv_backward_weight(_nhwc(x), gy, 7, 2, 3)
+
+
+def _stem_eligible(x, w):
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and not x.requires_grad and
+            x.shape[1] == 3 and w.is_cuda and w.dtype == torch.float32 and w.device == x.device and w.is_contiguous() and
+            tuple(w.shape) == (64, 3, 7, 7)):
+        return False
+    B, _, H, W = x.shape
+    if min(B, H, W) < 1 or not ops.trunk32_stem_train_supported(B, H, W):
+        return False
+    if torch.is_grad_enabled() and w.requires_grad:
+        H1, W1 = ops._conv_out(H, W, 7, 2, 3)
+        return ops.stem_pool_backward_supported(B, H1, W1, 64) and ops.conv_backward_supported(3, 64, 7, 2, 3, B, H, W, "weight")
+    return True
+
+
+def native_stem(x, conv1_w):
+    """``maxpool3x3/2/1(relu(instance_norm(conv2d(x, conv1_w, stride 2, padding 3))))`` on the native path, for models that keep
+    the stem as entries of an ``nn.Sequential``: x fp32 NCHW [B,3,H,W] on the device, not requiring grad -> NCHW [B,64,Hp,Wp], a
+    view of the NHWC result (a following NativeBasicBlock copies nothing).  Raises where ``use_native_stem`` would take torch."""
+    if not _stem_eligible(x, conv1_w):
+        raise NotImplementedError("native_stem takes a 4-d fp32 CUDA(HIP) input that does not require grad, a contiguous fp32 "
+                                  "[64,3,7,7] weight on its device and a shape the stem entries take")
+    return _StemNative.apply(x.contiguous(), conv1_w).permute(0, 3, 1, 2)
+
+
+def _stem_modules_ok(model):
+    mp = model.maxpool
+    return (resnet._conv_is(model.conv1, 7, 2, 3) and model.conv1.in_channels == 3 and model.conv1.out_channels == 64 and
+            resnet._is_plain_instance_norm(model.bn1) and isinstance(model.relu, torch.nn.ReLU) and
+            isinstance(mp, torch.nn.MaxPool2d) and resnet._pair(mp.kernel_size) == (3, 3) and resnet._pair(mp.stride) == (2, 2) and
+            resnet._pair(mp.padding) == (1, 1) and resnet._pair(mp.dilation) == (1, 1) and not mp.ceil_mode and
+            not mp.return_indices)
+
+
+def stem_forward(model, x):
+    """What ``ResNet._features_torch`` runs for its stem once ``use_native_stem`` has marked the model: ``_StemNative`` where the
+    modules and the input are eligible, else the torch chain unchanged."""
+    if _stem_modules_ok(model) and _stem_eligible(x, model.conv1.weight):
+        return _StemNative.apply(x.contiguous(), model.conv1.weight).permute(0, 3, 1, 2)
+    return model.maxpool(model.relu(model.bn1(model.conv1(x))))
+
+
+def use_native_stem(model):
+    """Marks a ``resnet.ResNet`` (in place) so that its TRAINING forward sends ``maxpool(relu(bn1(conv1(x))))`` through
+    ``_StemNative`` when it is eligible: a 4-d fp32 CUDA input that does not require grad, a plain InstanceNorm ``bn1``, the
+    bias-free 7/2/3 ``conv1``, ``nn.ReLU``, ``MaxPool2d(3, 2, 1)`` (dilation 1, no ceil mode) and a shape the entries take;
+    everything else takes the torch chain unchanged.  Returns 1 where the model's stem modules are the eligible ones, else 0
+    (the mark is set either way; eligibility is decided per call).  No child module is added, removed or renamed, the Parameters
+    are the same objects, state_dict() is the same; resnet18_in_convs and IClassifier's native inference route are unaffected.
+    Composes with ``use_native_blocks`` and ``use_native_convs`` in any order."""
+    if not isinstance(model, resnet.ResNet):
+        raise TypeError("use_native_stem takes a resnet.ResNet")
+    model._native_stem = True
+    return int(_stem_modules_ok(model))

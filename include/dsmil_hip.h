@@ -1064,6 +1064,68 @@ int dsmil_norm_bwd(int32_t kind, const float* g, const float* out, const float* 
                    const float* yd, const float* md, const float* rd, float* gy, float* gyd, float* gres, int32_t B, int32_t HW,
                    int32_t C, void* ws, size_t ws_bytes, void* stream);
 
+/* The stem on the training path (csrc/resnet_fwd.hip, csrc/stem_bwd.hip): a forward that keeps what the backward needs, and the
+ * gradient of the RAW stem map from the gradient of pooled = maxpool3x3/2/1(relu((y - mean) rstd)).  fp32 NHWC maps, statistics
+ * [B,C] fp32 (biased variance, eps 1e-5, no affine), H1 = (H - 1) / 2 + 1 for the 7x7/2/3 conv and Hp = (H1 - 1) / 2 + 1 for the
+ * pool (the same for the widths).
+ *   dsmil_trunk32_stem_train   dsmil_trunk32_stem's InstanceNorm route on its two-kernel form (k_pack_stem_s6, k_stem_s6 writing
+ *                              the raw map, k_in_finalize_stem) and a pool pass that records the winners:
+ *                              x fp32 NCHW [B,3,H,W] or (x_is_u8_nhwc) uint8 NHWC, conv1_w OIHW [64,3,7,7] ->
+ *                              y [B,H1,W1,64] (the caller's buffer), mean / rstd [B,64], pooled [B,Hp,Wp,64], win [B,Hp,Wp,64] uint8.
+ *                              pooled, mean and rstd are bit-identical to dsmil_trunk32_stem's on the same input.
+ *     Winner rule, all fp32: a = fl(fl(y - mean) rstd).  The window of pooled pixel (oy, ox) is rows 2 oy - 1 .. 2 oy + 1 and
+ *     columns 2 ox - 1 .. 2 ox + 1, clipped to the map; win = dy * 3 + dx (0..8, dy = row - (2 oy - 1), dx = column - (2 ox - 1): the
+ *     position in the UNCLIPPED window, row-major) of the FIRST pixel in row-major order whose a equals the window's largest a —
+ *     a later value replaces the current one only if strictly greater, max_pool2d's rule.  The rule is on a, not on y: two
+ *     different y may round to one a.  Non-finite inputs are unspecified.
+ *     Checks in dsmil_trunk32_stem's order: DSMIL_E_INVALID (a null pointer, non-positive sizes), DSMIL_E_UNSUPPORTED (precision
+ *     other than 0 / 1; H or W < 32; B > 65535; B 3 H W or B H1 W1 64 >= 2^31), DSMIL_E_ALIGN (x off 4 bytes unless uint8,
+ *     conv1_w or win off 4, y / pooled / mean / rstd off 16, ws off 256), DSMIL_E_WORKSPACE.  The size query answers 0 for what
+ *     the entry refuses.
+ *   dsmil_stem_pool_bwd        g [B,Hp,Wp,C] = the gradient of pooled, y [B,H1,W1,C], mean / rstd [B,C], win [B,Hp,Wp,C] -> gy
+ *                              [B,H1,W1,C]:
+ *         q[n,p,c]  = sum over the windows whose winner is p of g[n,w,c]   if fl(fl(y - mean) rstd)[n,p,c] > 0, else 0
+ *         gy        = INB(q; y, mean, rstd)                                (the INB of dsmil_norm_bwd, the same fp32 arithmetic)
+ *     A GATHER over the pixels of y: a pixel lies in at most four windows — one per dimension for an even coordinate, two for an
+ *     odd one — and takes g of a window where win names its position; the (at most four) terms are added in window row-major
+ *     order starting from + 0, a window it did not win contributing an exact + 0.  Then, as dsmil_norm_bwd: x^ = fl(fl(y - mean)
+ *     rstd); the sums of q and of fma(q, x^) per (n, c); mean = sum / (H1 W1), a correctly rounded division; gy = fl(rstd
+ *     fma(-x^, mean(q x^), fl(q - mean q))).
+ *     Order.  The H1 W1 pixels of an image, row-major, are dealt to chunks of plan[CHUNK]; inside a chunk plan[LANES] threads per
+ *     channel each add every LANES-th pixel serially (at most plan[RUN_LEN] terms per accumulator), their sums are combined in a
+ *     fixed tree (xor shuffles inside a wave, then the waves through LDS in wave order) into one partial in ws; the
+ *     plan[PARTIALS] partials of an (n, c) are added in chunk order; the element pass then runs.  No atomics anywhere: two calls
+ *     on the same inputs are bit-identical, and a call never reads what another call left in ws.  An all-zero g and a channel
+ *     whose every element is masked give exact zeros.  win values that no pixel of the window holds select nothing.
+ *     Checks, all before the first launch, in this order: DSMIL_E_INVALID (non-positive sizes, a NULL pointer, gy sharing a
+ *     byte with an input); DSMIL_E_UNSUPPORTED (C % 4 != 0, C / 4 neither dividing 256 nor a multiple of it, C > 2048,
+ *     B H1 W1 C >= 2^31; the size function returns 0); DSMIL_E_ALIGN (g, y, mean, rstd or gy off 16 bytes, win off 4, ws off
+ *     256); DSMIL_E_WORKSPACE.  ws: device, 256-byte aligned, dsmil_stem_pool_bwd_workspace_bytes bytes, any contents.
+ *     dsmil_stem_pool_bwd_plan is a HOST function: out[DSMIL_STEM_BWD_PLAN_*], the rest 0.
+ * Asynchronous on `stream`; nothing is allocated.  Added without a change of DSMIL_ABI_VERSION (it stays 6, no existing signature
+ * moved): a caller finds them by symbol. */
+enum {
+    DSMIL_STEM_BWD_PLAN_HP = 0,            /* the pooled map: (H1 - 1) / 2 + 1 */
+    DSMIL_STEM_BWD_PLAN_WP = 1,
+    DSMIL_STEM_BWD_PLAN_CHUNK = 2,         /* pixels of y per chunk: 256, doubled while B chunks > 2048, 4096 at most */
+    DSMIL_STEM_BWD_PLAN_PARTIALS = 3,      /* partials per (n, c) and sum: ceil(H1 W1 / chunk) */
+    DSMIL_STEM_BWD_PLAN_RUN_LEN = 4,       /* the longest serial run of terms one accumulator adds: ceil(min(H1 W1, chunk) / lanes) */
+    DSMIL_STEM_BWD_PLAN_LANES = 5,         /* accumulators per channel and chunk, combined in a fixed tree: 256 / min(C / 4, 256) */
+    DSMIL_STEM_BWD_PLAN_GRID_PARTIAL = 6,  /* workgroups of the chunk sums: B * partials */
+    DSMIL_STEM_BWD_PLAN_GRID_FINISH = 7,   /* of the pass that adds the partials */
+    DSMIL_STEM_BWD_PLAN_GRID_APPLY = 8,    /* of the element pass: 8192 at most, grid stride beyond */
+    DSMIL_STEM_BWD_PLAN_BLOCK = 9,         /* threads per workgroup of every launch */
+    DSMIL_STEM_BWD_PLAN_GROUPS = 10        /* 4-channel groups per thread: 1, or 2 at C = 2048 */
+};
+size_t dsmil_trunk32_stem_train_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int dsmil_trunk32_stem_train(const void* x, int32_t x_is_u8_nhwc, const float* conv1_w, float* y, float* mean, float* rstd,
+                             float* pooled, uint8_t* win, int32_t B, int32_t H, int32_t W, int32_t precision, void* ws,
+                             size_t ws_bytes, void* stream);
+int dsmil_stem_pool_bwd_plan(int32_t B, int32_t H1, int32_t W1, int32_t C, int32_t out[16]);
+size_t dsmil_stem_pool_bwd_workspace_bytes(int32_t B, int32_t H1, int32_t W1, int32_t C);
+int dsmil_stem_pool_bwd(const float* g, const float* y, const float* mean, const float* rstd, const uint8_t* win, float* gy,
+                        int32_t B, int32_t H1, int32_t W1, int32_t C, void* ws, size_t ws_bytes, void* stream);
+
 /* Measurement hooks (bench.py's roofline leg; no reference counterpart).  While enabled, every
  * launch of a dominant kernel is bracketed by hipEventRecord on its own launch stream (up to 4096
  * launches per channel: 0 = k_query_attend of the aggregator, 1 = k_conv of the embedder);
