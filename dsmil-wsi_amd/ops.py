@@ -5,6 +5,7 @@ hot path happens in libdsmil_hip.so.  Functions raise if handed CPU tensors — 
 the nn.Modules (config 0, MUSK1 plumbing) never comes through this file.
 """
 import collections
+import copy
 import ctypes
 
 import numpy as np
@@ -119,9 +120,21 @@ class StreamPool:
         self.streams = [torch.cuda.Stream(device=self.device) for _ in range(max(1, int(n)))]
         self._i = 0
 
-    def run(self, fn, *args, **kwargs):
+    def next_stream(self):
+        """The next stream of the round-robin: the one place that deals."""
         s = self.streams[self._i % len(self.streams)]
         self._i += 1
+        return s
+
+    def dealer(self):
+        """A round-robin of its own over the same streams, from the first: for a caller whose deal must neither depend on nor
+        move this pool's count, and that orders its streams itself (next_stream, no wait per call)."""
+        d = copy.copy(self)
+        d._i = 0
+        return d
+
+    def run(self, fn, *args, **kwargs):
+        s = self.next_stream()
         s.wait_stream(torch.cuda.current_stream(self.device))   # inputs may have been produced on the caller's stream
         with torch.cuda.stream(s):
             return fn(*args, **kwargs)

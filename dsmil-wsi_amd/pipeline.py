@@ -11,8 +11,10 @@ result-preserving:
     ranks and reassembled by one all-gather (dist.py).
 """
 import glob
+import itertools
 import os
 import sys
+import time
 from collections import OrderedDict
 
 import numpy as np
@@ -113,29 +115,49 @@ def read_files(paths):
     return [buf[int(e - s_):int(e)] for s_, e in zip(sizes, ends)]
 
 
+def _read_tasks(tp, files):
+    """The reads of a chunk's files, submitted to the thread pool `tp` -> the chunk as _resolve takes it: one read_files task
+    per 64 files (a future per FILE cost 26 us to submit and as much to wait for — 105 + 150 ms of a 4 000-tile bag's 318), one
+    C call per task (no interpreter time per file)."""
+    return [tp.submit(read_files, files[j:j + 64]) for j in range(0, len(files), 64)]
+
+
 _decode_streams = {}
 
 
+def _resolve(chunk):
+    """A chunk's entries as bytes-likes: anything with .result() (a concurrent.futures-style lazy read) is resolved now; a result
+    that is a LIST stands for that many files."""
+    out = []
+    for b in chunk:
+        r = b.result() if hasattr(b, "result") else b
+        if isinstance(r, list):                           # (a read task's files)
+            out.extend(r)
+        else:
+            out.append(r)
+    return out
+
+
 class _ChunkDecoder:
-    """Device JPEG decode of a slide's chunks on a side stream, double-buffered.
-    decode(blobs) -> uint8 [n, H, W, 3] (a view of one of two staging buffers), enqueued on the decode stream; the CALLER's
-    current stream is made to wait for it.  release() — called when the consumer has ENQUEUED its work on the chunk — marks the
-    buffer: the decode that reuses it (two chunks later) waits for that point of the consumer's stream.
-    The stream has HIGH priority: (a) its own hardware queue — the runtime multiplexes a process's normal-priority streams over
+    """Device JPEG decode of a slide's chunks on side streams, `ahead` decodes in flight into `ahead + 1` staging buffers; the
+    whole staging-buffer protocol lives here.  decoded(chunks) hands out each chunk's uint8 [n, H, W, 3] images (a view of a
+    staging buffer) with the event its consumer has to wait for; release() — called when the consumer has ENQUEUED its work on
+    the chunk — marks the buffer: the decode that reuses it (`ahead + 1` chunks later) waits for that point of every stream that
+    read it; finish() joins the decode streams into the caller's.
+    The streams have HIGH priority: (a) their own hardware queue — the runtime multiplexes a process's normal-priority streams over
     four hardware queues, so a fifth stream created behind the embed pool's would share one with conv kernels and the ~11 ms
     decode launch would sit in line behind them (measured: 35.7 k instead of 55.5 k patches/s); (b) the dispatcher places the
     decode's few workgroups as soon as compute units free up."""
 
-    def __init__(self, device, decode_batch, stats=None, nbuf=2, nstreams=1):
+    def __init__(self, device, decode_batch, stats=None, ahead=1, nstreams=1):
         self.dev = torch.device(device)
         pool = _decode_streams.setdefault(str(self.dev), [])
         while len(pool) < nstreams:                       # (created once per process and device, high priority: see above)
             pool.append(torch.cuda.Stream(device=self.dev, priority=-1))
         self.dss = pool[:nstreams]
-        self.ds = self.dss[0]
-        self.decode_batch, self.stats = decode_batch, stats
-        self.bufs, self.free_ev = [None] * nbuf, [None] * nbuf
-        self.size, self.k, self.n, self.last = None, 0, 0, None
+        self.decode_batch, self.stats, self.ahead = decode_batch, stats, ahead
+        self.bufs, self.free_ev = [None] * (ahead + 1), [[] for _ in range(ahead + 1)]
+        self.size, self.k, self.n, self.held = None, 0, 0, None
 
     def begin(self, blobs):
         """Enqueue the decode of a chunk into the next staging buffer, on the next decode stream; no host wait
@@ -144,10 +166,9 @@ class _ChunkDecoder:
         self.k = (k + 1) % len(self.bufs)
         ds = self.dss[self.n % len(self.dss)]
         self.n += 1
-        def buffer_free():                                # the consumer's work on the chunk that used this buffer (one event, or
-            if self.free_ev[k] is not None:               # one per stream) — waited for BEHIND the files' host-to-device copies:
-                for e in (self.free_ev[k] if isinstance(self.free_ev[k], list) else [self.free_ev[k]]):   # a pageable copy
-                    ds.wait_event(e)                      # queued behind this wait held the host until the buffer was free
+        def buffer_free():                                # the consumer's work on the chunk that used this buffer (one event per
+            for e in self.free_ev[k]:                     # stream that read it) — waited for BEHIND the files' host-to-device
+                ds.wait_event(e)                          # copies: a pageable copy queued behind this wait held the host until the buffer was free
 
         with torch.cuda.stream(ds):                       # (the inputs are host bytes: nothing of the caller's stream to wait for)
             p = ops.jpeg_decode_begin(blobs, self.dev, size=self.size, out=self.bufs[k], before_launch=buffer_free)
@@ -170,25 +191,64 @@ class _ChunkDecoder:
                 ev.record(ds)
         return imgs, ev, k
 
-    def decode(self, blobs):
-        return self.end(self.begin(blobs))
+    def decoded(self, chunks):
+        """Generator over a sequence of chunks (lists of bytes-likes or lazy reads, _resolve; taken from `chunks` one at a time,
+        when their decode begins): `ahead` decodes in flight, each chunk's (imgs, event, item) in order.  The consumer makes every
+        stream that reads `imgs` wait for `event` and calls release(item) before it asks for the next chunk: only then does the
+        next decode begin, into the buffer that the chunk `ahead` chunks back was read from.  ahead = 1 on one decode stream is a
+        double buffer (decode chunk i + 1 under the consumer's work on chunk i)."""
+        it = iter(chunks)
+        pending = [self.begin(_resolve(c)) for c in itertools.islice(it, self.ahead)]
+        while pending:
+            self.held = self.end(pending.pop(0))
+            yield self.held[0], self.held[1], self.held
+            assert self.held is None, "release() a chunk before asking for the next one"
+            pending += [self.begin(_resolve(c)) for c in itertools.islice(it, 1)]
 
-    def acquire(self, item):
-        """Make the caller's current stream wait for a decode()'s result; returns the images."""
-        imgs, ev, k = item
-        cur = torch.cuda.current_stream(self.dev)
-        cur.wait_event(ev)
-        imgs.record_stream(cur)
-        return imgs
-
-    def release(self, item):
-        e = torch.cuda.Event()
-        e.record(torch.cuda.current_stream(self.dev))
-        self.free_ev[item[2]] = e
+    def release(self, item, streams=None):
+        """The work that reads this chunk is enqueued on `streams` (default: the current stream, the one the chunk was acquired
+        on): one event per stream, the only write of free_ev.  Streams named here get the allocator's mark for `imgs` too."""
+        imgs, _, k = item
+        self.free_ev[k] = []
+        for s_ in streams or [torch.cuda.current_stream(self.dev)]:
+            if streams:
+                imgs.record_stream(s_)
+            e = torch.cuda.Event()
+            e.record(s_)
+            self.free_ev[k].append(e)
+        self.held = None
 
     def finish(self):
+        """The caller's stream waits for every decode stream."""
         for ds in self.dss:
             torch.cuda.current_stream(self.dev).wait_stream(ds)
+
+
+def _decoded_batches(dec, chunks, batch_size, handed=None):
+    """The single-stream consumer of a _ChunkDecoder: the chunks' images as uint8 NHWC batches of `batch_size` for the CURRENT
+    stream, which waits for each chunk's decode; a chunk is released when the consumer has taken — i.e. enqueued its work on —
+    its last batch.  `handed()` runs when a chunk has been decoded, in front of its batches."""
+    for imgs, ev, item in dec.decoded(chunks):
+        if handed is not None:
+            handed()
+        cur = torch.cuda.current_stream(dec.dev)
+        cur.wait_event(ev)
+        imgs.record_stream(cur)
+        for o in range(0, imgs.shape[0], batch_size):
+            yield {"input": imgs[o:o + batch_size]}
+        dec.release(item)                                 # the consumer's work on this chunk is enqueued by now
+    dec.finish()
+
+
+def _join(pool, results, dec=None):
+    """Join a stream pool (and a decoder's streams) into the caller's stream, then mark `results` — produced on a pool stream,
+    consumed (and freed) on the caller's — for the allocator."""
+    pool.join()
+    if dec is not None:
+        dec.finish()
+    cur = torch.cuda.current_stream(pool.device)
+    for t in results:
+        t.record_stream(cur)
 
 
 @torch.no_grad()
@@ -208,33 +268,10 @@ def embed_jpeg_blobs(i_classifier, blobs, batch_size=256, decode_batch=2048, str
 
 
 def _embed_jpeg_chunks(i_classifier, chunks, batch_size, decode_batch, streams, dev, stats=None):
-    """embed_jpeg_blobs over a sequence of chunks (lists of bytes-likes; entries may be concurrent.futures-style lazily read:
-    anything with .result() is resolved when its chunk is decoded; a result that is a LIST stands for that many files)."""
-    def resolve(chunk):
-        out = []
-        for b in chunk:
-            r = b.result() if hasattr(b, "result") else b
-            if isinstance(r, list):                       # (a read task's files)
-                out.extend(r)
-            else:
-                out.append(r)
-        return out
-
-    pool = stream_pool(dev, streams) if streams > 1 else None
-    ahead = max(1, min(DECODE_AHEAD[0], len(chunks)))
-    dec = _ChunkDecoder(dev, decode_batch, stats, nbuf=2 if pool is None else ahead + 1, nstreams=1 if pool is None else DECODE_STREAMS[0])
-    fl, cl = [], []
-    if pool is None:
-        cur = dec.decode(resolve(chunks[0]))
-        for ci in range(len(chunks)):
-            imgs = dec.acquire(cur)
-            f, c = embed_tiles(i_classifier, imgs, batch_size, streams=1, device=dev)
-            dec.release(cur)
-            if ci + 1 < len(chunks):
-                cur = dec.decode(resolve(chunks[ci + 1]))
-            fl.append(f)
-            cl.append(c)
-        dec.finish()
+    """embed_jpeg_blobs over a sequence of chunks (lists of bytes-likes or lazy reads: _resolve)."""
+    if streams <= 1:                                      # batch by batch on the current stream, the next chunk's decode beside it
+        batches = _decoded_batches(_ChunkDecoder(dev, decode_batch, stats), chunks, batch_size)
+        fl, cl = zip(*[i_classifier(b["input"]) for b in batches])
         return torch.cat(fl), torch.cat(cl)
     # The batches of ALL chunks go round-robin over the pool's streams, and a pool stream waits for the DECODE of the chunk it
     # is about to read — not for the caller's stream: embed_tiles per chunk joined the pool into the caller's stream and the next
@@ -246,44 +283,26 @@ def _embed_jpeg_chunks(i_classifier, chunks, batch_size, decode_batch, streams, 
     # enqueued the chunk's ~500 launches, so the next decode started late and a 16-bit trunk (15 ms per 2 048 tiles) ran out of
     # decoded tiles: 115 ms per 10 000-tile slide against 75 ms from decoded tiles; now 98 ms (the first decode, which nothing
     # can hide, + ~10 ms of the decodes' share of the device).  The fp32-class trunk (31 ms per chunk) never waited: unchanged.
+    pool = stream_pool(dev, streams)
+    deal = pool.dealer()                                  # (from the pool's first stream, whatever pool.run has dealt before)
+    dec = _ChunkDecoder(dev, decode_batch, stats, max(1, min(DECODE_AHEAD[0], len(chunks))), DECODE_STREAMS[0])
+    fl, cl = [], []
     caller = torch.cuda.current_stream(dev)
     for s_ in pool.streams:
         s_.wait_stream(caller)                            # (weights / earlier work of the caller's stream)
-    pending, nxt = [], 0
-    while nxt < len(chunks) and len(pending) < ahead:
-        pending.append(dec.begin(resolve(chunks[nxt])))
-        nxt += 1
-    bi = 0
-    for ci in range(len(chunks)):
-        imgs, ev, k = dec.end(pending.pop(0))
+    for imgs, ev, item in dec.decoded(chunks):
         used = set()
         for lo in range(0, imgs.shape[0], batch_size):
-            s_ = pool.streams[bi % len(pool.streams)]
-            bi += 1
-            if id(s_) not in used:
+            s_ = deal.next_stream()
+            if s_ not in used:
                 s_.wait_event(ev)                         # this chunk's decode
-                used.add(id(s_))
+                used.add(s_)
             with torch.cuda.stream(s_):
                 f, c = i_classifier(imgs[lo:lo + batch_size])
             fl.append(f)
             cl.append(c)
-        done = []
-        for s_ in pool.streams:                           # the staging buffer is free when every stream is past this chunk
-            if id(s_) in used:
-                imgs.record_stream(s_)
-                e = torch.cuda.Event()
-                e.record(s_)
-                done.append(e)
-        dec.free_ev[k] = done
-        if nxt < len(chunks):
-            pending.append(dec.begin(resolve(chunks[nxt])))   # chunk ci + 2, into the buffer chunk ci - 1 was embedded from
-            nxt += 1
-    for s_ in pool.streams:
-        caller.wait_stream(s_)
-    for ds in dec.dss:
-        caller.wait_stream(ds)
-    for t in fl + cl:                                     # produced on a pool stream, consumed (and freed) on the caller's
-        t.record_stream(caller)
+        dec.release(item, [s_ for s_ in pool.streams if s_ in used])   # the staging buffer is free when every stream is past this chunk
+    _join(pool, fl + cl, dec)
     return torch.cat(fl), torch.cat(cl)
 
 
@@ -306,31 +325,17 @@ def gpu_decoded_batches(files, batch_size, device, io_threads=4, decode_batch=20
     PCIe bytes and without worker processes.  The next chunk is read and decoded (on the side stream of _ChunkDecoder) when the
     consumer has taken — i.e. enqueued its work on — the last batch of the current one."""
     from concurrent.futures import ThreadPoolExecutor
-
-    read = read_files                                     # (a task per 64 files, one C call per task: embed_files)
-
     files = list(files)
     if not files:
         return
     dec = _ChunkDecoder(device, decode_batch, stats)
-    with ThreadPoolExecutor(max_workers=max(1, int(io_threads))) as pool:
-        def start(chunk):
-            return [pool.submit(read, chunk[j:j + 64]) for j in range(0, len(chunk), 64)]
+    with ThreadPoolExecutor(max_workers=max(1, int(io_threads))) as tp:
+        todo = (files[i:i + decode_batch] for i in range(0, len(files), decode_batch))
+        reading = [_read_tasks(tp, next(todo))]
 
-        def collect(tasks):
-            return [b for t in tasks for b in t.result()]
-
-        chunks = [files[i:i + decode_batch] for i in range(0, len(files), decode_batch)]
-        cur = dec.decode(collect(start(chunks[0])))
-        for ci in range(len(chunks)):
-            pending = start(chunks[ci + 1]) if ci + 1 < len(chunks) else None   # (read while this chunk is consumed)
-            imgs = dec.acquire(cur)
-            for o in range(0, imgs.shape[0], batch_size):
-                yield {"input": imgs[o:o + batch_size]}
-            dec.release(cur)                              # the consumer's work on this chunk is enqueued by now
-            if pending is not None:
-                cur = dec.decode(collect(pending))
-        dec.finish()
+        def read_next():                                  # (read while this chunk is consumed)
+            reading[0] = _read_tasks(tp, next(todo, []))
+        yield from _decoded_batches(dec, (reading[0] for _ in range(0, len(files), decode_batch)), batch_size, read_next)
 
 
 @torch.no_grad()
@@ -355,10 +360,10 @@ def embed_files(i_classifier, files, batch_size=128, num_workers=4, device=None,
     feats_l, cls_l, keep_l = [], [], []
     # decoded uint8 images go to the GPU as they are when the native ResNet-18-IN stem will take them
     from .modules import resnet_convs_of
-    u8 = torch.device(device).type == "cuda" and resnet_convs_of(i_classifier.feature_extractor) is not None
+    on_gpu = torch.device(device).type == "cuda"
+    u8 = on_gpu and resnet_convs_of(i_classifier.feature_extractor) is not None
     filt = bg_threshold is not None
     F_, C_ = i_classifier.fc.in_features, i_classifier.fc.out_features
-    on_gpu = torch.device(device).type == "cuda"
 
     def embed(patches, keep_idx):
         if keep_idx is not None:
@@ -381,48 +386,48 @@ def embed_files(i_classifier, files, batch_size=128, num_workers=4, device=None,
 
     if gpu_decode is None:
         gpu_decode = GPU_DECODE[0]
-    if hi > lo and gpu_decode and u8 and on_gpu and not filt:
+    # The source of this shard's batches, decided once: the DataLoader, the device decode batch by batch on this stream (the
+    # background filter reads every batch's keep mask), or the device decode dealt to the stream pool
+    if hi <= lo:
+        batches = ()
+    elif not (gpu_decode and u8):
+        batches = patch_loader(files[lo:hi], batch_size, num_workers, False, uint8=u8 or filt)
+    elif filt:
+        batches = gpu_decoded_batches(files[lo:hi], batch_size, device, io_threads=max(1, num_workers), decode_batch=DECODE_BATCH[0])
+    else:
         # Round 6: the device-decode path deals its batches to the stream pool (the loop below embeds batch by batch on ONE
         # stream: ~59 k patches/s at bs 256 against 65 k on three) — the files of a chunk are read by a thread pool while the
         # chunk in front is decoded and embedded; same bytes, same batches, same features
         from concurrent.futures import ThreadPoolExecutor
-
-        read = read_files     # one task per 64 files (a future per FILE cost 26 us to submit and as much to wait for — 105 + 150
-        #                       ms of a 4 000-tile bag's 318), one C call per task (no interpreter time per file)
-
         mine = list(files[lo:hi])
         with ThreadPoolExecutor(max_workers=max(1, int(num_workers))) as tp:
-            chunks = [[tp.submit(read, mine[j:min(j + 64, i + DECODE_BATCH[0])]) for j in range(i, min(i + DECODE_BATCH[0], len(mine)), 64)]
-                      for i in range(0, len(mine), DECODE_BATCH[0])]
+            chunks = [_read_tasks(tp, mine[i:i + DECODE_BATCH[0]]) for i in range(0, len(mine), DECODE_BATCH[0])]   # (all up front)
             f_, c_ = _embed_jpeg_chunks(i_classifier, chunks, batch_size, DECODE_BATCH[0], EMBED_STREAMS[0], torch.device(device))
         feats_l.append(f_)
         cls_l.append(c_)
-    elif hi > lo:
-        pending = None
-        loader = (gpu_decoded_batches(files[lo:hi], batch_size, device, io_threads=max(1, num_workers), decode_batch=DECODE_BATCH[0])
-                  if gpu_decode and u8 and on_gpu
-                  else patch_loader(files[lo:hi], batch_size, num_workers, False, uint8=u8 or filt))
-        for batch in loader:
-            patches = batch["input"].to(device, non_blocking=True)
-            if not filt:
-                embed(patches, None)
-                continue
-            # the keep mask is computed on the device and read by the host ONE BATCH LATER, so the loader, the H2D copy and
-            # the embedder of the previous batch do not wait for it
-            keep = background_keep_mask(patches, edge_threshold=bg_threshold)
-            keep_l.append(keep)
-            if on_gpu:
-                keep_h = torch.empty(keep.shape, dtype=torch.bool, pin_memory=True)
-                keep_h.copy_(keep, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-            else:
-                keep_h, ev = keep, None
-            if pending is not None:
-                finish(pending)
-            pending = (patches, keep, keep_h, ev)
+        batches = ()
+    pending = None
+    for batch in batches:
+        patches = batch["input"].to(device, non_blocking=True)
+        if not filt:
+            embed(patches, None)
+            continue
+        # the keep mask is computed on the device and read by the host ONE BATCH LATER, so the loader, the H2D copy and
+        # the embedder of the previous batch do not wait for it
+        keep = background_keep_mask(patches, edge_threshold=bg_threshold)
+        keep_l.append(keep)
+        if on_gpu:
+            keep_h = torch.empty(keep.shape, dtype=torch.bool, pin_memory=True)
+            keep_h.copy_(keep, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        else:
+            keep_h, ev = keep, None
         if pending is not None:
             finish(pending)
+        pending = (patches, keep, keep_h, ev)
+    if pending is not None:
+        finish(pending)
     if feats_l:
         feats, classes = torch.cat(feats_l), torch.cat(cls_l)
     else:
@@ -759,7 +764,6 @@ def attention_maps(args, bags_list, milnet, colors=None, rng=None, embedder_low=
     compute_tree_feats reads, compute_feats.py:91-101); the [high || low] tree features go through
     ``milnet`` = MILNet(FCLayer(feats_size), BClassifier(feats_size)) and the map is painted at the high tiles'
     positions."""
-    from PIL import Image
     milnet.eval()
     rng = rng or np.random
     colors = colors or [rng.choice(range(256), size=3) for _ in range(args.num_classes)]
@@ -973,10 +977,7 @@ def embed_tiles(i_classifier, tiles, batch_size=256, streams=3, device=None):
         fl.append(f)
         cl.append(c)
     if pool is not None:
-        pool.join()
-        cur = torch.cuda.current_stream(dev)
-        for t in fl + cl:                               # produced on a pool stream, consumed (and freed) on this one
-            t.record_stream(cur)
+        _join(pool, fl + cl)
     if not fl:
         return (torch.zeros((0, i_classifier.fc.in_features), device=dev),
                 torch.zeros((0, i_classifier.fc.out_features), device=dev))
@@ -1015,11 +1016,8 @@ def _multiscale_embed_pooled(wsi, embedder_low, embedder_high, tile, factor, lo,
 
     fl = pool.run(low_all)
     fh = [pool.run(high_batch, a, min(a + ppb, hi - lo)) for a in range(0, hi - lo, ppb)]
-    pool.join()
-    cur = torch.cuda.current_stream(dev)
-    for t in fh + fl:
-        t.record_stream(cur)
-    cy = torch.arange(factor, device=dev).repeat_interleave(factor)
+    _join(pool, fh + fl)
+    cy =torch.arange(factor, device=dev).repeat_interleave(factor)
     cx = torch.arange(factor, device=dev).repeat(factor)
     rows = (ly[:, None] * factor + cy[None, :]).reshape(-1)
     cols = (lx[:, None] * factor + cx[None, :]).reshape(-1)
@@ -1052,7 +1050,6 @@ def multiscale_bag(wsi, embedder_low, embedder_high, tree_fusion="cat", tile=224
     if world > 1 or ddist._FORCE[0]:
         # shards are whole low tiles: rows per rank = f*f x its low-tile count; ONE collective carries the tree rows and
         # the (row, col) grid positions the map needs (int64, bit-cast into float lanes)
-        import time
         t0 = time.perf_counter()
         sizes = [(ddist.shard_range(L, r, world)[1] - ddist.shard_range(L, r, world)[0]) * ch for r in range(world)]
         tree, pos = ddist.all_gather_packed([tree, pos], sizes)

@@ -247,3 +247,49 @@ def test_decodes_in_flight_with_host_decoded_files_and_a_chunk_without_a_device_
     o1, r1 = ops.jpeg_decode_end(p1)
     assert (r0, r1) == (1, 4)
     assert torch.equal(o0, tiles[:8]) and torch.equal(o1, tiles[28:32])
+
+
+def test_single_stream_chunk_path_equals_pillow_rows():
+    """embed_jpeg_blobs(streams=1): batch by batch on the caller's stream, the next chunk's decode beside it (the double buffer
+    of _ChunkDecoder, one decode ahead).  29 files in chunks of 4 — the short last chunk holds ONE file — one of them
+    progressive (Pillow inside the same call): rows bit-identical to the embedding of Pillow's decode, in order."""
+    from test_resnet_gpu import _build
+    from dsmil_wsi_amd import pipeline as pl
+    rng = np.random.default_rng(53)
+    blobs = [_jpeg(_img(rng, 96, 96, i % 3), quality=70, progressive=i == 9) for i in range(29)]
+    ic, _ = _build(seed=13)
+    ic = ic.cuda()
+    tiles = torch.from_numpy(np.stack([_pil(b) for b in blobs])).cuda()
+    ref_f, ref_c = pl.embed_tiles(ic, tiles, 4, streams=1)
+    st = {}
+    f, c = pl.embed_jpeg_blobs(ic, blobs, batch_size=4, decode_batch=4, streams=1, stats=st)
+    torch.cuda.synchronize()
+    assert st == {"device": 28, "pillow": 1}
+    assert torch.equal(ref_f, f) and torch.equal(ref_c, c)
+
+
+def test_device_decode_with_the_background_filter_equals_the_loader(tmp_path):
+    """embed_files(gpu_decode=True, bg_threshold=15, return_keep=True): the device decode batch by batch (gpu_decoded_batches,
+    four chunks of 8 files, the last one short) under the one-batch-late read of the keep mask — rows, logits and keep mask
+    bit-identical to the DataLoader path's.  Every fourth tile is flat (background): the filter keeps some and drops some."""
+    import os
+    from test_resnet_gpu import _build
+    from dsmil_wsi_amd import pipeline as pl
+    rng = np.random.default_rng(31)
+    files = []
+    for i in range(29):
+        a = _img(rng, 96, 96, i % 4) if i % 4 < 3 else np.full((96, 96, 3), 200 + rng.integers(0, 40)).astype(np.uint8)
+        files.append(os.path.join(tmp_path, f"{i}_{i + 1}.jpeg"))
+        with open(files[-1], "wb") as fh:
+            fh.write(_jpeg(a, quality=70))
+    ic, _ = _build(seed=11)
+    ic = ic.cuda()
+    old = pl.DECODE_BATCH[0]
+    pl.DECODE_BATCH[0] = 8
+    try:
+        ref_f, ref_c, ref_k = pl.embed_files(ic, files, batch_size=4, num_workers=0, gpu_decode=False, bg_threshold=15, return_keep=True)
+        got_f, got_c, got_k = pl.embed_files(ic, files, batch_size=4, num_workers=2, gpu_decode=True, bg_threshold=15, return_keep=True)
+    finally:
+        pl.DECODE_BATCH[0] = old
+    assert 0 < int(ref_k.sum()) < len(files) and ref_f.shape[0] == int(ref_k.sum())
+    assert np.array_equal(ref_k, got_k) and torch.equal(ref_f, got_f) and torch.equal(ref_c, got_c)
