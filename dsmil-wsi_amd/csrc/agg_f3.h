@@ -6,9 +6,8 @@
 // (the launch on 64 workgroups takes the same time per tile as on 256).  Taller tiles would amortise the weights but do not
 // fit LDS.  k_attend_bf16_res (agg_res.h) showed the way out for bf16 bags: one wave per SIMD may hold 512 registers, so
 //   * one 256-thread workgroup per CU; wave w keeps the A fragments of ITS 32 hidden / query units for the whole launch:
-//     W1 (two fp16 planes x K <= 512: up to 256 registers) in the ACCUMULATOR half of the register file, W2's first plane in
-//     VGPRs (its second plane too up to K = 256; at K = 512 it is re-read from L2 once per tile, under the hidden-layer
-//     exchange: 32 KB).  The MFMAs are inline asm with "a" weight operands and VGPR accumulators (k_attend_bf16_res's recipe;
+//     W1 (two fp16 planes x K <= 512: up to 256 registers) in the ACCUMULATOR half of the register file, W2's two planes in
+//     VGPRs (64 registers).  The MFMAs are inline asm with "a" weight operands and VGPR accumulators (k_attend_bf16_res's recipe;
 //     f3_mfma_* below say why).  No W1 byte moves after the prologue, so a short tile costs nothing:
 //   * tile = 32 rows, TWO plane buffers in LDS (row-major [row][plane][K] fp16 with a 16-B pad: B fragments, the value
 //     sum's k-contiguous reads and the cut's writes are all conflict-free).  While tile t is in GEMM 1, every wave cuts
@@ -120,14 +119,17 @@ __device__ __forceinline__ bool f3_fetch(const AttendArgs& a, int tiles_per_bag,
 // a.nonlinear, a.C <= 2, vals == feats.  Workgroup g owns the tile items [g per_wg, (g + 1) per_wg) of the (bag, tile) list
 // (tiles_per_bag items per bag) and writes partial slot g + bag for every bag it touches.
 template <int NK1, bool TWO, int DBG = 0>   // DBG 1 (experiment builds, with DSMIL_EXPT=64: k_finish skipped): wave 0 stores s_memtime stamps
-                                            // of the phase boundaries into the tile's 32 rows of A (C = 1; tools/f3_stamps.py)
+                                            // of the phase boundaries into the tile's 32 rows of A (C = 1; tools/f3_stamps.py);
+                                            // DBG 2 .. 6: timing-only ablations, wrong results by design (profiles/r06_forms/f3_ablations.txt)
 __global__ __launch_bounds__(F3_THREADS, 1) void k_attend_f3(AttendArgs a, const float* __restrict__ rowmax, int tiles_per_bag,
                                                              int n_items, int per_wg) {
     static_assert(NK1 % 4 == 0 && NK1 >= 4 && NK1 <= 16, "K a multiple of 128 up to 512");
     constexpr int K = 32 * NK1, NKS = 2 * NK1, NG = NK1 / 2;   // NK1 32-k steps of GEMM 1 (NKS 16-k chunks of the image); 64-k groups of the feature ring
     constexpr int RB = f3_row_bytes(K), BUF = F3_BM * RB;
     constexpr int NC = TWO ? 2 : 1;
-    constexpr bool W2_STREAM = NK1 > 8;
+    constexpr bool STAMPS = DBG >= 1 && DBG <= 5;          // (DBG 6 keeps the product's instruction stream)
+    constexpr bool W2_P1 = DBG != 6;                       // (DBG 6: timing without W2's second plane — neither held nor loaded, the first plane stands in for it)
+    constexpr bool W2_STREAM = STAMPS;                     // (the stamp forms, K = 512 only, hold 32 registers of stamps: they re-read W2's second plane from L2 once per tile, as the product did at K = 512 when they were measured)
     constexpr int NMOVE = 2;                               // ring groups refilled from GEMM 2's gaps instead of GEMM 1's (measured, kernel time relative to k_attend_f2 on the same box: 1 -> 0.84, 2 -> 0.81, 3 -> 0.83, 4 -> 0.83)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     char* sX = reinterpret_cast<char*>(smem);              // [2 buffers][32 rows][plane 2][K] fp16 + pad
@@ -178,16 +180,17 @@ __global__ __launch_bounds__(F3_THREADS, 1) void k_attend_f3(AttendArgs a, const
         for (int uh = 0; uh < 2; ++uh)
 #pragma unroll
             for (int p = 0; p < 2; ++p) w1[s][uh][p].f = wimg[f3_frag_slot(s, 2 * wave + uh, p, lane)];
-    // (W2's second plane is NOT resident at K = 512: 2 x 256 + 64 weight registers left too few for the LDS reads of GEMM 1 to
-    // run ahead of their MFMAs — hipcc issued every read right in front of its MFMA.  Its 32 KB per tile come from L2 behind
-    // GEMM 1, under the hidden-layer exchange.)
+    // (W2's second plane is resident at every K.  At K = 512 it used to be re-read from L2 behind GEMM 1 of every tile, from the
+    // time when 2 x 256 + 64 weight registers left hipcc too few to keep GEMM 1's LDS reads ahead of their MFMAs; the reads
+    // now stand where the sched_barriers of GEMM 1 put them, and the kernel takes 500 (C = 1) / 508 (C = 2) of 512 registers
+    // without scratch — DESIGN.md §3 "W2's second plane resident at K = 512" has the compile check that must keep holding.)
     const f32x4* w2p1 = wimg + f3_frag_slot(NK1, 2 * wave, 1, lane);   // + 2 st chunks + 8 uh
 #pragma unroll
     for (int st = 0; st < 4; ++st)
 #pragma unroll
         for (int uh = 0; uh < 2; ++uh) {
             w2[st][uh][0].f = wimg[f3_frag_slot(NK1 + st, 2 * wave + uh, 0, lane)];
-            if constexpr (!W2_STREAM) w2[st][uh][1].f = w2p1[(long long)2 * st * F2_CHUNK_F4 + 8 * uh];
+            if constexpr (W2_P1 && !W2_STREAM) w2[st][uh][1].f = w2p1[(long long)2 * st * F2_CHUNK_F4 + 8 * uh];
         }
     const float ia1 = trailer[0], ia2 = trailer[1];
     // Bound of a row's hidden layer: relu(W1 x + b)[j] <= ||W1[j]||_1 max|x| + |b[j]|, and max|x| < 2^14 / (row scale).  The
@@ -279,8 +282,8 @@ __global__ __launch_bounds__(F3_THREADS, 1) void k_attend_f3(AttendArgs a, const
             } else if constexpr (ph == 9) {
                 *reinterpret_cast<f32x4*>(d + 2 * K) = cutf[1].f;
             } else if constexpr (ph == 10) {
-                // (the last NMOVE groups are refilled from GEMM 2's gaps: the loads of W2's second plane are issued between the
-                // two GEMMs, and the in-order vmcnt wait for them would otherwise include HBM loads a few hundred cycles old)
+                // (the last NMOVE groups are refilled from GEMM 2's gaps: placed when W2's second plane was still loaded between
+                // the two GEMMs at K = 512 and its in-order vmcnt wait would have included these HBM loads; kept as measured)
                 if constexpr (DBG != 4 && c < NG - NMOVE) fill(refill_src, c);   // (DBG 4: timing without the refills)
             }
         }
@@ -328,7 +331,7 @@ __global__ __launch_bounds__(F3_THREADS, 1) void k_attend_f3(AttendArgs a, const
 #pragma unroll
     for (int i = 0; i < 16; ++i) stamps[i] = 0;
     auto STAMP = [&](int i) {
-        if constexpr (DBG >= 1) {                         // (pinned: hipcc otherwise sinks work past the counter read)
+        if constexpr (STAMPS) {                           // (pinned: hipcc otherwise sinks work past the counter read)
             __builtin_amdgcn_sched_barrier(0);
             asm volatile("s_waitcnt vmcnt(63) lgkmcnt(0)" ::: "memory");
             stamps[i] = __builtin_readcyclecounter();
@@ -452,7 +455,7 @@ __global__ __launch_bounds__(F3_THREADS, 1) void k_attend_f3(AttendArgs a, const
                 f3_static_for<0, 12>([&](auto j_c) {
                     constexpr int j = decltype(j_c)::value;
                     constexpr int pr = j / 4, uh = (j >> 1) & 1, rh = j & 1;
-                    constexpr int pa = pr == 0 ? 1 : 0, pb = pr == 1 ? 1 : 0;
+                    constexpr int pa = pr == 0 && W2_P1 ? 1 : 0, pb = pr == 1 ? 1 : 0;
                     __builtin_amdgcn_sched_barrier(0);
                     if constexpr (st == 0 && pr == 0) f3_mfma_v0(Qacc[uh][rh], w2[st][uh][pa].f, hs[st % 2][rh][pb].f);
                     else f3_mfma_v(Qacc[uh][rh], w2[st][uh][pa].f, hs[st % 2][rh][pb].f);
@@ -506,7 +509,7 @@ __global__ __launch_bounds__(F3_THREADS, 1) void k_attend_f3(AttendArgs a, const
                 const float s = ((quad(0) + quad(4)) + (quad(8) + quad(12))) * scale;
                 const float p = valid ? expf(s - m_bag[c]) : 0.f;
                 if (hi == 0) l_run[c] += p;
-                if (DBG == 0 && wave == 0 && hi == 0 && valid) a.scores[(cur.off0 + grow) * (long long)a.C + c] = s;
+                if ((DBG == 0 || DBG == 6) && wave == 0 && hi == 0 && valid) a.scores[(cur.off0 + grow) * (long long)a.C + c] = s;
                 if (hi == 0) sPw[c * F3_BM + l31] = p * rinv;
             }
         }
@@ -531,7 +534,7 @@ __global__ __launch_bounds__(F3_THREADS, 1) void k_attend_f3(AttendArgs a, const
             }
         }
         STAMP(9);
-        if constexpr (DBG >= 1) {
+        if constexpr (STAMPS) {
             if (tid == 0 && !TWO && cur.row0 + F3_BM <= cur.Nb) {
                 unsigned long long* so = reinterpret_cast<unsigned long long*>(a.scores + (cur.off0 + cur.row0));
 #pragma unroll
@@ -571,7 +574,7 @@ __global__ __launch_bounds__(F3_THREADS, 1) void k_attend_f3(AttendArgs a, const
             reset_acc();
         }
         STAMP(13);
-        if constexpr (DBG >= 1) {
+        if constexpr (STAMPS) {
             if (tid == 0 && !TWO && cur.row0 + F3_BM <= cur.Nb)
                 reinterpret_cast<unsigned long long*>(a.scores + (cur.off0 + cur.row0))[13] = stamps[13];
         }

@@ -1718,7 +1718,7 @@ Attended launch_f3(const AttendArgs& a, const float* rowmax, long long max_rows,
     }
 #ifdef DSMIL_EXPERIMENTS
 #define F3_DBG(n) case n: fn = k_attend_f3<16, false, n>; break;
-    if (a.K == 512 && a.C == 1) switch (expt().f3_dbg) { F3_DBG(1) F3_DBG(2) F3_DBG(3) F3_DBG(4) F3_DBG(5) default: break; }
+    if (a.K == 512 && a.C == 1) switch (expt().f3_dbg) { F3_DBG(1) F3_DBG(2) F3_DBG(3) F3_DBG(4) F3_DBG(5) F3_DBG(6) default: break; }
 #undef F3_DBG
 #endif
     return launch_runs(fn, F3_THREADS, f3_lds_bytes(a.K), F3_BM, F3_MAX_WG, 0, a, max_rows, total_rows, n_bags, st, rowmax);
